@@ -1,6 +1,12 @@
 """Headline benchmark: chain-updates/sec on the GMRF smoother (BASELINE.json configs[2]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, conditions the device and runs the W warm-up steps, times the K steps and prints the line.
+--dump-outputs DIR also writes what the last timed step stored (b, lambda, tau, log_post) as DIR/<name>.npy.  --full
+adds everything else the benchmark measures, all after the headline and never part of `value`: the repeats of the K-step
+run (`config.repeats`), the CPU baseline, the other BASELINE configs (`config.secondary`) and, for N > 1, the store
+gathers and the other scaling mode.
 
 For N > 1 the ranks are one process per GPU under torch.distributed.run (RCCL); started directly with
 --gpus N > 1 (no WORLD_SIZE in the environment) the script launches that itself as a child process, before
@@ -15,15 +21,15 @@ from the in-kernel Philox stream; all inputs are resident in HBM before the time
 Chains are independent, so ranks share nothing during sampling; the only collective is the gather of
 the per-chain traces and stores at the end, outside the timed region.  --scaling strong (default, the
 headline `value`; BASELINE.json's metric is "1024 chains ... at 1/2/4/8 GPUs", BASELINE.md section 3 "chains
-sharded evenly"): 1024 chains in all.  --scaling weak: every GPU runs 1024 chains.  For N > 1 the default run
+sharded evenly"): 1024 chains in all.  --scaling weak: every GPU runs 1024 chains.  For N > 1 a --full run
 measures the other mode as well, after the headline, and reports it in the same JSON line (`other_scaling`).
 
 Every timed run explains itself (`config.diagnostics`): the library's launch log (host clock around every kernel
 launch of the run), the in-kernel sweep clock (entry and exit of every (sweep, chain) workgroup on the device's
 constant-rate counter) and the deltas of the slow-path counters, reduced to: when the host issued, when the device
 started, how long the sweeps took (median, maximum, which chain), whether slow sweeps were single chains or the whole
-device at once -- so a slow run says where its time went.  After the headline and its repeats the other BASELINE
-configs run for a bounded time each and are attached under `config.secondary` (never part of `value`).
+device at once -- so a slow run says where its time went.  With --full, after the headline and its repeats the other
+BASELINE configs run for a bounded time each and are attached under `config.secondary` (never part of `value`).
 """
 
 import argparse
@@ -43,6 +49,15 @@ CHAINS_PER_GPU = 1024
 ALG_BYTES_PER_CHAIN_UPDATE = 40 * N_NODES  # d,t written+read (32n) + x written (8n)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 STORE_SLABS_MAX = 256  # stored iterations kept resident (ring); 82 MB each at 1024 x 10 000
+DUMP_B_MAX = 1 << 22  # entries of the last draw of b that --dump-outputs writes at most (32 MB in f64; the headline's b has 10.24 M)
+
+
+def dump_index(chains, n):
+    """Flat (chain-major) indices of the entries of b that --dump-outputs writes: all of them up to DUMP_B_MAX, beyond that
+    a fixed seeded sample, so that two builds run with the same arguments write the same entries."""
+    if chains * n <= DUMP_B_MAX:
+        return None
+    return np.sort(np.random.default_rng(0).choice(chains * n, DUMP_B_MAX, replace=False))
 
 
 def gmrf_problem(n):
@@ -146,6 +161,14 @@ class GmrfSweep:
         if kernel_events is not None:
             kernel_events[1].record()
         self.it += 1
+
+    def last_outputs(self, b_index=None):
+        """Device copies of what the last step stored: the draw b (the entries at the flat indices b_index, or all), lambda,
+        tau and log_post of every chain -- copies, because later steps overwrite the store ring."""
+        slot = (self.it - 1) % self.n_store
+        b = self.store_b[slot].reshape(-1)
+        return {"b": b.clone() if b_index is None else b[b_index], "lambda": self.store_lam[slot].clone(),
+                "tau": self.store_tau[slot].clone(), "log_post": self.store_lp[slot].clone()}
 
 
 def cpu_baseline(n, seconds_budget=12.0):
@@ -258,24 +281,31 @@ def main():
     ap.add_argument("--chains", type=int, default=None, help="chains per GPU (weak) / in all (strong); default: the config's")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="strong (default; BASELINE's metric): --chains in all, sharded evenly over the GPUs; weak: --chains per GPU")
-    ap.add_argument("--one-mode", action="store_true", help="N > 1: do not measure the other scaling mode as well")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: its repeats, cpu_baseline, cfg2 / cfg4 / cfg5 (N = 1), the store "
+                         "gathers and the other scaling mode (N > 1); a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step stored as DIR/<name>.npy (f64): b (every entry up to 4 Mi of them, "
+                         "else a fixed seeded sample, chain-major), lambda, tau, log_post; rank 0's chains for N > 1")
+    ap.add_argument("--one-mode", action="store_true", help="N > 1 with --full: do not measure the other scaling mode as well")
     ap.add_argument("--condition-sweeps", type=int, default=4096,
                     help="untimed device conditioning before the W warm-up steps: this many sweeps of the same kernel on the same "
                          "chains (a FIXED count: state, draw indices and check values are the same on every box), so that a short "
                          "run does not time the clock ramp out of the idle power state (first ~10 ms of load); ends with a dress "
                          "rehearsal of the timed run (event pair + K sweeps + read-back of the diagnostics)")
     ap.add_argument("--secondary-ms", type=float, default=1000.0,
-                    help="N = 1: after the headline, run cfg2 / cfg4 / cfg5 for about this long each and attach them under "
-                         "config.secondary (0 = skip)")
+                    help="N = 1 with --full: after the headline, run cfg2 / cfg4 / cfg5 for about this long each and attach "
+                         "them under config.secondary (0 = skip)")
     ap.add_argument("--repeat-ms", type=float, default=250.0,
-                    help="after the headline, repeat the K-step run until this much time has been measured (spread report)")
+                    help="with --full: after the headline, repeat the K-step run until this much time has been measured "
+                         "(spread report)")
     ap.add_argument("--collective-timeout", type=float, default=240.0,
                     help="N > 1: seconds the gathers and the second scaling mode may take after the headline before rank 0 prints "
                          "the line without them and all ranks leave (0 = wait for ever)")
     ap.add_argument("--no-library-gather", action="store_true",
-                    help="N > 1 on GPUs: do not time the store gather through the library's own RCCL collective as well")
+                    help="N > 1 on GPUs with --full: do not time the store gather through the library's own RCCL collective as well")
     ap.add_argument("--nodes", type=int, default=N_NODES)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (of --full, and of --config cfg2|cfg4|cfg5)")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--no-sweep-clock", action="store_true", help="diagnostic: without the in-kernel sweep clock (one 16-byte store per workgroup and sweep)")
     ap.add_argument("--python-loop", action="store_true", help="issue every sweep from Python instead of omc_gmrf_run")
@@ -295,6 +325,8 @@ def main():
     args = ap.parse_args()
 
     if args.config != "cfg3":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the headline config (cfg3) only")
         from benchmarks import secondary
 
         if args.steps == 200 and args.config == "cfg5":
@@ -519,6 +551,11 @@ def main():
         # NaN-filled store arrays are before its loop, mcmc.py:88-95).  A FIXED number of sweeps, so that the chains'
         # state, every draw index and the check values are the same on every box and in every run; the last K of them
         # are a dress rehearsal of the timed run (same call, same events, same read-back).
+        b_index = None
+        if args.dump_outputs and diagnostics:  # (set up here: no host work between the headline and its repeats)
+            b_index = dump_index(C, n)
+            if b_index is not None:
+                b_index = torch.from_numpy(b_index).to("cuda")
         rehearsal = None
         if c_loop and args.condition_sweeps > 0 and not (diagnostics and args.stamps):
             # First everything the timed run's bookkeeping touches for the first time in this process (the events' first
@@ -544,9 +581,12 @@ def main():
         sweep.eng.check_status()
 
         dt, kern_ms, raw0 = timed()
+        outputs = sweep.last_outputs(b_index) if args.dump_outputs and diagnostics else None
         sweep.eng.check_status()
         # spread: the same K-step run again (every rank the same count: the loop bound comes from rank-agreed dt)
-        reps = int(min(20, max(0, np.ceil(args.repeat_ms * 1e-3 / max(dt, 1e-6)) - 1))) if not (diagnostics and args.stamps) else 0
+        reps = 0
+        if args.full and not (diagnostics and args.stamps):
+            reps = int(min(20, max(0, np.ceil(args.repeat_ms * 1e-3 / max(dt, 1e-6)) - 1)))
         rep_ms, rep_kern, raws = [1e3 * dt / args.steps], [kern_ms], [raw0]
         for _ in range(reps):
             d, k, rw = timed()
@@ -573,7 +613,7 @@ def main():
                   "sweep_ms_median_per_run": [g.get("sweep_ms", {}).get("median") for g in rep_diag],
                   "reenter_abi_ok": sweep.eng.counter("reenter_abi_ok") if c_loop else None}
         return {"mode": mode, "C": C, "dt": dt, "kern_ms": kern_ms, "sweep": sweep, "stamps": stamps, "spread": spread,
-                "n_store": n_store, "diagnostics": report}
+                "n_store": n_store, "diagnostics": report, "outputs": outputs}
 
     def make_line(lam_mean, trace_error, gather_info, other):
         """the bench line of this run (rank 0), with whatever of the collective part is known"""
@@ -647,6 +687,11 @@ def main():
 
     m = measure(args.scaling, diagnostics=True)
     sweep, C, dt, n_store, stamps = m["sweep"], m["C"], m["dt"], m["n_store"], m["stamps"]
+    if m["outputs"] is not None and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in m["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.cpu().numpy())
+        del m["outputs"]
 
     # The headline is measured.  What follows for N > 1 -- the library's own RCCL communicator, the gathers, the other scaling
     # mode -- has never met real multi-GPU hardware in this repository (one-GPU boxes; gloo rehearsals only), and a collective
@@ -697,7 +742,7 @@ def main():
     # ... and of the sample store itself: timed on a bounded part (the last <= 8 stored iterations of b,
     # 82 MB each per rank at 1024 chains) so the run stays short; reported next to the headline, never inside it
     gather_info = None
-    if dist is not None:
+    if dist is not None and args.full:
         try:
             from openmcmc_amd.parallel import gather_chains
 
@@ -758,7 +803,7 @@ def main():
     other = None
     if comm is not None:
         comm.close()
-    if world > 1 and not args.one_mode and not args.stamps:
+    if world > 1 and args.full and not args.one_mode and not args.stamps:
         del sweep
         m["sweep"] = None
         torch.cuda.empty_cache()
@@ -773,9 +818,9 @@ def main():
         watchdog.cancel()
     if rank == 0:
         out = make_line(lam_mean, trace_error, gather_info, other)
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(n)
-        if world == 1 and args.secondary_ms > 0 and not args.stamps:
+        if world == 1 and args.full and args.secondary_ms > 0 and not args.stamps:
             # the other BASELINE configs, bounded, after everything the headline needs has been measured
             m["sweep"] = None
             del sweep

@@ -20,8 +20,8 @@ fi
 if [ "$what" = all ] || [ "$what" = bench ]; then
   step "bench (driver's command)" &&
   timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_steps20.json 2> $out/bench_steps20.err &&
-  step "bench (default)" &&
-  timeout -k 10 300 python3 bench.py > $out/bench.json 2> $out/bench.err &&
+  step "bench (--full)" &&
+  timeout -k 10 300 python3 bench.py --full > $out/bench.json 2> $out/bench.err &&
   python3 - $out <<'EOF'
 import json, sys
 for f in ("bench_steps20.json", "bench.json"):

@@ -5,7 +5,7 @@
 out=${1:-gpurun_out/r04a}
 mkdir -p $out
 set -o pipefail
-run() { name=$1; shift; timeout -k 10 200 python3 bench.py "$@" --no-cpu --secondary-ms 0 > $out/$name.json 2> $out/$name.err || { echo "$name failed"; tail -5 $out/$name.err; exit 1; }
+run() { name=$1; shift; timeout -k 10 200 python3 bench.py --full "$@" --no-cpu --secondary-ms 0 > $out/$name.json 2> $out/$name.err || { echo "$name failed"; tail -5 $out/$name.err; exit 1; }
   python3 - $out/$name.json $name <<'P'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,8 +8,8 @@ export TMPDIR=/tmp
 set -o pipefail
 step() { echo "== $(date +%T) $*" | tee -a $out/progress.log; }
 root=$PWD
-step "two gloo ranks on one GPU: bench.py --gpus 2 (driver's command)" &&
-OMC_BENCH_BACKEND=gloo timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 5 > $out/bench_gpus2.json 2> $out/bench_gpus2.err; echo "exit code $?" | tee -a $out/progress.log
+step "two gloo ranks on one GPU: bench.py --gpus 2 --full" &&
+OMC_BENCH_BACKEND=gloo timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --full --steps 20 --warmup 5 > $out/bench_gpus2.json 2> $out/bench_gpus2.err; echo "exit code $?" | tee -a $out/progress.log
 python3 - $out/bench_gpus2.json <<'P'
 import json, sys
 lines = [l for l in open(sys.argv[1]).read().splitlines() if l.startswith("{")]

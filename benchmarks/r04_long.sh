@@ -4,7 +4,7 @@ out=${1:-gpurun_out/r04n}
 mkdir -p $out
 export TMPDIR=/tmp
 root=$PWD
-OMC_BENCH_BACKEND=gloo timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 2 --steps 20 --warmup 5 > $out/gpus2.json 2> $out/gpus2.err; echo "exit $?"
+OMC_BENCH_BACKEND=gloo timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 2 --full --steps 20 --warmup 5 > $out/gpus2.json 2> $out/gpus2.err; echo "exit $?"
 python3 - $out/gpus2.json <<'P'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -2,7 +2,7 @@
 # quick configuration probes of the headline kernel (kernel us per sweep)
 out=${1:-gpurun_out/r04i}
 mkdir -p $out
-run() { name=$1; shift; timeout -k 10 200 python3 bench.py "$@" --no-cpu --secondary-ms 0 --repeat-ms 100 > $out/$name.json 2> $out/$name.err || { echo "$name failed"; tail -3 $out/$name.err; return 0; }
+run() { name=$1; shift; timeout -k 10 200 python3 bench.py --full "$@" --no-cpu --secondary-ms 0 --repeat-ms 100 > $out/$name.json 2> $out/$name.err || { echo "$name failed"; tail -3 $out/$name.err; return 0; }
   python3 - $out/$name.json $name <<'P'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/strong}
 mkdir -p $out
 for c in 1024 512 256 128 64; do
-  timeout -k 10 120 python3 bench.py --chains $c --steps 200 --warmup 20 --no-cpu --secondary-ms 0 --repeat-ms 100 > $out/chains_$c.json 2> $out/chains_$c.err || { echo "chains $c failed"; tail -5 $out/chains_$c.err; exit 1; }
+  timeout -k 10 120 python3 bench.py --full --chains $c --steps 200 --warmup 20 --no-cpu --secondary-ms 0 --repeat-ms 100 > $out/chains_$c.json 2> $out/chains_$c.err || { echo "chains $c failed"; tail -5 $out/chains_$c.err; exit 1; }
   python3 - $out/chains_$c.json $c <<'P'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
