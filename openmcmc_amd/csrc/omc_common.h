@@ -116,7 +116,19 @@ extern "C" omc_status omc_gram_mfma_launch(omc_ctx* ctx, int64_t n, int64_t p, c
 //   ctr = (block, draw_index_lo, global_chain_lo, purpose<<24 | global_chain_hi(8b)<<16 | draw_index_hi(16b))
 // so a draw is a pure function of (seed, global chain id, draw_index, position): independent of
 // launch geometry and of how chains are sharded over GPUs.
+// Field map of the counter as the library fills it (tests/test_stream_map.py checks that no two draws share one):
+//   purpose       ctr3 bits 24-31: OMC_RNG_* below
+//   global chain  ctr2 = bits 0-31, ctr3 bits 16-23 = bits 32-39 (chains < 2^40)
+//   draw index    ctr1 = bits 0-31, ctr3 bits 0-15 = bits 32-47:
+//                   bits  0-39  sweep draw t * n_samplers + position (sweeps < 2^32, positions < 2^8; the fused run of
+//                               omc_tridiag.hip makes the same numbers: its sweep draw plus the block's position)
+//                   bit  40     prior draw of the start value: (1 << 40) + position (mcmc.py)
+//                   bits 44-47  `sub`, several draws of one purpose under one draw index (Gamma.rvs, Normal columns)
+//   block         ctr0: position within the draw.  A Gamma(a) draw reads blocks 0 .. OMC_GAMMA_BLOCKS - 1; mixture
+//                 component k of k_mixture_normal_gamma adds (k + 1) << OMC_COMPONENT_SHIFT (k < 255), so its
+//                 blocks lie above those of every plain gamma draw of the same draw index.
 enum : uint32_t { OMC_RNG_NORMAL = 0, OMC_RNG_GAMMA = 1, OMC_RNG_UNIFORM = 2, OMC_RNG_RAW = 3 };
+enum : uint32_t { OMC_GAMMA_BLOCKS = 513, OMC_COMPONENT_SHIFT = 24 };  // 1 + 2 x 256 attempts; see the field map above
 
 struct omc_rng_key {
   uint32_t k0, k1;    // seed
@@ -395,14 +407,16 @@ __host__ __device__ inline void omc_normal_pair(uint4 w, double& n0, double& n1)
 // Attempt j (j = 0, 1, ...) consumes blocks 1+2j (two N(0,1) candidates) and 2+2j (their two
 // uniforms); block 0 feeds the a < 1 boost Gamma(a) = Gamma(a+1) U^(1/a).  The draw is the first
 // accepted candidate in (attempt, candidate) order, so evaluating attempts on different lanes and
-// taking the lowest accepted one gives the same value as the serial loop.
+// taking the lowest accepted one gives the same value as the serial loop.  `block0` moves the whole draw up the block
+// counter (mixture components, see the field map above).
 struct omc_gamma_prep { double d, cst, boost; };
 
-__device__ __forceinline__ omc_gamma_prep omc_gamma_prepare(const omc_rng_key& key, int64_t gc, double a) {
+__device__ __forceinline__ omc_gamma_prep omc_gamma_prepare(const omc_rng_key& key, int64_t gc, double a,
+                                                            uint32_t block0 = 0u) {
   omc_gamma_prep p;
   p.boost = 1.0;
   if (a < 1.0) {
-    const uint4 w = omc_rng_block(key, gc, 0u);
+    const uint4 w = omc_rng_block(key, gc, block0);
     p.boost = exp(omc_log_unit(omc_u53(w.x, w.y)) / a);
     a += 1.0;
   }
@@ -426,19 +440,20 @@ __device__ __forceinline__ bool omc_gamma_candidate(const omc_gamma_prep& p, dou
 
 // one attempt: returns true and the Gamma(a,1) value if one of its two candidates is accepted
 __device__ __forceinline__ bool omc_gamma_attempt(const omc_rng_key& key, int64_t gc, const omc_gamma_prep& p,
-                                                  uint32_t attempt, double& value) {
+                                                  uint32_t attempt, double& value, uint32_t block0 = 0u) {
   double x0, x1;
-  omc_normal_pair(omc_rng_block(key, gc, 1u + 2u * attempt), x0, x1);
-  const uint4 w = omc_rng_block(key, gc, 2u + 2u * attempt);
+  omc_normal_pair(omc_rng_block(key, gc, block0 + 1u + 2u * attempt), x0, x1);
+  const uint4 w = omc_rng_block(key, gc, block0 + 2u + 2u * attempt);
   if (omc_gamma_candidate(p, x0, omc_u53(w.x, w.y), value)) return true;
   return omc_gamma_candidate(p, x1, omc_u53(w.z, w.w), value);
 }
 
-__device__ inline double omc_standard_gamma(const omc_rng_key& key, int64_t gc, double a, bool* failed) {
-  const omc_gamma_prep p = omc_gamma_prepare(key, gc, a);
+__device__ inline double omc_standard_gamma(const omc_rng_key& key, int64_t gc, double a, bool* failed,
+                                            uint32_t block0 = 0u) {
+  const omc_gamma_prep p = omc_gamma_prepare(key, gc, a, block0);
   double v;
   for (uint32_t attempt = 0; attempt < 256; ++attempt)
-    if (omc_gamma_attempt(key, gc, p, attempt, v)) return v;
+    if (omc_gamma_attempt(key, gc, p, attempt, v, block0)) return v;
   *failed = true;
   return p.boost * p.d;
 }

@@ -3,6 +3,14 @@
 
 #include "omc_common.h"
 
+// log Gamma(shape, rate) density at v (lnorm = shape log rate - lgamma(shape)), as scipy.stats.gamma.logpdf: at v = 0 the
+// density is +inf for shape < 1, rate for shape = 1 and 0 for shape > 1; -inf below 0
+__device__ __forceinline__ double gamma_logpdf_at(double v, double shape, double rate, double lnorm) {
+  if (v > 0.0) return lnorm + (shape - 1.0) * log(v) - rate * v;
+  if (v == 0.0) return (shape < 1.0) ? INFINITY : (shape == 1.0 ? lnorm : -INFINITY);
+  return -INFINITY;
+}
+
 __global__ void k_normal_gamma(int64_t C, int64_t chain_offset, double a0, double b0, double half_npos,
                                const double* quad, const double* g_inject, omc_rng_key key, double* out,
                                long long* bad) {
@@ -46,9 +54,7 @@ __global__ void k_log_post_sum(int64_t C, LogpArgs P, double host_const, double*
       const double ld = (q.logdet_mult == 1.0) ? q.logdet[0] : q.logdet[0] * q.logdet_mult;
       lp = 0.5 * (q.n * log(s) + ld - q.n * 1.8378770664093453 - s * q.quad[c]);
     } else {
-      const double v = q.x[c];
-      lp = (v > 0.0) ? P.lnorm[i] + (q.shape - 1.0) * log(v) - q.rate * v : -INFINITY;
-      if (v == 0.0 && q.shape == 1.0) lp = P.lnorm[i];
+      lp = gamma_logpdf_at(q.x[c], q.shape, q.rate, P.lnorm[i]);
     }
     acc = (i == 0) ? lp : acc + lp;
   }
@@ -59,9 +65,7 @@ __global__ void k_gamma_logpdf(int64_t C, const double* x, double shape, double 
                                int accumulate) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double v = x[c];
-  double lp = (v > 0.0) ? lnorm + (shape - 1.0) * log(v) - rate * v : -INFINITY;
-  if (v == 0.0 && shape == 1.0) lp = lnorm;
+  const double lp = gamma_logpdf_at(x[c], shape, rate, lnorm);
   out[c] = accumulate ? out[c] + lp : lp;
 }
 
@@ -391,10 +395,7 @@ __global__ void k_gamma_logpdf_ragged(int64_t C, int64_t kmax, const double* x, 
   const int64_t k = count ? (int64_t)count[c] : kmax;
   double lp = 0.0;
   for (int64_t j = last_only ? (k > 0 ? k - 1 : 0) : 0; j < k; ++j) {
-    const double v = x[c * kmax + j];
-    double t = (v > 0.0) ? lnorm + (shape - 1.0) * log(v) - rate * v : -INFINITY;
-    if (v == 0.0 && shape == 1.0) t = lnorm;
-    lp += t;
+    lp += gamma_logpdf_at(x[c * kmax + j], shape, rate, lnorm);
   }
   out[c] = accumulate ? out[c] + lp : lp;
 }
@@ -501,10 +502,8 @@ __global__ void __launch_bounds__(256) k_mixture_normal_gamma(int64_t C, int64_t
   double g;
   if (g_in) {
     g = g_in[t];
-  } else {  // component k draws from its own stream: the draw index carries k in bits 32-39 of the 48-bit index
-    omc_rng_key kk = key;
-    kk.c3_base |= ((uint32_t)k & 0xffu) << 8;
-    g = omc_standard_gamma(kk, chain_offset + c, a, &failed);
+  } else {  // component k draws from its own blocks of the draw's stream (field map in omc_common.h)
+    g = omc_standard_gamma(key, chain_offset + c, a, &failed, ((uint32_t)k + 1u) << OMC_COMPONENT_SHIFT);
   }
   out[t] = g * scale;
   if (failed) atomicMin((unsigned long long*)bad, (unsigned long long)c);
@@ -516,8 +515,8 @@ __global__ void k_gamma_logpdf_vec(int64_t C, int64_t K, const double* x, const 
   if (c >= C) return;
   double lp = 0.0;
   for (int64_t k = 0; k < K; ++k) {
-    const double v = x[c * K + k], a = shape[k], b = rate[k];
-    lp += (v > 0.0) ? a * log(b) - lgamma(a) + (a - 1.0) * log(v) - b * v : -INFINITY;
+    const double a = shape[k], b = rate[k];
+    lp += gamma_logpdf_at(x[c * K + k], a, b, a * log(b) - lgamma(a));
   }
   out[c] = accumulate ? out[c] + lp : lp;
 }

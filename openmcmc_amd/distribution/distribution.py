@@ -152,6 +152,9 @@ class Gamma(Distribution):
             v = x.data  # (C, p, n_rep)
             lp = (a * float(np.log(b)) - float(_lgamma(a))) + (a - 1.0) * torch.log(v) - b * v
             lp = torch.where(v > 0, lp, torch.full_like(lp, float("-inf")))
+            # at 0 as stats.gamma.logpdf: +inf for shape < 1, log(rate) for shape 1, -inf above
+            at0 = float("inf") if a < 1.0 else (float(np.log(b)) if a == 1.0 else float("-inf"))
+            lp = torch.where(v == 0, torch.full_like(lp, at0), lp)
             if x.ragged is not None:
                 axis = x.ragged[1]
                 live = torch.arange(v.shape[1 + axis], device=v.device).reshape((1, -1, 1) if axis == 0 else (1, 1, -1)) \

@@ -66,3 +66,47 @@ def normals(seed, draw_index, global_chain, n):
     out = np.empty(2 * nb)
     out[0::2], out[1::2] = normal_pairs(x, y, z, w)
     return out[:n]
+
+
+# ---- counters and the gamma stream (omc_common.h: field map, omc_standard_gamma) ----------------------------------
+GAMMA_BLOCKS = 513      # blocks one Gamma(a) draw may read: 0 (the a < 1 boost) and 1 + 2j, 2 + 2j for 256 attempts
+COMPONENT_SHIFT = 24    # mixture component k of k_mixture_normal_gamma reads blocks from (k + 1) << COMPONENT_SHIFT
+
+
+def counter(purpose, draw_index, global_chain, block=0):
+    """(c0, c1, c2, c3) of omc_rng_block() as Python ints."""
+    c3 = (PURPOSE[purpose] << 24) | (((global_chain >> 32) & 0xFF) << 16) | ((draw_index >> 32) & 0xFFFF)
+    return block & 0xFFFFFFFF, draw_index & 0xFFFFFFFF, global_chain & 0xFFFFFFFF, c3
+
+
+def mixture_component_block0(k):
+    """First block of mixture component k's gamma draw (k_mixture_normal_gamma)."""
+    return (int(k) + 1) << COMPONENT_SHIFT
+
+
+def standard_gamma(seed, draw_index, global_chain, a, block0=0):
+    """Gamma(a, 1) of omc_standard_gamma (Marsaglia & Tsang, the device's block order).  Libm-level differences from the
+    device only: a candidate lying within an ulp of its acceptance bound could be decided the other way."""
+    def block(b):
+        return [np.uint32(v[0]) for v in rng_blocks(seed, draw_index, "gamma", global_chain, [block0 + b])]
+
+    boost = 1.0
+    if a < 1.0:
+        x, y, _, _ = block(0)
+        boost = np.exp(np.log(u53(np.array([x]), np.array([y]))[0]) / a)
+        a += 1.0
+    d = a - 1.0 / 3.0
+    cst = 1.0 / np.sqrt(9.0 * d)
+    for attempt in range(256):
+        n0, n1 = normal_pairs(*block(1 + 2 * attempt))
+        x, y, z, w = block(2 + 2 * attempt)
+        uu = u53(np.array([x, z]), np.array([y, w]))
+        for xn, u in ((float(n0), uu[0]), (float(n1), uu[1])):
+            v = 1.0 + cst * xn
+            if not v > 0.0:
+                continue
+            v = v * v * v
+            x2 = xn * xn
+            if u < 1.0 - 0.0331 * x2 * x2 or np.log(u) < 0.5 * x2 + d * ((1.0 - v) + np.log(v)):
+                return boost * d * v
+    return boost * d

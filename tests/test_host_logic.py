@@ -250,3 +250,21 @@ def test_null_distribution_and_band_recognition():
     assert tri.band is None and tri.band_rows().shape == (2, 5)
     with pytest.raises(ValueError):
         band_storage(sparse.csc_matrix(np.triu(np.ones((8, 8)), 0) * (np.abs(np.subtract.outer(np.arange(8), np.arange(8))) <= 2)), 8)
+
+
+@pytest.mark.parametrize("shape", [1e-3, 0.5, 1.0, 2.0, 1e6])
+def test_gamma_log_p_by_observation_at_zero_matches_scipy(shape):
+    """The torch branch of Gamma.log_p (per-replicate densities of a per-chain response, run here on CPU tensors): at x = 0
+    +inf for shape < 1, log(rate) for shape 1, -inf above, as stats.gamma.logpdf."""
+    import torch
+    from scipy import stats
+
+    from openmcmc_amd.chains import ChainArray
+
+    x = np.array([[[0.0, 1.5, -0.0]], [[-1.0, 0.0, 1e-300]]])
+    st = {"x": ChainArray(torch.tensor(x)), "a": np.array([[shape]]), "b": np.array([[2.0]])}
+    got = Gamma("x", "a", "b").log_p(st, by_observation=True).numpy()
+    ref = stats.gamma.logpdf(x[:, 0, :], shape, scale=0.5)
+    inf = ~np.isfinite(ref)
+    assert np.array_equal(got[inf], ref[inf])
+    assert np.allclose(got[~inf], ref[~inf], rtol=1e-13, atol=0.0)
