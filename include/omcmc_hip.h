@@ -99,6 +99,7 @@ omc_status omc_ctx_synchronize(omc_ctx* ctx);
  * 2: without a barrier in front of the restart, the scales handed from sweep to sweep through LDS; by default the
  * restarting form is taken when the chains fill the CUs in whole rounds and the (sweep, chain) grid otherwise, an
  * explicit setting holds for every chain count),
+ * "diag_algo" (0 auto; 1 the short-series form of omc_store_rhat_ess, M <= 64; 2 its blocks of lags),
  * "band_algo" (0 auto; 1 narrow bands one lane per chain in ONE piece; 2 one workgroup per chain, a column per step; 3 one
  * workgroup per chain in blocks of 16 columns, the next block factorised ahead, the window update on the matrix cores -- auto
  * takes it from w = 9, and from w = 4 on up to 3072 chains, where a lane per chain leaves the SIMDs to lone waves), "band_seg_overlap"
@@ -726,6 +727,25 @@ omc_status omc_store_moments(omc_ctx* ctx, int64_t n_iter, int64_t size, const d
  * no copy of the store), then numpy's interpolation operation by operation: results are bit-equal to np.quantile's.      */
 omc_status omc_store_quantiles(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int32_t pooled, int32_t n_q,
                                const double* q, int32_t omit_nan, double* out);
+/* Convergence diagnostics of the same store, per element k: split R-hat and the effective sample size.  N = n_iter >= 4
+ * (else OMC_INVALID_ARG), M = N / 2; every chain gives two series, its first and its last M iterations (the middle draw of
+ * an odd N is dropped): J = 2 C series x_j[0..M).
+ *   m_j = mean(x_j),  g_j(t) = (1/M) sum_{i=0}^{M-1-t} (x_j[i] - m_j)(x_j[i+t] - m_j),
+ *   W = mean_j g_j(0) M / (M - 1),  B_M = var(m_0 .. m_{J-1}, ddof 1),  var_plus = W (M - 1) / M + B_M,
+ *   rhat = sqrt(var_plus / W),  rho(t) = 1 - (W - mean_j g_j(t)) / var_plus;
+ *   ess = J M / max(tau, 1 / log10(J M)), tau = -1 + 2 sum(r[0 .. max_t]) + r[max_t + 1] from Geyer's initial monotone
+ *   sequence r on rho (initial positive pairs while t < M - 3, then a running minimum of the pair sums), as ArviZ's
+ *   ess(method="mean").
+ *   Any NaN draw of element k (any chain, any iteration): rhat = ess = NaN.  Every split draw equal: ess = J M, rhat = NaN.
+ *   Every series constant but the series differ (W == 0 < B_M): rhat = +inf.
+ *   rhat_out, ess_out [size]; lag_out [size] = max_t + 1, the lags the element's sequence used (0 where it was not run:
+ *   NaN or constant elements); any output may be NULL.
+ * Direct lag sums on the device, one lane per (series, element): M <= 64 reads the store once, longer series read it
+ * 1 + 1 + 2 (ceil((max_t + 2) / 32) - 1) times (the means, then blocks of 32 lags until every element's sequence has ended;
+ * the host reads one word per block).  Option "diag_algo" (0 auto; 1 the short-series form, M <= 64 only; 2 blocks of
+ * lags) forces a form: same results to rounding.  Deterministic: repeated calls are bit-equal.                    */
+omc_status omc_store_rhat_ess(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store,
+                              double* rhat_out, double* ess_out, int32_t* lag_out);
 /* Thinned copy of the store for a thinned gather: out[j] = store[first + j * every] (slabs of C * size doubles),
  * j = 0 .. ceil((n_iter - first) / every) - 1 (that count is left in *n_out when n_out is not NULL, host).           */
 omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int64_t first, int64_t every,

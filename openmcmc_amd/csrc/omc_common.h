@@ -64,6 +64,7 @@ struct omc_ctx {
   int tridiag_perturb_ppb;  // tests only: relative error (parts per billion) put on the Moebius start values of the segment joins
   int tridiag_generic;  // 1: never take the structure-specialised instantiation of the segmented kernel (tests)
   int band_algo;  // 0 auto, 1 lane-per-chain in one piece (narrow bands), 2 workgroup-per-chain
+  int diag_algo;  // omc_store_rhat_ess: 0 auto, 1 short-series form (M <= 64), 2 blocks of lags
   int band_seg_overlap;  // segmented lane kernel: columns of warm-up before a segment (default 192)
   int band_seg_count;    // segmented lane kernel: number of segments (0 = chosen for the SIMDs; tuning and tests)
   int band_blocked_threads;  // blocked band kernel: 0 = form chosen by what fits a CU; 512, 4, 8 force one (A/B, tests; omc_bandwide.hip)

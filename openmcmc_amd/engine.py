@@ -1119,6 +1119,20 @@ class Engine:
                                       qs.ctypes.data_as(C.POINTER(C.c_double)), int(bool(omit_nan)), self._p(out)))
         return out
 
+    def store_rhat_ess(self, store):
+        """Split R-hat and effective sample size of every element of a device store (n_iter, C, size), computed on the
+        device (omc_store_rhat_ess): (rhat, ess, lags) as device tensors of shape (size,), lags int32 = the lags the
+        element's Geyer sequence used.  n_iter >= 4."""
+        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
+            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        n_iter, _, size = store.shape
+        if n_iter < 4:
+            raise ValueError("split R-hat and ESS need at least 4 stored iterations")
+        rhat, ess = self.empty(size), self.empty(size)
+        lags = _torch().empty(size, dtype=_torch().int32, device=self.device)
+        check(lib.omc_store_rhat_ess(self._ctx, n_iter, size, self._p(store), self._p(rhat), self._p(ess), lags.data_ptr()))
+        return rhat, ess, lags
+
     def store_thin(self, store, every, first=0):
         """store[first::every] of a device store (n_iter, C, ...) as a packed device tensor (one launch)."""
         if store.dim() < 2 or store.shape[1] != self.n_chains or not store.is_contiguous():

@@ -385,6 +385,20 @@ class MCMC:
         t = t.unsqueeze(-1) if t.dim() == 2 else t.reshape(t.shape[0], t.shape[1], -1)
         return self.engine.store_quantiles(t.contiguous(), q, pooled=pooled, omit_nan=omit_nan).cpu().numpy()
 
+    def diagnostics(self, key):
+        """Convergence diagnostics of store[key], computed on the device (no gather of the store): a dict of host arrays
+        of shape (size,) -- "rhat" (split R-hat), "ess" (effective sample size, Geyer's initial monotone sequence as
+        ArviZ's ess(method="mean")) and "mcse_mean" (pooled sd / sqrt(ess)).  Every chain is split into its first and last
+        halves; an element with a NaN draw (the padding of variable-size parameters) gives NaN.  Under a sharded multi-GPU
+        run these are diagnostics of this rank's chains only."""
+        self._whole_store_on_device("diagnostics")
+        t = self.store[key]
+        t = (t.unsqueeze(-1) if t.dim() == 2 else t.reshape(t.shape[0], t.shape[1], -1)).contiguous()
+        rhat, ess, _ = self.engine.store_rhat_ess(t)
+        _, var = self.engine.store_moments(t, pooled=True)
+        rhat, ess, var = rhat.cpu().numpy(), ess.cpu().numpy(), var.cpu().numpy()
+        return {"rhat": rhat, "ess": ess, "mcse_mean": np.sqrt(var) / np.sqrt(ess)}
+
     def _thinned(self, every):
         """{key: device tensor (ceil(n_iter / every), C, ...)}: every `every`-th stored iteration, packed on the device"""
         self._whole_store_on_device("a thinned transfer")
