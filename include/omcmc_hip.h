@@ -474,7 +474,8 @@ omc_status omc_band_matvec_chain(omc_ctx* ctx, int64_t n, int64_t w, const doubl
  * the untruncated entry points; lower / upper: device [n] (NULL = unbounded on that side).
  * u_inject [C][ld_u] injected uniforms; in-kernel uniforms are Philox blocks i/2 of (seed, chain, draw_index).
  * The scan is sequential in i by definition, the parallelism is over chains (tridiagonal: one lane per chain;
- * dense: one wave per chain, p <= 8192).                                                                    */
+ * dense: one wave per chain, p <= 8192).  omc_dense_gibbs_truncated takes terms->diag_chain: Q_c gets the per-chain
+ * diagonal of a truncated mixture prior (parameter.py:501) and its prec * mean arrives through rhs_chain.                */
 omc_status omc_tridiag_gibbs_truncated(omc_ctx* ctx, int64_t n, const omc_tridiag_terms* terms,
                                        const double* rhs_chain, int64_t ld_rhs, const double* lower,
                                        const double* upper, const double* u_inject, int64_t ld_u,
@@ -612,6 +613,19 @@ omc_status omc_small_sample_canonical(omc_ctx* ctx, int64_t kmax, const double* 
                                       const double* count, const double* z_inject, uint64_t draw_index,
                                       double* x, double* mu);
 
+/* The same operator under domain limits (sampler.py:194-205 -> gmrf.gibbs_canonical_truncated_normal, gmrf.py:201-266):
+ * a truncated mixture prior on a ragged parameter (a cfg5 basis with beta >= 0).  ONE scan of single-site updates in natural
+ * order on the live block of x [C][kmax], in place (the scan starts from x):
+ *   x_i ~ N_[lower, upper]( (b_i - Q_i. x + Q_ii x_i) / Q_ii, 1/Q_ii ),  x_j already updated for j < i;
+ * count[c] == 1 takes the reference's p == 1 branch (mean = b / Q); count[c] == 0 leaves the chain at 0; entries at and
+ * beyond count[c] are written as 0.  lower / upper: scalars (-inf / +inf = open on that side).  u_inject [C][kmax]
+ * uniforms; NULL: Philox blocks i/2 of (seed, chain, draw_index), purpose OMC_RNG_UNIFORM, as the other truncated scans.
+ * A non-positive Q_ii latches the chain.  kmax <= 64.                                                              */
+omc_status omc_small_gibbs_truncated(omc_ctx* ctx, int64_t kmax, const double* gram, const double* gram_rhs,
+                                     const double* lik_scale, const double* prior_prec, const double* prior_mean,
+                                     const double* count, double lower, double upper, const double* u_inject,
+                                     uint64_t draw_index, double* x);
+
 /* Per-chain small SPD matrices A [C][k][k] (k <= 64): Av_out[c] = A_c v_c, quad_out[c] = v_c' A_c v_c, logdet_out[c] =
  * log det A_c by the natural-order Cholesky (a non-positive pivot latches the chain); any output may be NULL.  The pieces
  * of ManifoldMALA's proposal for a Hessian that depends on the parameter (metropolis_hastings.py:325-373): Lambda x,
@@ -667,6 +681,11 @@ omc_status omc_uniform_draw(omc_ctx* ctx, int64_t p, const double* lower, const 
                             uint64_t draw_index, uint32_t sub, double* out);
 omc_status omc_diag_gauss_logpdf(omc_ctx* ctx, int64_t kmax, const double* x, const double* mean, const double* prec,
                                  const double* count, double* out, int32_t accumulate);
+/* omc_diag_gauss_logpdf of a mixture Normal with domain limits (location_scale.py:162-188): the same value, and -inf for a
+ * chain with a LIVE element (index < count[c]) below lower or above upper; the padding is not looked at.  lower / upper:
+ * scalars (-inf / +inf = open).  One launch.                                                                      */
+omc_status omc_diag_gauss_logpdf_limits(omc_ctx* ctx, int64_t kmax, const double* x, const double* mean, const double* prec,
+                                        const double* count, double lower, double upper, double* out, int32_t accumulate);
 /* Mixture models: a parameter vector whose prior mean / precision are picked per element
  * by a categorical allocation (parameter.py:376-538), the allocation's conditional draw and the per-component
  * precision update.

@@ -189,6 +189,9 @@ SIGNATURES = {
     "omc_centered_rowdot": (i32, [C.c_void_p, i64, c_dp, i64, c_dp, c_dp, i64, c_dp, c_dp]),
     "omc_uniform_draw": (i32, [C.c_void_p, i64, c_dp, c_dp, c_dp, u64, u32, c_dp]),
     "omc_diag_gauss_logpdf": (i32, [C.c_void_p, i64, c_dp, c_dp, c_dp, c_dp, c_dp, i32]),
+    "omc_diag_gauss_logpdf_limits": (i32, [C.c_void_p, i64, c_dp, c_dp, c_dp, c_dp, C.c_double, C.c_double, c_dp, i32]),
+    "omc_small_gibbs_truncated": (
+        i32, [C.c_void_p, i64, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_double, C.c_double, c_dp, u64, c_dp]),
     "omc_gamma_logpdf_ragged": (i32, [C.c_void_p, i64, c_dp, c_dp, C.c_double, C.c_double, i32, c_dp, i32]),
     "omc_diag_gauss_grad": (i32, [C.c_void_p, i64, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "omc_poisson_logpmf": (i32, [C.c_void_p, c_dp, C.c_double, c_dp, i32]),

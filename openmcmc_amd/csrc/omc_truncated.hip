@@ -362,6 +362,11 @@ __global__ void k_domain_penalty(int64_t C, int64_t n, const double* x, int64_t 
   if (threadIdx.x == 0 && outside) out[c] = -INFINITY;
 }
 
+omc_status omc_dense_gibbs_truncated_diag_launch(omc_ctx* ctx, int64_t p, const omc_dense_terms* terms, const double* rhs_chain,
+                                                 int64_t ld_rhs, const double* lower, const double* upper,
+                                                 const double* u_inject, int64_t ld_u, uint64_t draw_index, double* x,
+                                                 int64_t ld_x);  // omc_truncmix.hip
+
 extern "C" {
 
 omc_status omc_tridiag_gibbs_truncated(omc_ctx* ctx, int64_t n, const omc_tridiag_terms* terms, const double* rhs_chain,
@@ -436,7 +441,8 @@ omc_status omc_dense_gibbs_truncated(omc_ctx* ctx, int64_t p, const omc_dense_te
   if (!ctx || p < 1 || p > 8192 || !terms || terms->n_terms < 1 || terms->n_terms > OMC_MAX_TERMS || !x || ld_x < p ||
       (rhs_chain && ld_rhs < p) || (u_inject && ld_u < p))
     return OMC_INVALID_ARG;
-  if (terms->diag_chain) return OMC_UNSUPPORTED;  // per-chain diagonal (mixture prior) under a truncated conditional
+  if (terms->diag_chain)  // per-chain diagonal (a mixture prior): omc_truncmix.hip
+    return omc_dense_gibbs_truncated_diag_launch(ctx, p, terms, rhs_chain, ld_rhs, lower, upper, u_inject, ld_u, draw_index, x, ld_x);
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const double *m[4] = {0, 0, 0, 0}, *s[4] = {0, 0, 0, 0}, *r[4] = {0, 0, 0, 0};
   for (int k = 0; k < terms->n_terms; ++k) { m[k] = terms->mat[k]; s[k] = terms->scale[k]; r[k] = terms->rhs[k]; }

@@ -335,7 +335,21 @@ class Normal(Distribution):
         if self.is_mixture:
             x, mean, prec, count = self.mixture_pieces(state, engine)
             out = engine.empty(engine.n_chains) if out is None else out
-            engine.diag_gauss_logpdf(x, prec, out, mean=mean, count=count, accumulate=accumulate)
+            if self.domain_response_lower is None and self.domain_response_upper is None:
+                engine.diag_gauss_logpdf(x, prec, out, mean=mean, count=count, accumulate=accumulate)
+                return out
+            # location_scale.py:162-164: -inf for a chain with a live element outside the domain (the padding of a ragged
+            # parameter is not part of its value); the truncation's normalising constant is ignored, as in the reference
+            limits = self.scalar_domain_limits()
+            if limits is not None:
+                engine.diag_gauss_logpdf_limits(x, prec, out, lower=limits[0], upper=limits[1], mean=mean, count=count,
+                                                accumulate=accumulate)
+            elif count is None:  # fixed size, one limit per element
+                engine.diag_gauss_logpdf(x, prec, out, mean=mean, accumulate=accumulate)
+                lo, hi = self._domain_device(engine, x.shape[1])
+                engine.domain_penalty(x, out, lower=lo, upper=hi)
+            else:
+                raise ValueError(f"{self.response}: a variable-size parameter takes scalar domain limits only")
             return out
         if self._column_replicates(state):
             lp = self._columns_log_p(state, engine)[0]
@@ -377,6 +391,19 @@ class Normal(Distribution):
         scale = state[st.scale_key].scalar() if st.scale_key is not None else None
         n_rep = 1 if is_chain(resp) else resp.shape[1]
         return ("gauss", st.n * n_rep, scale, engine.matrix_logdet(st), float(n_rep), quad)
+
+    def scalar_domain_limits(self):
+        """(lower, upper) as floats (infinite where open) when each given limit holds one value, else None."""
+        lims = []
+        for v, open_ in ((self.domain_response_lower, -np.inf), (self.domain_response_upper, np.inf)):
+            if v is None:
+                lims.append(open_)
+                continue
+            a = np.asarray(v, dtype=np.float64)
+            if a.size != 1:
+                return None
+            lims.append(float(a.reshape(-1)[0]))
+        return tuple(lims)
 
     def _domain_device(self, engine, n):
         memo = self.__dict__.setdefault("_domain_memo", {})

@@ -719,9 +719,11 @@ class Engine:
                                               int(draw_index), self._p(x, Cn, n), ld(x)))
         return x
 
-    def dense_gibbs_truncated(self, p, terms, x, lower=None, upper=None, u=None, rhs_chain=None, draw_index=0):
+    def dense_gibbs_truncated(self, p, terms, x, lower=None, upper=None, u=None, rhs_chain=None, draw_index=0, diag_chain=None):
+        """diag_chain: optional (C, p) per-chain diagonal added to Q_c (a truncated mixture prior's precision)."""
         T = terms if isinstance(terms, _abi.DenseTerms) else self.dense_terms(terms, p)
         Cn = self.n_chains
+        T.diag_chain = self._p(diag_chain, Cn, p)
         ld = lambda t: 0 if t is None else t.stride(0)  # noqa: E731
         check(lib.omc_dense_gibbs_truncated(self._ctx, p, C.byref(T), self._p(rhs_chain, Cn, p), ld(rhs_chain),
                                             self._vec(lower, p), self._vec(upper, p), self._p(u, Cn, p), ld(u),
@@ -918,6 +920,19 @@ class Engine:
                                              self._p(mean_out)))
         return x
 
+    def small_gibbs_truncated(self, gram, gram_rhs, prior_prec, x, lower=-np.inf, upper=np.inf, lik_scale=None, prior_mean=None,
+                              count=None, u=None, draw_index=0):
+        """One in-place scan of single-site truncated updates on x (C, kmax) under the operator of small_sample_canonical
+        (omc_small_gibbs_truncated); lower / upper: scalars (infinite = open on that side); u: injected uniforms (C, kmax)."""
+        Cn, kmax, _ = gram.shape
+        if tuple(x.shape) != (Cn, kmax) or not x.is_contiguous():
+            raise ValueError("x must be a contiguous (C, kmax) tensor")
+        check(lib.omc_small_gibbs_truncated(self._ctx, kmax, self._p(gram.view(Cn, -1)), self._p(gram_rhs),
+                                            self._chain_scalar(lik_scale), self._p(prior_prec), self._p(prior_mean),
+                                            self._chain_scalar(count), float(lower), float(upper), self._p(u), int(draw_index),
+                                            self._p(x, Cn, kmax)))
+        return x
+
     def small_spd_ops(self, A, v=None, want_Av=False, want_quad=False, want_logdet=False):
         """(Av, quad, logdet) for per-chain small SPD matrices A (C, k, k) and vectors v (C, k) (omc_small_spd_ops)."""
         Cn, k, _ = A.shape
@@ -997,6 +1012,13 @@ class Engine:
         Cn, kmax = x.shape
         check(lib.omc_diag_gauss_logpdf(self._ctx, kmax, self._p(x), self._p(mean), self._p(prec),
                                         self._chain_scalar(count), self._chain_scalar(out), int(accumulate)))
+
+    def diag_gauss_logpdf_limits(self, x, prec, out, lower=-np.inf, upper=np.inf, mean=None, count=None, accumulate=False):
+        """diag_gauss_logpdf, and -inf for a chain with a live element outside [lower, upper] (scalars)."""
+        Cn, kmax = x.shape
+        check(lib.omc_diag_gauss_logpdf_limits(self._ctx, kmax, self._p(x), self._p(mean), self._p(prec),
+                                               self._chain_scalar(count), float(lower), float(upper), self._chain_scalar(out),
+                                               int(accumulate)))
 
     def gamma_logpdf_ragged(self, x, shape, rate, out, count=None, last_only=False, accumulate=False):
         Cn, kmax = x.shape

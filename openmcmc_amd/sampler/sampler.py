@@ -127,7 +127,8 @@ class NormalNormal(MCMCSampler):
       band         banded but wider (RW2, seasonal, lattice GMRFs; omc_band_sample_canonical);
       dense        anything else, incl. a regression likelihood through its Gram matrix (example 3; blocked batched Cholesky);
       ragged       a variable-size parameter with a mixture prior and a per-chain design matrix (reversible jump);
-    a prior with domain limits switches the tridiagonal and dense routes to the truncated single-site scan."""
+    a prior with domain limits switches the tridiagonal, dense and ragged routes to the truncated single-site scan (a
+    truncated mixture prior included: scalar limits on a ragged parameter)."""
 
     def __post_init__(self):
         super().__post_init__()
@@ -142,12 +143,12 @@ class NormalNormal(MCMCSampler):
         n = state[self.param].shape[0]
         mixture_prior = prior.is_mixture
         if mixture_prior:
-            if prior.domain_response_lower is not None or prior.domain_response_upper is not None:
-                raise NotImplementedError("truncated mixture prior")
             per_chain_design = any(k != self.param and isinstance(d.mean, LinearCombination)
                                    and is_chain(state[d.mean.form[self.param]]) for k, d in self.model.items())
             if per_chain_design or state[self.param].ragged is not None:
-                return self._ragged_plan(state, n)
+                plan = self._ragged_plan(state, n)
+                plan["limits"] = self._ragged_limits(prior)
+                return plan
         pieces = []  # one per distribution: what Q and b receive from it
         for key, dist in self.model.items():
             if mixture_prior and key == self.param:
@@ -234,6 +235,21 @@ class NormalNormal(MCMCSampler):
         if np.all(np.isneginf(lo)) and np.all(np.isposinf(hi)):
             return None
         return self.engine.to_device(lo.copy()), self.engine.to_device(hi.copy())
+
+    def _ragged_limits(self, prior):
+        """(lower, upper) scalars of a truncated prior on a variable-size parameter, or None without limits (then the
+        conditional is sampled exactly).  One limit per element has no meaning when the number of elements changes."""
+        if prior.domain_response_lower is None and prior.domain_response_upper is None:
+            return None
+        lims = prior.scalar_domain_limits()
+        if lims is None:
+            raise ValueError(f"{self.param}: a variable-size parameter takes scalar domain limits only")
+        lo, hi = lims
+        if not lo < hi:
+            raise ValueError("Error lower bound must be strictly less than upper bound")  # gmrf.py:149-150
+        if np.isneginf(lo) and np.isposinf(hi):
+            return None
+        return lo, hi
 
     def _replicated_structure(self, key, st, n_rep):
         """The structure of n_rep * M (kept on the sampler so the device cache sees one stable matrix object)."""
@@ -324,7 +340,7 @@ class NormalNormal(MCMCSampler):
             likes.append((key, dist, st))
         if len(likes) != 1:
             raise NotImplementedError("ragged NormalNormal: exactly one likelihood term")
-        return {"kind": "ragged", "n": n_max, "like": likes[0], "terms_list": [], "keys": [], "limits": None}
+        return {"kind": "ragged", "n": n_max, "like": likes[0], "terms_list": [], "keys": []}
 
     def _band_plan(self, state, n, pieces):
         """Q_c = sum_k s_k[c] M_k with banded M_k wider than tridiagonal (RW2, seasonal, lattice GMRFs): natural-order
@@ -472,8 +488,16 @@ class NormalNormal(MCMCSampler):
             # truncated prior: the scan starts from the current value and `z` carries the injected UNIFORMS
             lower, upper = p["limits"]
             eng.chain_copy(current_state[self.param].vector(), x)
-            gibbs = {"tridiag": eng.tridiag_gibbs_truncated, "band": eng.band_gibbs_truncated}.get(p["kind"], eng.dense_gibbs_truncated)
-            gibbs(n, p["terms"], x, lower=lower, upper=upper, u=z, rhs_chain=rhs_chain, draw_index=self._draw_index())
+            if p.get("mixture_prior") is not None:
+                # prior N(mean[alloc], diag(prec[alloc])^-1): the per-chain diagonal on Q and prec * mean on b, as below
+                _, pmean, pprec, _ = p["mixture_prior"].mixture_pieces(current_state, eng)
+                prior_rhs = pprec * pmean
+                eng.dense_gibbs_truncated(n, p["terms"], x, lower=lower, upper=upper, u=z, diag_chain=pprec,
+                                          rhs_chain=prior_rhs if rhs_chain is None else eng.chain_lincomb(1.0, prior_rhs, 1.0, rhs_chain),
+                                          draw_index=self._draw_index())
+            else:
+                gibbs = {"tridiag": eng.tridiag_gibbs_truncated, "band": eng.band_gibbs_truncated}.get(p["kind"], eng.dense_gibbs_truncated)
+                gibbs(n, p["terms"], x, lower=lower, upper=upper, u=z, rhs_chain=rhs_chain, draw_index=self._draw_index())
         elif p["kind"] == "tridiag":
             vecs = [None] * len(p["keys"])
             for k, (kind, what) in p.get("center_chain", ()):
@@ -545,8 +569,14 @@ class NormalNormal(MCMCSampler):
                 y = eng.to_device(np.asarray(state[key], dtype=np.float64).reshape(-1) - np.asarray(host).reshape(-1))
         gram, rhs = eng.design_gram_batched(B.columns(), w=w, resid_shared=y, resid_chain=rest, count=B.count(state))
         scale = _as_chain_scalar(eng, state, st.scale_key).scalar() if st.scale_key is not None else None
-        x = eng.small_sample_canonical(gram, rhs, pprec, lik_scale=scale, prior_mean=pmean, count=count, z=z,
-                                       draw_index=self._draw_index())
+        if p["limits"] is not None:
+            # truncated prior: one scan of single-site updates from the current value; `z` carries the injected UNIFORMS
+            x = cur.vector().clone()
+            eng.small_gibbs_truncated(gram, rhs, pprec, x, lower=p["limits"][0], upper=p["limits"][1], lik_scale=scale,
+                                      prior_mean=pmean, count=count, u=z, draw_index=self._draw_index())
+        else:
+            x = eng.small_sample_canonical(gram, rhs, pprec, lik_scale=scale, prior_mean=pmean, count=count, z=z,
+                                           draw_index=self._draw_index())
         state[self.param] = cur.like(x.unsqueeze(2))
         self._sweep += 1
         return state
