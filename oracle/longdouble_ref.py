@@ -1,4 +1,4 @@
-"""Extended-precision restatement of the tridiagonal canonical draw (test infrastructure, never shipped).
+"""Extended-precision restatements of the tridiagonal and the dense canonical draw (test infrastructure, never shipped).
 
 The same recurrences as gmrf.sample_normal_canonical on a tridiagonal Q (factor gmrf.py:489-520, solves
 gmrf.py:414-462, draw gmrf.py:29-61), carried in numpy.longdouble (x87 80-bit on the x86 hosts here and on the GPU
@@ -35,3 +35,43 @@ def tridiag_draw(a, b, r, z):
         x[i] = g[i] - l[i] * x[i + 1]
         mu[i] = m[i] - l[i] * mu[i + 1]
     return x.astype(np.float64), mu.astype(np.float64), float(np.sum(np.log(D)))
+
+
+def dense_draw(Q, b, z):
+    """Q (p, p) symmetric (only the lower triangle is read), b (p,) right-hand side, z (p,) N(0,1) draws.
+
+    The dense branch of gmrf.sample_normal_canonical (factor gmrf.py:481: np.linalg.cholesky, natural order, no
+    pivoting; solves gmrf.py:437-462; draw gmrf.py:29-61) in longdouble: Cholesky column by column (the inner products of
+    a column in one vectorised product), forward and backward substitution.  Returns
+        x = Q^-1 b + L^-T z, mu = Q^-1 b   (float64, rounded once from the longdouble result),
+        log det Q = 2 sum log L_ii         (float),
+        L                                  (p, p) lower factor, kept in longdouble.
+    A non-positive (or NaN) pivot raises numpy.linalg.LinAlgError whose attribute `pivot` is the 0-based index of the
+    first such pivot: the leading pivot x pivot block is positive definite, the one a row larger is not."""
+    ld = np.longdouble
+    A = np.asarray(Q, dtype=ld)
+    b, z = np.asarray(b, dtype=ld).ravel(), np.asarray(z, dtype=ld).ravel()
+    p = A.shape[0]
+    if A.shape != (p, p) or b.size != p or z.size != p:
+        raise ValueError("dense_draw: Q must be (p, p), b and z (p,)")
+    L = np.zeros((p, p), dtype=ld)
+    for j in range(p):
+        row = L[j, :j]
+        d = A[j, j] - row @ row
+        if not d > 0:
+            err = np.linalg.LinAlgError(f"Matrix is not positive definite (pivot {j})")
+            err.pivot = j
+            raise err
+        ljj = np.sqrt(d)
+        L[j, j] = ljj
+        if j + 1 < p:
+            L[j + 1:, j] = (A[j + 1:, j] - L[j + 1:, :j] @ row) / ljj
+    w = np.empty(p, dtype=ld)  # L w = b
+    for i in range(p):
+        w[i] = (b[i] - L[i, :i] @ w[:i]) / L[i, i]
+    t = np.stack([w, w + z], axis=1)  # L' [mu, x] = [w, w + z], by columns of L' (= rows of L)
+    for i in range(p - 1, -1, -1):
+        t[i] /= L[i, i]
+        t[:i] -= np.outer(L[i, :i], t[i])
+    logdet = 2 * np.sum(np.log(np.diag(L)))
+    return t[:, 1].astype(np.float64), t[:, 0].astype(np.float64), float(logdet), L
