@@ -1,6 +1,7 @@
 """RW(w) band draws only (for rocprofv3): python benchmarks/band_profile.py [--n 10000 --chains 1024 --w 2 --steps 20]
 --lattice K: a K x K first-order lattice GMRF instead (4-neighbour Laplacian + ridge, row-major order: n = K^2, bandwidth K --
-SURVEY 8f rank 1's "2-D lattice GMRF with bandwidth sqrt(n)", gmrf.py:489-520 on a sparse precision of that shape)."""
+SURVEY 8f rank 1's "2-D lattice GMRF with bandwidth sqrt(n)", gmrf.py:489-520 on a sparse precision of that shape).
+OMC_WIDE_STAMPS=1 (the phase stamps of k_band_blocked) needs OMC_HIP_LIB=openmcmc_amd/libomcmc_hip_stamped.so (make -C openmcmc_amd/csrc stamped)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import argparse, json, time

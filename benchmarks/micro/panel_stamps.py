@@ -1,4 +1,5 @@
-"""Where does k_chol_panel spend its time?  (diagnostic; stamps of chain 0 per panel through the context's stamps buffer)"""
+"""Where does k_chol_panel spend its time?  (diagnostic; stamps of chain 0 per panel through the context's stamps buffer)
+The stamps need OMC_HIP_LIB=openmcmc_amd/libomcmc_hip_stamped.so (make -C openmcmc_amd/csrc stamped); the product carries none."""
 import sys, os
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -14,55 +14,19 @@
 // kernel of omc_tridiag.hip instead).
 #include <math.h>
 
-#include "omc_common.h"
+#include "omc_band_common.h"
 
 omc_status omc_ensure_bytes(omc_ctx* ctx, void** buf, size_t* have, size_t need);  // omc_dense.hip
-bool omc_band_blocked_launch(omc_ctx* ctx, int64_t n, int w, const void* terms, const double* rhs_chain, int64_t ld_rhs,
-                             const double* z_inject, int64_t ld_z, omc_rng_key key, double* Lws, double* x, int64_t ld_x, double* mean,
-                             int64_t ld_mean, double* logdet);  // omc_bandwide.hip
 
 #define BAND_WMAX 128
 
-// Workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains the vector-memory
-// counter, which would expose the latency of the prefetched global loads (and of the factor stores) on every
-// column; inside the two loops the threads communicate through LDS alone.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-struct BandTermsDev {
-  int n_terms;
-  const double* band[OMC_MAX_TERMS];  // [ (bw+1) x n ], band[d*n + i] = M[i+d, i]; NULL = identity
-  int bw[OMC_MAX_TERMS];
-  const double* rhs[OMC_MAX_TERMS];
-  const double* scale[OMC_MAX_TERMS];
+// k_band_sample's two LDS images at bandwidth w, offsets in doubles: the kernel's pointers and the host's size from one place.
+// Forward: ring [W1][W1] at 0, rring [W1], lcol [W1], misc [2]; the backward pass lays xr [W1] at 0, mr [W1], red [8] over it.
+struct BandSampleLds {
+  int W1, rring, lcol, misc, mr, red;
+  __host__ __device__ BandSampleLds(int w) : W1(w + 1), rring(W1 * W1), lcol(rring + W1), misc(lcol + W1), mr(W1), red(2 * W1) {}
+  size_t bytes() const { return (size_t)(misc + 2 > red + 8 ? misc + 2 : red + 8) * sizeof(double); }
 };
-
-__device__ __forceinline__ double band_entry(const BandTermsDev& T, const double* s, int64_t n, int64_t col, int d) {
-  // Q[col + d, col]
-  if (col + d >= n) return 0.0;
-  double v = 0.0;
-#pragma unroll
-  for (int k = 0; k < OMC_MAX_TERMS; ++k) {
-    if (k < T.n_terms) {
-      if (T.band[k]) {
-        if (d <= T.bw[k]) v = fma(s[k], T.band[k][(int64_t)d * n + col], v);
-      } else if (d == 0) {
-        v += s[k];
-      }
-    }
-  }
-  return v;
-}
-
-__device__ __forceinline__ double band_rhs(const BandTermsDev& T, const double* s, int64_t n, int64_t col, const double* rc) {
-  if (col >= n) return 0.0;
-  double b = rc ? rc[col] : 0.0;
-#pragma unroll
-  for (int k = 0; k < OMC_MAX_TERMS; ++k)
-    if (k < T.n_terms && T.rhs[k]) b = fma(s[k], T.rhs[k][col], b);
-  return b;
-}
 
 template <int BAND_TX, int BAND_TY>
 __global__ void __launch_bounds__(BAND_TX* BAND_TY) k_band_sample(int64_t C, int64_t chain_offset, int64_t n, int w,
@@ -71,11 +35,12 @@ __global__ void __launch_bounds__(BAND_TX* BAND_TY) k_band_sample(int64_t C, int
                                                                    double* Lws, double* x, int64_t ld_x, double* mean,
                                                                    int64_t ld_mean, double* logdet, long long* bad) {
   extern __shared__ double sm[];
-  const int W1 = w + 1;
+  const BandSampleLds lds(w);
+  const int W1 = lds.W1;
   double* ring = sm;                    // W1 x W1: ring[(col % W1) * W1 + d] = open entry Q[col + d, col]
-  double* rring = ring + (int64_t)W1 * W1;  // W1: open right-hand side
-  double* lcol = rring + W1;            // W1: the column being eliminated
-  double* misc = lcol + W1;             // [0] u_j, [1] fail flag
+  double* rring = sm + lds.rring;       // W1: open right-hand side
+  double* lcol = sm + lds.lcol;         // W1: the column being eliminated
+  double* misc = sm + lds.misc;         // [0] u_j, [1] fail flag
   const int64_t c = blockIdx.x;
   const int tx = threadIdx.x, ty = threadIdx.y;
   const int tid = ty * BAND_TX + tx;
@@ -140,7 +105,7 @@ __global__ void __launch_bounds__(BAND_TX* BAND_TY) k_band_sample(int64_t C, int
       ld_exp += __builtin_amdgcn_frexp_exp(ld_mant);
       ld_mant = __builtin_amdgcn_frexp_mant(ld_mant);
     }
-    lds_barrier();
+    omc_lds_barrier();
     // trailing update: Q[j+a, j+b] -= l_a l_b, 1 <= b <= a <= w, and the right-hand side
     for (int a = 1 + ty; a <= w; a += BAND_TY) {
       const double la = lcol[a];
@@ -159,7 +124,7 @@ __global__ void __launch_bounds__(BAND_TX* BAND_TY) k_band_sample(int64_t C, int
     if (tid < W1) ring[slot * W1 + tid] = pre;
     else if (tid == W1) rring[slot] = pre;
     pre = pre_next;
-    lds_barrier();
+    omc_lds_barrier();
   }
   const bool failed = misc[1] != 0.0;
   if (tid == 0) {
@@ -190,10 +155,10 @@ __global__ void __launch_bounds__(BAND_TX* BAND_TY) k_band_sample(int64_t C, int
   __syncthreads();
 
   // backward pass  L' x = t:  x_j = (t_j - sum_{d=1..w} L[j+d, j] x_{j+d}) / L_jj ;  ring of the last w solutions
-  double* xr = ring;        // W1 entries: x_{col} at xr[col % W1]
-  double* mr = ring + W1;   // the same for the mean
-  double* red = ring + 2 * W1;  // per-wave partial sums (2 x 4)
-  for (int t = tid; t < 2 * W1; t += nthreads) ring[t] = 0.0;
+  double* xr = sm;             // W1 entries: x_{col} at xr[col % W1]
+  double* mr = sm + lds.mr;    // the same for the mean
+  double* red = sm + lds.red;  // per-wave partial sums (2 x 4)
+  for (int t = tid; t < 2 * W1; t += nthreads) xr[t] = 0.0;
   __syncthreads();
   const int lane = tid & 63, wave = tid >> 6;
   const int n_waves = (w + 63) / 64;  // waves that carry band entries (w <= 128 -> at most 2)
@@ -232,7 +197,7 @@ __global__ void __launch_bounds__(BAND_TX* BAND_TY) k_band_sample(int64_t C, int
       }
       if (lane == 0) { red[wave] = px; red[4 + wave] = pm; }
     }
-    lds_barrier();
+    omc_lds_barrier();
     if (tid == 0) {
       double sx = red[0], smn = red[4];
       if (n_waves > 1) { sx += red[1]; smn += red[5]; }
@@ -246,7 +211,7 @@ __global__ void __launch_bounds__(BAND_TX* BAND_TY) k_band_sample(int64_t C, int
       }
     }
     l_cur = l_next; ljj_cur = ljj_next; t_cur = t_next; tm_cur = tm_next;
-    lds_barrier();
+    omc_lds_barrier();
   }
 }
 
@@ -1294,9 +1259,7 @@ omc_status omc_band_sample_canonical(omc_ctx* ctx, int64_t n, int64_t w, const o
   // does once per segment of its group (joins, composition of the incoming states).
   const int ov = ctx->band_seg_overlap;
   int64_t min_seg = ov / 2 > 96 ? ov / 2 : 96;
-  int dev_cus = 256;
-  hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-  const int64_t simds = 4 * (int64_t)(dev_cus > 0 ? dev_cus : 256);
+  const int64_t simds = 4 * (int64_t)ctx->dev_cus;
   int nseg = 0;
   {
     int64_t best = -1;
@@ -1384,15 +1347,12 @@ omc_status omc_band_sample_canonical(omc_ctx* ctx, int64_t n, int64_t w, const o
     OMC_HIP_CHECK(hipGetLastError());
     return OMC_OK;
   }
-  const int W1 = (int)w + 1;
-  size_t lds = ((size_t)W1 * W1 + 2 * W1 + 2) * sizeof(double);
-  const size_t lds_back = (size_t)(2 * W1 + 8) * sizeof(double);
-  if (lds < lds_back) lds = lds_back;
+  const size_t lds = BandSampleLds((int)w).bytes();
   const omc_rng_key key = omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL);
   // wide bands (lattice GMRFs): NB columns per step, the window update on the matrix cores (omc_bandwide.hip); "band_algo" 3
   // forces it for any bandwidth, 2 keeps the column-at-a-time kernel
   if ((blocked_first || (ctx->band_algo != 2 && w >= 9)) &&
-      omc_band_blocked_launch(ctx, n, (int)w, &T, rhs_chain, ld_rhs, z_inject, ld_z, key, ctx->workspace, x, ld_x, mean, ld_mean, logdet)) {
+      omc_band_blocked_launch(ctx, n, (int)w, T, rhs_chain, ld_rhs, z_inject, ld_z, key, ctx->workspace, x, ld_x, mean, ld_mean, logdet)) {
     OMC_HIP_CHECK(hipGetLastError());
     return OMC_OK;
   }

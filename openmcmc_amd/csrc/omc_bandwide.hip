@@ -20,50 +20,12 @@
 // streams; results agree with it to rounding (another summation order), parity tests as for it.  Sums are taken in fixed orders:
 // results do not depend on timing.
 #include <math.h>
-#include <string.h>
 
 #include <type_traits>
 
-#include "omc_common.h"
-
-#define BAND_WMAX_W 128
-#define BAND_W16_MAX 115  // 16 columns per step up to here (LDS: blocked_lds(116, 16) > 160 KB), 8 beyond
+#include "omc_band_common.h"
 
 namespace {
-
-struct BandTermsW {  // (the image of omc_band.hip's BandTermsDev: kept in step by hand, both are filled from omc_band_terms)
-  int n_terms;
-  const double* band[OMC_MAX_TERMS];  // [(bw+1) x n], band[d*n + i] = M[i+d, i]; NULL = identity
-  int bw[OMC_MAX_TERMS];
-  const double* rhs[OMC_MAX_TERMS];
-  const double* scale[OMC_MAX_TERMS];
-};
-
-__device__ __forceinline__ void lds_barrier_w() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ double entry_w(const BandTermsW& T, const double* s, int64_t n, int64_t col, int d) {
-  if (col >= n || col + d >= n) return 0.0;
-  double v = 0.0;
-#pragma unroll
-  for (int k = 0; k < OMC_MAX_TERMS; ++k) {
-    if (k < T.n_terms) {
-      if (T.band[k]) {
-        if (d <= T.bw[k]) v = fma(s[k], T.band[k][(int64_t)d * n + col], v);
-      } else if (d == 0) {
-        v += s[k];
-      }
-    }
-  }
-  return v;
-}
-__device__ __forceinline__ double rhs_w(const BandTermsW& T, const double* s, int64_t n, int64_t col, const double* rc) {
-  if (col >= n) return 0.0;
-  double b = rc ? rc[col] : 0.0;
-#pragma unroll
-  for (int k = 0; k < OMC_MAX_TERMS; ++k)
-    if (k < T.n_terms && T.rhs[k]) b = fma(s[k], T.rhs[k][col], b);
-  return b;
-}
 
 __device__ __forceinline__ double readlane_d(double v, int lane) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
@@ -112,26 +74,19 @@ typedef double wide_d4 __attribute__((ext_vector_type(4)));
 // MT: the number of terms the kernel is compiled for (2 covers most models: their entries a block ahead are half the registers)
 // WPE: waves per SIMD the register allocation leaves room for (4: 128 registers -- two 512-thread or four 256-thread workgroups on a CU)
 template <int NB, int NT, int MT, int WPE>
-__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) k_band_blocked(int64_t C, int64_t chain_offset, int64_t n, int w, BandTermsW T, const double* rhs_chain,
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) k_band_blocked(int64_t C, int64_t chain_offset, int64_t n, int w, BandTermsDev T, const double* rhs_chain,
                                                       int64_t ld_rhs, const double* z_in, int64_t ld_z, omc_rng_key key, double* Lws, double* x,
                                                       int64_t ld_x, double* mean, int64_t ld_mean, double* logdet, long long* bad, unsigned long long* dbg) {
   static_assert(NT == 512 || NT == 256, "eight waves: one per tile of the window's first tile column; four for bands up to 15");
   extern __shared__ double sm[];
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter(), twork = 0, tback = 0;
-#define WSTAMP(i) do { if (dbg) { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; } } while (0)
-  const int W1 = w + 1;
-  const int WS = w + NB;                 // columns of the window (ring slots)
-  const int WP = (w + 15) & ~15;         // panel rows, padded to whole tiles
-  constexpr int PS = NB + 1;             // panel row stride
-  double* ring = sm;                               // WS x W1: ring[slot(col) * W1 + d] = open entry Q[col + d, col]
-  double* rring = ring + (int64_t)WS * W1;         // WS: open right-hand side
-  // a factorised block column, TWO copies (the block being applied and the one factorised ahead of it), FBS doubles apart:
-  double* Ld = rring + WS;                         // NB x PS: the diagonal block's factor (its strict lower triangle is what is read)
-  double* P = Ld + NB * PS;                        // WP x PS: the panel below it, right behind: row r of the block column = Ld[r * PS ..]
-  double* dv = P + (int64_t)WP * PS;               // NB: 1 / L_jj of the block
-  double* Us = dv + NB;                            // NB: forward-substituted right-hand side of the block
-  const int FBS = WP * PS + NB * PS + 2 * NB;
-  double* misc = Ld + 2 * FBS;                     // [0] fail flag, [1] a zero to read, [2 .. 65] a slot per lane to write to in vain, [66] a counter
+  // (diagnostic build only: cycles per phase, and each wave's own work in S3 and in a step of the backward pass)
+  OMC_STAMPED(unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter(), twork = 0, tback = 0;)
+#define WSTAMP(i) OMC_STAMPED(do { if (dbg) { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; } } while (0))
+  const BandBlockedLds lds(w, NB, NT);   // both LDS images: what lies where is written down there and nowhere else
+  const int W1 = lds.W1, WS = lds.WS, WP = lds.WP, FBS = lds.FBS;
+  constexpr int PS = NB + 1;             // panel row stride (lds.PS)
+  double* ring = sm + lds.ring, * rring = sm + lds.rring, * Ld = sm + lds.Ld, * P = sm + lds.P, * dv = sm + lds.dv, * Us = sm + lds.Us;
+  double* misc = sm + lds.misc;
   const int64_t c = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double s[MT];
@@ -144,12 +99,12 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
   // open the first WS columns (slot of column col = col % WS, kept incrementally below)
   for (int t = tid; t < WS * W1; t += NT) {
     const int col = t / W1, d = t % W1;
-    ring[col * W1 + d] = entry_w(T, s, n, col, d);
+    ring[col * W1 + d] = band_entry(T, s, n, col, d);
   }
-  for (int t = tid; t < WS; t += NT) rring[t] = rhs_w(T, s, n, t, rc);
+  for (int t = tid; t < WS; t += NT) rring[t] = band_rhs(T, s, n, t, rc);
   if (tid == 0) {
-    misc[0] = misc[1] = 0.0;  // [0] a pivot was not positive, [1] a zero to read
-    *(int*)(misc + 66) = 0;   // [66] the next item of the block's list (see drain_items)
+    misc[lds.FAIL] = misc[lds.ZERO] = 0.0;
+    *(int*)(misc + lds.COUNTER) = 0;   // the next item of the block's list (see drain_items)
   }
   for (int t = tid; t < WP * PS; t += NT) P[t] = P[FBS + t] = 0.0;  // (rows w .. WP - 1 pad the last tile: never written again)
   __syncthreads();
@@ -160,8 +115,9 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
   // What does not change from block to block -- which term has an entry at this thread's distance from the diagonal, and where
   // its row of the band storage starts -- is worked out once: a block then asks for its entries with a compare and a load each.
   constexpr int TPC = NT / NB;                                   // threads per column
-  // widest band this instantiation is launched for (the four-wave form: bands narrower than a block, several workgroups per CU)
-  constexpr int WMAX_NB = (NT == 256) ? ((NB == 16) ? 15 : 64) : ((NB == 16) ? BAND_W16_MAX : BAND_WMAX_W);
+  constexpr int WMAX_NB = BandBlockedForm{NB, NT, MT, WPE}.wmax();  // widest band this instantiation is launched for
+  static_assert((WMAX_NB + 15) / 16 <= NT / 64 && (WMAX_NB + 64 - NB) / (64 - NB) <= NT / 64,
+                "a wave per tile of the first tile column (nt) and per share of the block column (npw)");
   constexpr int NPRE = (WMAX_NB + 2 + TPC - 1) / TPC;             // entries per thread
   const int pcol = tid / TPC, pq = tid % TPC;                    // (NB is a power of two: shifts)
   const double* pbase[NPRE][MT];                      // term k's row d of the band (or its right-hand side), NULL: no entry
@@ -200,10 +156,10 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
   const bool f_rhs = lane >= NB && frow_i == w;
   const int f_rowoff = lane < NB ? lane : NB + frow_i;            // row jj + f_rowoff of the matrix (the rhs lane: any value >= NB)
   const bool f_row = lane < NB || frow_i < w;
-  // where the lane's entry against column jj + b sits: ring[slot * W1 + f_rowoff - b], the right-hand side rring[slot] (= ring[WS W1 + slot])
-  const int f_mul = f_rhs ? 1 : W1, f_base = f_rhs ? WS * W1 : f_rowoff, f_dec = f_rhs ? 0 : 1;
-  const int zero_at = (int)(misc + 1 - ring);                     // misc[1] == 0.0
-  const int dump_at = zero_at + 1 + lane;
+  // where the lane's entry against column jj + b sits: ring[slot * W1 + f_rowoff - b], the right-hand side rring[slot] (= ring[lds.rring + slot])
+  const int f_mul = f_rhs ? 1 : W1, f_base = f_rhs ? lds.rring : f_rowoff, f_dec = f_rhs ? 0 : 1;
+  const int zero_at = lds.misc + lds.ZERO;                        // (offsets from ring, the start of the image)
+  const int dump_at = lds.misc + lds.DUMP + lane;
   auto factor_block = [&](const int64_t jj, const int slot, double* Pn, double* Ldn, double* dvn, double* Usn) {
     __builtin_amdgcn_s_setprio(3);
     const int nbj = (int)((n - jj < NB) ? n - jj : NB);
@@ -250,7 +206,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
       for (int b = 0; b < NB; ++b) dst[b] = D[b];
     }
     if (tid < NB) dvn[tid] = dkeep;
-    if (tid == 0 && nfail) misc[0] = 1.0;
+    if (tid == 0 && nfail) misc[lds.FAIL] = 1.0;
     __builtin_amdgcn_s_setprio(0);
   };
   // one 16 x 16 tile of P P' off the window (rows 16 ti .., columns 16 tj .. behind the block)
@@ -305,10 +261,10 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
   // then the rows of the block column, which lie one behind the other in LDS) -- is a list of items the waves TAKE from a
   // counter in LDS: the waves that factorise join when they are done, and nobody waits for the slowest share.  The items touch
   // disjoint entries: who takes which does not change a bit of the result.
-  int* const q_next = (int*)(misc + 66);
+  int* const q_next = (int*)(misc + lds.COUNTER);
   auto drain_items = [&](const int64_t j, const int nb, const int slot0, const int cur) {
     const int ntiles = nt * (nt - 1) / 2, n_tile_items = (ntiles + 1) / 2, n_items = n_tile_items + (nb + 1) / 2;
-    const int ld_at = (int)(Ld - ring) + cur * FBS, dv_at = (int)(dv - ring) + cur * FBS;
+    const int ld_at = lds.Ld + cur * FBS, dv_at = lds.dv + cur * FBS;
     const double* Pc = P + cur * FBS;
     for (;;) {
       int it = 0;
@@ -383,7 +339,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
       }
       WSTAMP(0);
       // ---- S2: what block j + NB waits for: the first tile column of the window update and the right-hand side
-      if (wave < nt) window_tiles(std::false_type{}, j, slot0, Pc, wave, 0, wave, 0);   // (nt <= 8 = NT / 64)
+      if (wave < nt) window_tiles(std::false_type{}, j, slot0, Pc, wave, 0, wave, 0);   // (nt <= NT / 64: see WMAX_NB)
       if (tid < w && j + NB + tid < n) {
         double acc = 0.0;
 #pragma unroll
@@ -395,12 +351,12 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
       // (the block's forward-substituted right-hand side: overwritten by the draw in the backward pass)
       if (tid >= NT - 64 && lane < nb) xc[j + lane] = Usc[lane];
       if (!ahead) drain_items(j, nb, slot0, cur);
-      lds_barrier_w();
+      omc_lds_barrier();
       WSTAMP(2);
       if (!ahead) {
         BAND_REFILL();
         if (tid == 0) *q_next = 0;
-        lds_barrier_w();
+        omc_lds_barrier();
         WSTAMP(4);
       }
     } else {
@@ -412,23 +368,23 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
       }
     }
     // ---- S3: block j + NB factorised by the first waves, beside the rest of block j's work on the others
-    const unsigned long long tw0 = dbg ? __builtin_readcyclecounter() : 0;
+    OMC_STAMPED(const unsigned long long tw0 = dbg ? __builtin_readcyclecounter() : 0;)
     if (wave < npw && j + NB < n) factor_block(j + NB, slot1, P + nxt * FBS, Ld + nxt * FBS, dv + nxt * FBS, Us + nxt * FBS);
     if (ahead && apply) drain_items(j, nb, slot0, cur);
-    if (dbg) twork += __builtin_readcyclecounter() - tw0;   // (this wave's own work in S3, without the wait at the barrier)
-    lds_barrier_w();
+    OMC_STAMPED(if (dbg) twork += __builtin_readcyclecounter() - tw0;)   // (this wave's own work in S3, without the wait at the barrier)
+    omc_lds_barrier();
     WSTAMP(3);
     if (ahead && apply) {
       BAND_REFILL();
       if (tid == 0) *q_next = 0;
-      lds_barrier_w();
+      omc_lds_barrier();
       WSTAMP(4);
     }
     slot0 = slot1;
     cur = nxt;
   }
 #undef BAND_REFILL
-  const bool failed = misc[0] != 0.0;
+  const bool failed = misc[lds.FAIL] != 0.0;
   if (wave == 0) {
     // log det Q = -2 sum log(1 / L_KK): the lanes' shares in lane order
     const double share = (lane < NB) ? log(ld_mant) + (double)ld_exp * 0.69314718055994530942 : 0.0;
@@ -472,22 +428,18 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
   // timing.
   // (the ring of solutions has w + 2 NB slots, not w + NB: block J + 1 is still being copied out of it by wave 1 while wave 0
   // writes block J -- with w < NB the two blocks would share slots in a ring of w + NB)
-  const int WB = w + 2 * NB;
-  double* xs = sm;
-  double* ms = xs + WB;
-  double* Sx = ms + WB;        // NB: sum over the rows behind the block, per column
-  double* Sm = Sx + NB;
-  double* Lb = Sm + NB;        // NB x PS: the block's own triangle of the factor, Lb[a][b] = L[j+a][j+b], a > b; dinv on the diagonal
+  const int WB = lds.WB;
+  double* xs = sm + lds.xs, * ms = sm + lds.ms, * Sx = sm + lds.Sx, * Sm = sm + lds.Sm;
+  double* Lb = sm + lds.Lb;    // Lb[a][b] = L[j+a][j+b], a > b
+  double* Part = sm + lds.Part;
   constexpr int TPF = (NT - 64) / NB;   // threads per column for the far rows
   constexpr int QPC = TPF / 4;          // their quads per column
   constexpr int NPF = (WMAX_NB > NB) ? (WMAX_NB - NB + TPF - 1) / TPF : 1;  // far entries per thread (d = 2 NB - b .. w: at most w - NB of them, b = NB - 1)
   constexpr int LPC = 64 / NB;          // lanes of wave 0 per column for the block's own and the near rows
   constexpr int KN = 2 * NB / LPC;      // entries per lane there (d = 0 .. 2 NB - 1 - b)
   static_assert(TPF % 4 == 0 && TPF * NB == NT - 64, "quads of far threads do not straddle columns");
-  const int dump_b = NB * PS + 4 * NB * QPC + lane;  // (behind Part: a slot per lane to write to in vain)
-  const int diag_b = NB * PS + 4 * NB * QPC + 64;    // (and the block's 1 / L_jj: NB of them)
-  double* Part = Lb + NB * PS;  // [2][2][NB][QPC]: the far sums of the quads, for blocks of even and odd number, draw and mean
-  for (int t = tid; t < 2 * WB; t += NT) sm[t] = 0.0;
+  const int dump_b = lds.dump - lds.Lb + lane, diag_b = lds.diag - lds.Lb;   // (offsets from Lb)
+  for (int t = tid; t < 2 * WB; t += NT) xs[t] = 0.0;   // (xs and ms, one behind the other)
   for (int t = tid; t < NB * PS; t += NT) Lb[t] = 0.0;
   if (tid < NB) Lb[diag_b + tid] = 0.0;
   __syncthreads();
@@ -588,14 +540,14 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
   int slotJ = (int)(((nblk - 1) * NB) % WB);  // slot of the block's first column, kept incrementally
   request((int)nblk - 1);
   if (wave > 0) far_part((int)nblk - 1, slotJ);    // (nothing behind the last block but zeros: its sums are written all the same)
-  lds_barrier_w();
+  omc_lds_barrier();
   WSTAMP(6);
   for (int64_t J = nblk - 1; J >= 0; --J) {
     const int64_t j = J * NB;
     const int nb = (int)((n - j < NB) ? n - j : NB);
     int slotP = slotJ - NB;                   // slot of block J - 1's first column
     if (slotP < 0) slotP += WB;
-    const unsigned long long tb0 = dbg ? __builtin_readcyclecounter() : 0;
+    OMC_STAMPED(const unsigned long long tb0 = dbg ? __builtin_readcyclecounter() : 0;)
     if (wave > 0) {
       if (J > 0) far_part((int)J - 1, slotP);
       if (wave == 1 && J + 1 < nblk) store_block(J + 1, slotJ + NB >= WB ? slotJ + NB - WB : slotJ + NB);
@@ -679,85 +631,34 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8)
       }
     }
     slotJ = slotP;
-    if (dbg) tback += __builtin_readcyclecounter() - tb0;   // (this wave's own work, without the wait at the barrier)
-    lds_barrier_w();
+    OMC_STAMPED(if (dbg) tback += __builtin_readcyclecounter() - tb0;)   // (this wave's own work, without the wait at the barrier)
+    omc_lds_barrier();
     WSTAMP(7);
   }
   if (wave == 1) store_block(0, slotJ + NB >= WB ? slotJ + NB - WB : slotJ + NB);
-  if (dbg && blockIdx.x == 0 && tid == 0)
-    for (int i = 0; i < 8; ++i) dbg[i] = tacc[i];
-  if (dbg && blockIdx.x == 0 && lane == 0) {
+  OMC_STAMPED(if (dbg && blockIdx.x == 0 && lane == 0) {
+    for (int i = 0; i < 8 && tid == 0; ++i) dbg[i] = tacc[i];
     dbg[8 + wave] = twork;    // S3 per wave
     dbg[16 + wave] = tback;   // a step of the backward pass per wave
-  }
+  })
 #undef WSTAMP
 }
 
 }  // namespace
 
-// LDS bytes of a block size NB at bandwidth w with NT threads: the larger of the two passes' images (the factor phase's, except for
-// bands of a few entries)
-static size_t blocked_lds(int w, int NB, int NT = 512) {
-  const size_t W1 = (size_t)w + 1, WS = (size_t)w + NB, WP = ((size_t)w + 15) & ~(size_t)15, PS = (size_t)NB + 1;
-  const size_t fwd = WS * W1 + WS + 2 * (WP * PS + (size_t)NB * PS + 2 * (size_t)NB) + 2 + 64 + 2;
-  // the backward pass lays its own image over the same memory: two solution rings of w + 2 NB, the block's sums and triangle, the
-  // far sums of the quads (two blocks, draw and mean), a slot per lane to write to in vain, the block's 1 / L_jj
-  const size_t qpc = (size_t)(NT - 64) / NB / 4;
-  const size_t bwd = 2 * ((size_t)w + 2 * NB) + 2 * (size_t)NB + (size_t)NB * PS + 4 * (size_t)NB * qpc + 64 + (size_t)NB;
-  return (fwd > bwd ? fwd : bwd) * sizeof(double);
-}
-
-// terms: omc_band.hip's BandTermsDev (the same layout as BandTermsW above); Lws: [C][n][w + 1] doubles.  Returns false if no block
-// size fits the 160 KB of LDS (the caller then takes k_band_sample).
-bool omc_band_blocked_launch(omc_ctx* ctx, int64_t n, int w, const void* terms, const double* rhs_chain, int64_t ld_rhs,
+bool omc_band_blocked_launch(omc_ctx* ctx, int64_t n, int w, const BandTermsDev& T, const double* rhs_chain, int64_t ld_rhs,
                              const double* z_inject, int64_t ld_z, omc_rng_key key, double* Lws, double* x, int64_t ld_x, double* mean,
                              int64_t ld_mean, double* logdet) {
-  if (w < 1 || w > BAND_WMAX_W) return false;
-  BandTermsW T;
-  memcpy(&T, terms, sizeof(T));
-  const size_t limit = 160 * 1024;
-  const bool few = T.n_terms <= 2;
-#define OMC_BLOCKED_LAUNCH(NB_, NT_, MT_, WPE_)                                                                                       \
-  hipLaunchKernelGGL((k_band_blocked<NB_, NT_, MT_, WPE_>), dim3((unsigned)ctx->n_chains), dim3(NT_), blocked_lds(w, NB_, NT_), ctx->stream, \
-                     ctx->n_chains, ctx->chain_offset, n, w, T, rhs_chain, ld_rhs, z_inject, ld_z, key, Lws, x, ld_x, mean, ld_mean,  \
-                     logdet, ctx->d_bad_chain, ctx->stamps)
-  // Which form, by what fits a CU (measured on 10 000-node lattices, profiles/r04q_band.txt):
-  //  * bands narrower than a block take four waves per chain (one tile, one factorising wave); with more chains than three
-  //    workgroups per CU hold, the form compiled for 128 registers puts four there (1024 chains at w = 8: 8.0 -> 4.6 ms);
-  //  * bands up to ~64 on more chains than CUs: 8 columns per step at 128 registers -- four waves per chain and four workgroups
-  //    to a CU while their LDS fits (w <= 55: 1024 chains at w = 32 15.6 -> 6.2 ms, at w = 16 15.6 -> 5.6 ms), eight waves and
-  //    two to a CU beyond (w = 64: 16.4 -> 14.6 ms); slower where one workgroup per CU is all there is (3.9 -> 4.9 ms at 256
-  //    chains);
-  //  * otherwise 16 columns per step, eight waves, one workgroup per CU (8 columns where the window would not fit the LDS).
-  // "band_blocked_threads": 0 this choice; 512 eight waves and no register limit whatever the shape; 4 / 16 / 8 the 128-register
-  // forms wherever they apply (A/B runs and tests).  Only the forms compiled for two terms have the 128-register variants.
-  int dev_cus = 256;
-  hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-  const int forced = ctx->band_blocked_threads;
-  if (w <= 15 && forced != 512 && forced != 8) {
-    if (few && (forced == 4 || (forced == 0 && ctx->n_chains > 3 * (int64_t)dev_cus))) OMC_BLOCKED_LAUNCH(16, 256, 2, 4);
-    else if (few) OMC_BLOCKED_LAUNCH(16, 256, 2, 1);
-    else OMC_BLOCKED_LAUNCH(16, 256, OMC_MAX_TERMS, 1);
+  const BandBlockedForm f = band_blocked_choose(w, T.n_terms, ctx->n_chains, ctx->dev_cus, ctx->band_blocked_threads);
+  switch (f.key()) {
+#define OMC_BLOCKED_CASE(NB_, NT_, MT_, WPE_)                                                                                          \
+  case BandBlockedForm{NB_, NT_, MT_, WPE_}.key():                                                                                     \
+    hipLaunchKernelGGL((k_band_blocked<NB_, NT_, MT_, WPE_>), dim3((unsigned)ctx->n_chains), dim3(NT_),                               \
+                       BandBlockedLds(w, NB_, NT_).bytes(), ctx->stream, ctx->n_chains, ctx->chain_offset, n, w, T, rhs_chain, ld_rhs, \
+                       z_inject, ld_z, key, Lws, x, ld_x, mean, ld_mean, logdet, ctx->d_bad_chain, ctx->stamps);                       \
     return true;
+    BAND_BLOCKED_FORMS(OMC_BLOCKED_CASE)
+#undef OMC_BLOCKED_CASE
   }
-  if (few && w <= 64 && 4 * blocked_lds(w, 8, 256) <= limit && (forced == 16 || (forced == 0 && ctx->n_chains > (int64_t)dev_cus))) {
-    OMC_BLOCKED_LAUNCH(8, 256, 2, 4);   // 8 columns per step, four waves, four workgroups to a CU
-    return true;
-  }
-  if (few && 2 * blocked_lds(w, 8) <= limit && (forced == 8 || (forced == 0 && ctx->n_chains > (int64_t)dev_cus))) {
-    OMC_BLOCKED_LAUNCH(8, 512, 2, 4);   // 8 columns per step, eight waves, two workgroups to a CU
-    return true;
-  }
-  if (w <= BAND_W16_MAX && blocked_lds(w, 16) <= limit) {
-    if (few) OMC_BLOCKED_LAUNCH(16, 512, 2, 1);
-    else OMC_BLOCKED_LAUNCH(16, 512, OMC_MAX_TERMS, 1);
-    return true;
-  }
-  if (blocked_lds(w, 8) <= limit) {
-    if (few) OMC_BLOCKED_LAUNCH(8, 512, 2, 1);
-    else OMC_BLOCKED_LAUNCH(8, 512, OMC_MAX_TERMS, 1);
-    return true;
-  }
-#undef OMC_BLOCKED_LAUNCH
-  return false;
+  return false;  // no form fits
 }

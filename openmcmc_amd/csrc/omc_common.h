@@ -9,6 +9,7 @@
 #define OMC_SWEEP_RING_MIN 64  // >= 2 * OMC_RUN_MAX: a launch never laps its own records
 struct omc_ctx {
   int device;
+  int dev_cus;  // compute units of the device, asked of the driver once (omc_ctx_create; 256 if it does not say)
   int64_t n_chains;
   uint64_t seed;
   int64_t chain_offset;
@@ -67,7 +68,7 @@ struct omc_ctx {
   int diag_algo;  // omc_store_rhat_ess: 0 auto, 1 short-series form (M <= 64), 2 blocks of lags
   int band_seg_overlap;  // segmented lane kernel: columns of warm-up before a segment (default 192)
   int band_seg_count;    // segmented lane kernel: number of segments (0 = chosen for the SIMDs; tuning and tests)
-  int band_blocked_threads;  // blocked band kernel: 0 = form chosen by what fits a CU; 512, 4, 8 force one (A/B, tests; omc_bandwide.hip)
+  int band_blocked_threads;  // blocked band kernel: 0 = form chosen by what fits a CU; 512, 4, 8, 16 force one (A/B, tests; band_blocked_choose)
   int mh_gemm_ksplit;  // omc_dgemm_small: groups of four waves per workgroup cutting the contraction (1, 2 or 4)
   int mh_use_rocblas;  // 1: the products of the fused Metropolis-Hastings steps through rocBLAS DGEMM instead of omc_dgemm_small (cross-checks)
   int gram_use_rocblas;  // 1: X' diag(w) X through rocBLAS (scaled copy of X + DGEMM) instead of the own MFMA kernel (cross-checks)
@@ -109,6 +110,19 @@ extern "C" omc_status omc_gram_mfma_launch(omc_ctx* ctx, int64_t n, int64_t p, c
   } while (0)
 
 #define OMC_NO_BAD_CHAIN 0x7fffffffffffffffLL
+
+// Workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains the vector-memory counter, which
+// would expose the latency of prefetched global loads (and of stores) at every step of a loop whose threads communicate through
+// LDS alone.
+__device__ __forceinline__ void omc_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Cycle-counter stamps of k_band_blocked and k_chol_panel exist only in the diagnostic build (make stamped: -DOMC_KERNEL_STAMPS);
+// in the product the stamp state and every stamp site compile to nothing, and the kernels' dbg argument is ignored.
+#ifdef OMC_KERNEL_STAMPS
+#define OMC_STAMPED(...) __VA_ARGS__
+#else
+#define OMC_STAMPED(...)
+#endif
 
 // ------------------------------------------------------------------------------------------
 // Random streams: Philox4x32-10 (Salmon et al., SC'11), the generator rocRAND's

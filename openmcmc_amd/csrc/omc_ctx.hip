@@ -29,6 +29,8 @@ omc_status omc_ctx_create(int32_t device, int64_t n_chains, uint64_t seed, int64
   OMC_HIP_CHECK(hipSetDevice(device));
   omc_ctx* c = new omc_ctx();
   c->device = device;
+  c->dev_cus = 256;
+  if (hipDeviceGetAttribute(&c->dev_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->dev_cus <= 0) c->dev_cus = 256;
   c->n_chains = n_chains;
   c->seed = seed;
   c->chain_offset = chain_id_offset;

@@ -319,13 +319,10 @@ __global__ void __launch_bounds__(256) k_tri_solve_batched(int64_t p, const doub
 // rocSOLVER's potrf_strided_batched spent 13 ms on 256 matrices of order 1000 (6.5 TFLOP/s: small-panel kernels
 // and a syr2k-based update); here the flops sit in 15 well-shaped batched GEMMs.
 #define CH_NB 64
-__device__ __forceinline__ void lds_barrier() {  // workgroup barrier that waits for LDS traffic only
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 __global__ void __launch_bounds__(256) k_chol_panel(int64_t p, int64_t j0, int nb, double* Qall, int* info,
                                                     long long* bad, int64_t chain0, unsigned long long* dbg) {
-#define PANEL_STAMP(i) do { if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[(j0 / CH_NB) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
+#define PANEL_STAMP(i) OMC_STAMPED(do { if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[(j0 / CH_NB) * 8 + (i)] = __builtin_readcyclecounter(); } while (0))
   PANEL_STAMP(0);
   __shared__ double D[CH_NB][CH_NB + 1];  // diagonal block, then its Cholesky factor (zero outside the live nb x nb)
   __shared__ double LiT[CH_NB][CH_NB];    // transposed inverse of the factor (row t: column t of L_JJ^-1)
@@ -344,7 +341,7 @@ __global__ void __launch_bounds__(256) k_chol_panel(int64_t p, int64_t j0, int n
   __syncthreads();
   PANEL_STAMP(1);
   // unblocked right-looking Cholesky of the block: all 256 threads tile the (r, cc) update square 16 x 16, two
-  // LDS-only barriers per column (lds_barrier: no wait on vector memory)
+  // LDS-only barriers per column (omc_lds_barrier: no wait on vector memory)
   {
     const int tx = tid & 15, ty = tid >> 4;
     for (int k = 0; k < nb; ++k) {
@@ -358,12 +355,12 @@ __global__ void __launch_bounds__(256) k_chol_panel(int64_t p, int64_t j0, int n
         dinv[k] = rinv;
         if (!ok) failed = 1;
       }
-      lds_barrier();
+      omc_lds_barrier();
       for (int r = k + 1 + ty; r < nb; r += 16) {
         const double lr = D[r][k];
         for (int cc = k + 1 + tx; cc <= r; cc += 16) D[r][cc] = fma(-lr, D[cc][k], D[r][cc]);
       }
-      lds_barrier();
+      omc_lds_barrier();
     }
   }
   PANEL_STAMP(2);

@@ -122,10 +122,8 @@ __global__ void __launch_bounds__(256) k_gram_reduce(int p, int splits, const do
 extern "C" omc_status omc_gram_mfma_launch(omc_ctx* ctx, int64_t n, int64_t p, const double* X, const double* w, double* G_out) {
   const int ntile = (int)((p + GR_TS - 1) / GR_TS);
   const int pairs = ntile * (ntile + 1) / 2;
-  int dev_cus = 256;
-  hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
   // two workgroups per CU; slices at least a few slabs long
-  int splits = (2 * dev_cus) / pairs;
+  int splits = (2 * ctx->dev_cus) / pairs;
   if (splits < 1) splits = 1;
   const int64_t max_splits = (n + 4 * GR_BK - 1) / (4 * GR_BK);
   if (splits > max_splits) splits = (int)max_splits;
