@@ -765,6 +765,32 @@ omc_status omc_store_quantiles(omc_ctx* ctx, int64_t n_iter, int64_t size, const
  * lags) forces a form: same results to rounding.  Deterministic: repeated calls are bit-equal.                    */
 omc_status omc_store_rhat_ess(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store,
                               double* rhat_out, double* ess_out, int32_t* lag_out);
+/* Second moments of the same store: posterior covariance / correlation matrix of its elements, what a user of the reference
+ * computes with np.cov / np.corrcoef on MCMC.store[param].
+ *   store_a [n_iter][C][size_a], store_b [n_iter][C][size_b] (device).  store_b == NULL: "b is a", the symmetric form
+ *           (size_b, idx_b, n_b are then ignored and taken from a);
+ *   idx_a   [n_a] (device) the elements of a that take part, in that order, repeats allowed; NULL = all of them (n_a must then
+ *           equal size_a).  idx_b likewise.  An index outside [0, size) is OMC_INVALID_ARG, found on the device before any
+ *           launch reads through it (the host reads one word back); out is then untouched;
+ *   pooled != 0: out [n_a][n_b] over all R = n_iter C draws around the pooled means, divisor R - 1: the off-diagonal block of
+ *           np.cov(a2d, b2d), a2d = store_a.reshape(R, size_a).T;
+ *   pooled == 0: out [C][n_a][n_b], chain c over its own n_iter draws around its own means, divisor n_iter - 1;
+ *   a single draw gives 0, as omc_store_moments defines its variance;
+ *   correlation != 0: out_ij = c_ij / (sqrt(v_i) sqrt(v_j)), v the variances of the call's means pass (omc_store_moments'
+ *           values), clipped to [-1, 1]; an element with zero variance gives NaN in its row / column (np.corrcoef); in the
+ *           symmetric form an entry whose two sides are the same element (the diagonal, repeats of an index) is exactly 1.
+ *   NaN is propagated like np.cov: an element with a NaN draw (among the draws the entry is taken over: any chain when
+ *   pooled, that chain otherwise) makes its whole row / column NaN and nothing else.  There is no omit_nan form: leaving
+ *   NaN out pair by pair (pairwise deletion) is a different estimator, with a different divisor per entry and no guarantee
+ *   of a positive semi-definite result.
+ *   Symmetric form: out == out' bit for bit (one triangle of tiles is computed and mirrored).
+ * Two passes over the selected columns: their means, then the products of the values centred in fp64 as they are loaded, on
+ * the fp64 matrix cores; the contraction is cut into slices whose partial tiles are added in a fixed order (no atomics):
+ * repeated calls are bit-equal.  Runs on the context's stream; workspace (the partial tiles) from the context.        */
+omc_status omc_store_cov(omc_ctx* ctx, int64_t n_iter,
+                         int64_t size_a, const double* store_a, const int64_t* idx_a, int64_t n_a,
+                         int64_t size_b, const double* store_b, const int64_t* idx_b, int64_t n_b,
+                         int32_t pooled, int32_t correlation, double* out);
 /* Thinned copy of the store for a thinned gather: out[j] = store[first + j * every] (slabs of C * size doubles),
  * j = 0 .. ceil((n_iter - first) / every) - 1 (that count is left in *n_out when n_out is not NULL, host).           */
 omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int64_t first, int64_t every,

@@ -32,6 +32,7 @@ struct omc_ctx {
   double* workspace;       // scratch for the serial kernel (l vectors), grown on demand
   size_t workspace_bytes;
   void* store_ws; size_t store_ws_bytes;  // omc_store.hip: histograms / partial moments of the store summaries
+  double* cov_ws; size_t cov_ws_bytes;  // omc_cov.hip: means, variances and partial tiles of omc_store_cov
   // dense path (omc_dense.hip): rocBLAS handle and workspaces, created on first use
   void* blas;
   // blocked dense factorisation: second half of the chains on a side stream (forked from / joined into `stream` by events),

@@ -1155,6 +1155,50 @@ class Engine:
         check(lib.omc_store_rhat_ess(self._ctx, n_iter, size, self._p(store), self._p(rhat), self._p(ess), lags.data_ptr()))
         return rhat, ess, lags
 
+    def _store_index(self, index, size):
+        """(device int64 tensor or None, number of selected elements) of an element selection of a store"""
+        if index is None:
+            return None, size
+        torch = _torch()
+        if isinstance(index, torch.Tensor):
+            if index.is_floating_point() or index.dtype is torch.bool:
+                raise ValueError("index must hold integers")
+            idx = index.to(device=self.device, dtype=torch.int64).contiguous()
+        else:
+            arr = np.asarray(index)
+            if arr.size and arr.dtype.kind not in "iu":
+                raise ValueError("index must hold integers")
+            idx = torch.as_tensor(np.ascontiguousarray(arr, dtype=np.int64), device=self.device)
+        if idx.dim() != 1 or idx.numel() < 1:
+            raise ValueError("index must be a non-empty one-dimensional sequence")
+        return idx, idx.numel()
+
+    def store_cov(self, store_a, store_b=None, index_a=None, index_b=None, pooled=True, correlation=False):
+        """Covariance (correlation=True: correlation) matrix of the elements of a device store (n_iter, C, size_a), or of
+        its elements against those of a second store (n_iter, C, size_b), computed on the device (omc_store_cov):
+        (n_a, n_b) pooled over chains and iterations, else (C, n_a, n_b) per chain.  index_a / index_b (sequence, numpy or
+        torch integers) select elements, in that order, repeats allowed; without store_b the matrix is that of a with
+        itself and exactly symmetric (index_b is then not accepted).  NaN draws propagate as in np.cov."""
+        torch = _torch()
+        for t in (store_a,) if store_b is None else (store_a, store_b):
+            if t.dim() != 3 or t.shape[1] != self.n_chains or not t.is_contiguous():
+                raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        if store_b is None and index_b is not None:
+            raise ValueError("index_b needs store_b")
+        if store_b is not None and store_b.shape[0] != store_a.shape[0]:
+            raise ValueError("store_a and store_b must hold the same number of iterations")
+        n_iter, _, size_a = store_a.shape
+        idx_a, n_a = self._store_index(index_a, size_a)
+        size_b, idx_b, n_b = size_a, None, n_a
+        if store_b is not None:
+            size_b = store_b.shape[2]
+            idx_b, n_b = self._store_index(index_b, size_b)
+        out = self.empty(*((n_a, n_b) if pooled else (self.n_chains, n_a, n_b)))
+        check(lib.omc_store_cov(self._ctx, n_iter, size_a, self._p(store_a), None if idx_a is None else idx_a.data_ptr(), n_a,
+                                size_b, self._p(store_b), None if idx_b is None else idx_b.data_ptr(), n_b,
+                                int(bool(pooled)), int(bool(correlation)), self._p(out)))
+        return out
+
     def store_thin(self, store, every, first=0):
         """store[first::every] of a device store (n_iter, C, ...) as a packed device tensor (one launch)."""
         if store.dim() < 2 or store.shape[1] != self.n_chains or not store.is_contiguous():

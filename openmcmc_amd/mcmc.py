@@ -399,6 +399,28 @@ class MCMC:
         rhat, ess, var = rhat.cpu().numpy(), ess.cpu().numpy(), var.cpu().numpy()
         return {"rhat": rhat, "ess": ess, "mcse_mean": np.sqrt(var) / np.sqrt(ess)}
 
+    def _store_3d(self, key):
+        t = self.store[key]
+        return (t.unsqueeze(-1) if t.dim() == 2 else t.reshape(t.shape[0], t.shape[1], -1)).contiguous()
+
+    def covariance(self, key, other=None, index=None, other_index=None, pooled=True, correlation=False):
+        """Posterior covariance matrix of the elements of store[key] -- np.cov of the stored draws -- or, with `other`, of
+        its elements against those of store[other] (the off-diagonal block of np.cov of the stacked variables), computed on
+        the device (no gather of the store): pooled over chains and iterations -> (n_a, n_b), else per chain ->
+        (C, n_a, n_b).  index / other_index select elements (in that order, repeats allowed); a 2-D entry ("log_post") counts
+        as one element.  An element with a NaN draw (the padding of variable-size parameters) gives NaN in its row and
+        column; a single stored draw gives 0.  Under a sharded multi-GPU run this is the covariance over this rank's
+        chains only."""
+        self._whole_store_on_device("covariance")
+        a = self._store_3d(key)
+        b = None if other is None else self._store_3d(other)
+        return self.engine.store_cov(a, b, index_a=index, index_b=other_index, pooled=pooled, correlation=correlation).cpu().numpy()
+
+    def correlation(self, key, other=None, index=None, other_index=None, pooled=True):
+        """Posterior correlation matrix -- np.corrcoef of the stored draws: `covariance` scaled by the standard deviations
+        and clipped to [-1, 1]; an element that never moved gives NaN in its row and column."""
+        return self.covariance(key, other=other, index=index, other_index=other_index, pooled=pooled, correlation=True)
+
     def _thinned(self, every):
         """{key: device tensor (ceil(n_iter / every), C, ...)}: every `every`-th stored iteration, packed on the device"""
         self._whole_store_on_device("a thinned transfer")
