@@ -633,6 +633,40 @@ omc_status omc_small_gibbs_truncated(omc_ctx* ctx, int64_t kmax, const double* g
 omc_status omc_small_spd_ops(omc_ctx* ctx, int64_t k, const double* A, const double* v, double* Av_out, double* quad_out,
                              double* logdet_out);
 
+/* LinearCombinationWithTransform.predictor / predictor_conditional (parameter.py:253-279) for a per-chain vector under the
+ * exponential transform and a shared design X [n][ld_X] (row-major, p columns):
+ *   out[c] = alpha * chain_scale[c] * (X exp(x_c)) + add_chain[c] + add_shared
+ * for any n, p (at most 65 535 chains per context, here and in omc_transform_grad_hess: OMC_UNSUPPORTED beyond).  exp is applied as x is read (exp(x) is never stored); it overflows to inf as numpy's does; the sum over the
+ * columns runs in index order.  add_chain [C][ld_add], add_shared [n], chain_scale [C] may be NULL.                        */
+omc_status omc_transform_predict(omc_ctx* ctx, int64_t n, int64_t p, const double* X, int64_t ld_X, const double* x, int64_t ld_x,
+                                 const double* add_chain, int64_t ld_add, const double* add_shared, double alpha,
+                                 const double* chain_scale, double* out, int64_t ld_out);
+
+/* Branch (ii) of Normal.grad_log_p (location_scale.py:234-242) through LinearCombinationWithTransform.grad (parameter.py:281-297):
+ * with s_c = exp(x_c), u_c = A'W sum_rep (y - fitted_c) [C][ld_u] and the shared G = n_rep A'WA [p][p],
+ *   grad[c] = scale[c] * s_c o u_c [C][p],   H[c][i][j] = scale[c] * s_ci s_cj G_ij [C][p][p]
+ * (the reference's Gauss-Newton form: no second-derivative term).  Any p.  scale [C] may be NULL (ones); either output may be
+ * NULL (u is read only for grad, G only for H).                                                                            */
+omc_status omc_transform_grad_hess(omc_ctx* ctx, int64_t p, const double* x, int64_t ld_x, const double* u, int64_t ld_u,
+                                   const double* G, const double* scale, double* grad, double* H);
+
+/* One ManifoldMALA update (metropolis_hastings.py:127-173 accept/reject, :301-373 proposal) of a per-chain vector x [C][ld_x],
+ * p <= 64, whose target is  y ~ N(A exp(x) + shared terms, tau_c W),  x ~ N(m0, lam_c P), on the sufficient statistics
+ * G = n_rep A'WA [p][p], cvec = A'W sum_rep (y - shared terms) [p] and the dense prior precision P [p][p]:
+ *   t = exp(x);  g = tau_c t o (cvec - G t) - lam_c P (x - m0);  Lambda = (tau_c (t t') o G + lam_c P) / step^2 = L L'
+ *   (natural order; a non-positive pivot latches the chain and leaves x as it is);  mu = x + Lambda^-1 g / 2;  x' = mu + L^-T z;
+ *   log q(x'|x) = sum log L_ii - |L'(x' - mu)|^2 / 2, the same at x' for log q(x|x');  accept iff
+ *   log u < target(x') - target(x) + log q(x|x') - log q(x'|x),  target = tau_c (t'cvec - t'G t / 2) - lam_c (x-m0)'P(x-m0) / 2.
+ * One launch for every chain.  G and P are symmetric; the kernel reads element (i, j) at [j * p + i].  z_inject [C][p] / u_inject [C]; NULL: the normals of (seed, chain, draw_index) blocks i/2 and the
+ * uniform of block (p+1)/2 + 1, the streams omc_small_sample_canonical and omc_mh_accept read on the launch-by-launch route.
+ * m0 [p], tau [C], lam [C] may be NULL (zeros / ones).  accept_count / proposal_count [C] are incremented; prop_out [C][p],
+ * lq_fwd_out, lq_rev_out and logp_out [C] (the target, up to its constant, at the state left in x) may be NULL.            */
+omc_status omc_mala_transform_step(omc_ctx* ctx, int64_t p, const double* G, const double* cvec, const double* P, const double* m0,
+                                   const double* tau, const double* lam, double step, double* x, int64_t ld_x,
+                                   const double* z_inject, const double* u_inject, uint64_t draw_index, int64_t* accept_count,
+                                   int64_t* proposal_count, double* prop_out, double* lq_fwd_out, double* lq_rev_out,
+                                   double* logp_out);
+
 /* ReversibleJump.matched_birth_transition / matched_death_transition (reversible_jump.py:195-308):
  *   with X the larger of the two bases (the proposed one for a birth, the current one for a death),
  *   G = (X'X + 1e-10 I)^{-1} X'X_small by LU with partial pivoting (np.linalg.solve);

@@ -14,7 +14,7 @@ from scipy import sparse
 
 from openmcmc_amd.chains import is_chain
 from openmcmc_amd.distribution.distribution import Distribution
-from openmcmc_amd.parameter import (Identity, LinearCombination, MixtureParameterMatrix, MixtureParameterVector,
+from openmcmc_amd.parameter import (Identity, LinearCombination, LinearCombinationWithTransform, MixtureParameterMatrix, MixtureParameterVector,
                                      ScaledMatrix, _is_identity)
 
 
@@ -212,9 +212,20 @@ class Normal(Distribution):
         if hit is not None:  # the draw that produced this state computed it (NormalNormal.sample)
             return hit
         resp = state[self.response]
+        transformed = isinstance(self.mean, LinearCombinationWithTransform) and self.mean.is_transformed()
         dense_design = (isinstance(self.mean, LinearCombination) and not is_chain(resp)
-                        and any(is_chain(state[k]) and not _is_identity(state[a], state[k].shape[0])
+                        and any(is_chain(state[k]) and (transformed or not _is_identity(state[a], state[k].shape[0]))
                                 for k, a in self.mean.form.items()))
+        rep_mult, rep_const = 1.0, 0.0
+        if dense_design and transformed and resp.shape[1] != 1 and replicates:
+            # replicated response under an exp-transformed mean (location_scale.py:236 sums the replicates): the residual form
+            # around ybar times n_rep, plus the spread of the replicates around it (_replicate_split)
+            ybar, rep_const = self._replicate_split(st, np.asarray(resp, dtype=np.float64))
+            memo = self.__dict__.setdefault("_ybar_memo", {})
+            hit = memo.get(id(resp))
+            if hit is None or hit[0] is not resp:
+                hit = memo[id(resp)] = (resp, ybar)
+            rep_mult, resp = float(resp.shape[1]), hit[1]
         if dense_design and (st.diag is False or st.off is not None):
             # a correlated response under a design matrix: r_c = y - fitted_c on the device, then r'Wr on W's own route
             if resp.shape[1] != 1:
@@ -222,6 +233,10 @@ class Normal(Distribution):
             frozen = getattr(self.mean, "_frozen", None)
             fitted = self.mean.predictor_device(state, engine)
             r = engine.chain_lincomb(-1.0, fitted, 1.0, engine.shared(resp).reshape(-1))
+            if rep_mult != 1.0:
+                if st.diag is False and st.band is None:
+                    return engine.dense_quadform(engine.shared(st.matrix), r) * rep_mult + rep_const
+                raise NotImplementedError("replicated responses under a banded precision and a transformed mean")
             if st.diag is False and st.band is None:
                 return engine.dense_quadform(engine.shared(st.matrix), r)
             quad = engine.empty(engine.n_chains)
@@ -244,7 +259,7 @@ class Normal(Distribution):
             fitted = self.mean.predictor_device(state, engine)
             quad = engine.empty(engine.n_chains)
             engine.weighted_resid_sq(engine.shared(resp).reshape(-1), fitted, quad, w=w)
-            return quad
+            return quad if rep_mult == 1.0 else quad * rep_mult + rep_const
         if st.diag is False and st.band is None:
             # dense shared precision: r'Mr through one GEMM over all chains
             x, m = self.chain_and_center(state)
@@ -606,7 +621,14 @@ class Normal(Distribution):
     def constant_hessian(self, param: str) -> bool:
         """Is this distribution Gaussian in `param` (Hessian independent of it: branches (i) and (ii) of
         location_scale.py:190-250)?  Then ManifoldMALA may take the dense route built on grad_terms."""
+        if self._transformed_param(param):
+            return False  # H_c = n_rep (s_c s_c') o (A'WA) moves with the state
         return param == self.response or (param in self.mean.get_grad_param_list() and param not in self.precision.get_grad_param_list())
+
+    def _transformed_param(self, param: str) -> bool:
+        """Does `param` enter the mean under the exponential transform of a LinearCombinationWithTransform?"""
+        return (isinstance(self.mean, LinearCombinationWithTransform) and param != self.response and param in self.mean.form
+                and self.mean._transformed(param))
 
     def grad_terms(self, state: dict, param: str, engine):
         """This distribution's share of the gradient and Hessian w.r.t. a per-chain (p, 1) parameter, in the form the
@@ -718,6 +740,11 @@ class Normal(Distribution):
                 g = engine.design_predict(hit[1], r.contiguous())  # rows of r times A: (C, p)
                 H = hit[2]
             scale = state[st.scale_key].scalar() if st.scale_key is not None else None
+            if self._transformed_param(param):
+                # parameter.py:281-297 in location_scale.py:237-241: the rows of the mean's gradient carry s_c = exp(x_c), so
+                # grad_c = s_c o (A'W sum_rep (y - fitted_c)) and H_c = n_rep (s_c s_c') o (A'WA), per chain (Gauss-Newton form)
+                gt, Hc = engine.transform_grad_hess(x.vector(), engine.shared(H), u=g, scale=scale, want_hess=hessian_required)
+                return (ChainArray(gt), Hc) if hessian_required else ChainArray(gt)
             if scale is not None:
                 g = g * scale.unsqueeze(1)
             grad = ChainArray(g)

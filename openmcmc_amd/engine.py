@@ -943,6 +943,48 @@ class Engine:
                                     self._chain_scalar(logdet)))
         return Av, quad, logdet
 
+    # ------------------------------------------------------------------ exp-transformed regression terms
+    def transform_predict(self, X, x, add_chain=None, add_shared=None, alpha=1.0, chain_scale=None, out=None):
+        """out[c] = alpha * chain_scale[c] * (X exp(x_c)) + add_chain[c] + add_shared for a shared design X (n, p) on the
+        device and per-chain x (C, p) (omc_transform_predict)."""
+        n, p = X.shape
+        Cn = self.n_chains
+        out = self.empty(Cn, n) if out is None else out
+        check(lib.omc_transform_predict(self._ctx, n, p, self._p(X), X.stride(0), self._p(x, Cn, p), x.stride(0),
+                                        self._p(add_chain, Cn, n), 0 if add_chain is None else add_chain.stride(0),
+                                        self._vec(add_shared, n), float(alpha), self._chain_scalar(chain_scale),
+                                        self._p(out, Cn, n), out.stride(0)))
+        return out
+
+    def transform_grad_hess(self, x, G, u=None, scale=None, want_hess=True):
+        """(grad (C, p) or None, H (C, p, p) or None) = (scale s o u, scale (s s') o G) with s = exp(x)
+        (omc_transform_grad_hess); grad needs u (C, p)."""
+        Cn, p = x.shape
+        grad = self.empty(Cn, p) if u is not None else None
+        H = self.empty(Cn, p, p) if want_hess else None
+        check(lib.omc_transform_grad_hess(self._ctx, p, self._p(x, Cn, p), x.stride(0), self._p(u, Cn, p),
+                                          0 if u is None else u.stride(0), self._vec(G, p * p), self._chain_scalar(scale),
+                                          self._p(grad), None if H is None else self._p(H.view(Cn, -1))))
+        return grad, H
+
+    def mala_transform_step(self, G, cvec, P, step, x, m0=None, tau=None, lam=None, z=None, u=None, draw_index=0,
+                            accept_count=None, proposal_count=None, prop_out=None, lq_fwd_out=None, lq_rev_out=None,
+                            log_p_out=None):
+        """One fused position-dependent ManifoldMALA step on x (C, p), p <= 64, in place (omc_mala_transform_step)."""
+        Cn, p = x.shape
+        if z is not None and (tuple(z.shape) != (Cn, p) or not z.is_contiguous()):
+            raise ValueError("z must be a contiguous (C, p) tensor")
+        if prop_out is not None and (tuple(prop_out.shape) != (Cn, p) or not prop_out.is_contiguous()):
+            raise ValueError("prop_out must be a contiguous (C, p) tensor")
+        check(lib.omc_mala_transform_step(self._ctx, p, self._vec(G, p * p), self._vec(cvec, p), self._vec(P, p * p),
+                                          self._vec(m0, p), self._chain_scalar(tau), self._chain_scalar(lam), float(step),
+                                          self._p(x, Cn, p), x.stride(0), self._p(z), self._chain_scalar(u), int(draw_index),
+                                          None if accept_count is None else self._i64(accept_count),
+                                          None if proposal_count is None else self._i64(proposal_count),
+                                          self._p(prop_out), self._chain_scalar(lq_fwd_out), self._chain_scalar(lq_rev_out),
+                                          self._chain_scalar(log_p_out)))
+        self.note_write(x)
+
     # per-chain SPD matrices beyond one wave's 64 columns (the generic ManifoldMALA route with a parameter-dependent Hessian):
     # batched dense factorisations as tensor expressions on the context's stream -- a rarely taken generic branch, natural-order
     # Cholesky like everywhere else (the factor is unique: the same draw for the same z as the small-matrix kernels)

@@ -1,7 +1,7 @@
 """Parameter objects: how a distribution parameter is built from named state entries.
 
 Same names, fields and meaning as the reference (parameter.py:74-141 Identity, :144-228
-LinearCombination, :300-373 ScaledMatrix).  They are declarative: samplers read `form` /
+LinearCombination, :231-297 LinearCombinationWithTransform, :300-373 ScaledMatrix).  They are declarative: samplers read `form` /
 `matrix` / `scalar` to lay out GPU work; `predictor` evaluates on host constants and, for
 per-chain entries, returns ChainArray results for the cases the hot path needs.
 """
@@ -188,6 +188,105 @@ class LinearCombination(Parameter):
 
     def get_grad_param_list(self) -> list:
         return list(self.form.keys())
+
+
+@dataclass
+class LinearCombinationWithTransform(LinearCombination):
+    """f = sum_i state[prefactor_i] @ g_i(state[param_i]) with g_i = exp where transform[param_i], the identity otherwise
+    (parameter.py:231-297): positivity of a regression-type parameter without a truncated prior.  The transform applies to the
+    whole named vector.  With every transform False it is LinearCombination, bit for bit."""
+
+    transform: dict
+
+    def _transformed(self, prm) -> bool:
+        return bool(self.transform.get(prm, False))
+
+    def is_transformed(self, exclude=None) -> bool:
+        """Is any term other than `exclude` under the exponential transform?"""
+        skip = [] if exclude is None else ([exclude] if isinstance(exclude, str) else list(exclude))
+        return any(self._transformed(prm) and prm not in skip for prm in self.form)
+
+    def predictor_conditional(self, state: dict, term_to_exclude: Union[str, list] = None):
+        """parameter.py:253-279 on host values.  A per-chain transformed term needs the engine (predictor_device): summing it here
+        the way LinearCombination sums identity terms would drop the exp."""
+        skip = [] if term_to_exclude is None else ([term_to_exclude] if isinstance(term_to_exclude, str) else term_to_exclude)
+        if not self.is_transformed(exclude=skip):
+            return super().predictor_conditional(state, term_to_exclude)
+        total = 0
+        for prm, prefactor in self.form.items():
+            if prm in skip:
+                continue
+            A, v = state[prefactor], state[prm]
+            if is_chain(v) or is_chain(A):
+                raise NotImplementedError("a per-chain term next to an exp-transformed term on host sums: use predictor_device "
+                                          "(needs the engine)")
+            total = total + A @ (np.exp(v) if self._transformed(prm) else v)
+        return total
+
+    def grad(self, state: dict, param: str):
+        """(n_param x n_data) derivative of the predictor w.r.t. a host-valued `param` (parameter.py:281-297)."""
+        from scipy import sparse
+
+        A, v = state[self.form[param]], state[param]
+        if is_chain(v) or is_chain(A):
+            raise NotImplementedError("grad of a per-chain term: Normal.grad_log_p evaluates it on the device")
+        if self._transformed(param):
+            if sparse.issparse(A):
+                return A.multiply(np.exp(v).flatten()).T
+            return np.exp(v) * (A.T)
+        return A.T
+
+    def _predictor_device(self, state: dict, engine, out, exclude, alpha, chain_scale):
+        skip = [] if exclude is None else ([exclude] if isinstance(exclude, str) else list(exclude))
+        if not self.is_transformed(exclude=skip):
+            return super()._predictor_device(state, engine, out, exclude, alpha, chain_scale)
+        host_sum, tchain, plain_chain = 0, [], []
+        for prm, prefactor in self.form.items():
+            if prm in skip:
+                continue
+            A, v = state[prefactor], state[prm]
+            if not self._transformed(prm):
+                if is_chain(v) or is_chain(A):
+                    plain_chain.append(prm)
+                else:
+                    host_sum = host_sum + A @ v
+            elif is_chain(A):
+                raise NotImplementedError("an exp-transformed term with a per-chain design matrix")
+            elif not is_chain(v):
+                host_sum = host_sum + A @ np.exp(v)
+            elif v.shape[1] != 1 or v.ragged is not None:
+                raise NotImplementedError("an exp-transformed per-chain term must be a fixed-size (p, 1) vector")
+            else:
+                tchain.append((A, v))
+        shared = None if isinstance(host_sum, int) else engine.to_device(np.asarray(host_sum, dtype=np.float64).reshape(-1))
+        fitted = None
+        if plain_chain:  # the untransformed per-chain terms on today's paths, as a per-chain offset
+            others = [prm for prm in self.form if prm not in plain_chain]
+            fitted = LinearCombination._predictor_device(self, state, engine, None, others, 1.0, None)
+        if not tchain:
+            if fitted is None:
+                raise ValueError("no per-chain term: use predictor()")
+            if shared is not None:
+                fitted = engine.chain_lincomb(1.0, fitted, 1.0, shared)
+        scaled = alpha != 1.0 or chain_scale is not None
+        whole = scaled and len(tchain) == 1 and fitted is None and shared is None  # the kernel's own alpha * scale_c
+        for k, (A, v) in enumerate(tchain):
+            last = k == len(tchain) - 1
+            fitted = engine.transform_predict(engine.shared(A), v.vector(), add_chain=fitted, add_shared=shared if k == 0 else None,
+                                              alpha=alpha if whole else 1.0, chain_scale=chain_scale if whole else None,
+                                              out=out if (last and (whole or not scaled)) else None)
+        if scaled and not whole:
+            fitted = engine.tridiag_matvec_chain(fitted.shape[1], None, None, fitted, scale=_scaled(engine, chain_scale, alpha))
+        if out is not None and fitted.data_ptr() != out.data_ptr():
+            engine.chain_copy(fitted, out) if (fitted.stride(1) == 1 and out.stride(1) == 1) else out.copy_(fitted)
+            fitted = out
+        return fitted
+
+    def resid_sq_device(self, state: dict, engine, y, w=None):
+        """None while any term is transformed (the one-pass residual reads the basis times the raw coefficients)."""
+        if self.is_transformed():
+            return None
+        return super().resid_sq_device(state, engine, y, w)
 
 
 @dataclass

@@ -315,7 +315,7 @@ class RandomWalkLoop(RandomWalk):
         (then the loop runs launch by launch through the callback)."""
         from openmcmc_amd.basis import GaussianKnotBasis
         from openmcmc_amd.distribution.distribution import Uniform
-        from openmcmc_amd.parameter import LinearCombination, _is_identity
+        from openmcmc_amd.parameter import LinearCombination, LinearCombinationWithTransform, _is_identity
 
         basis = self.state_update_function
         if not isinstance(basis, GaussianKnotBasis) or basis.knots != self.param or self.trace is not None:
@@ -344,6 +344,8 @@ class RandomWalkLoop(RandomWalk):
                 return None
         if lik is None or not isinstance(lik.mean, LinearCombination):
             return None
+        if isinstance(lik.mean, LinearCombinationWithTransform) and lik.mean.is_transformed():
+            return None  # the kernel sums basis x coefficients itself: an exp-transformed term goes launch by launch through log_p
         resp = state[lik.response]
         if is_chain(resp) or resp.shape[1] != 1:
             return None
@@ -420,9 +422,98 @@ class RandomWalkLoop(RandomWalk):
 class ManifoldMALA(MetropolisHastings):
     """Manifold MALA (Girolami & Calderhead 2011; metropolis_hastings.py:292-373).  `whitened` (default True): the fused
     route for a Gaussian target runs in the coordinates a = L'(x - mu), where the step is element-wise
-    (omc_mala_step_white); False keeps it on the products of omc_mala_step."""
+    (omc_mala_step_white); False keeps it on the products of omc_mala_step.  `fused` (default True): a parameter under the
+    exponential transform of a LinearCombinationWithTransform takes its whole update in one launch when the model allows it
+    (`_transform_plan`); False keeps it on the launch-by-launch route (`_general_step`)."""
 
     whitened: bool = True
+    fused: bool = True
+
+    def _transform_plan(self, state):
+        """Can the whole update go to omc_mala_transform_step?  Yes when the parameter is a fixed-size per-chain (p, 1) vector,
+        p <= 64, without domain limits, that appears in exactly one likelihood Normal -- as an exp-transformed term of its
+        LinearCombinationWithTransform mean with a shared design, every other term shared, a shared response (any number of
+        replicates) and a shared precision matrix, optionally times a per-chain scalar -- and whose own distribution is a
+        non-mixture Normal with shared mean and shared precision matrix, optionally times a per-chain scalar.  Then target,
+        gradient and Hessian at any x need only G = n_rep A'WA, c = A'W sum_rep (y - shared terms) and the prior: computed
+        once on the host and kept while the state entries they were made from are the same objects.  None otherwise (the
+        launch-by-launch route takes the step)."""
+        from scipy import sparse
+
+        from openmcmc_amd.parameter import LinearCombinationWithTransform
+
+        x = state[self.param]
+        if (not self.fused or np.size(self.step) != 1 or not is_chain(x) or x.ragged is not None or x.shape[1] != 1
+                or x.shape[0] > 64 or not x.data.is_contiguous()):
+            return None
+        prior, lik = self.model.get(self.param), None
+        for key, dist in self.model.items():
+            if key == self.param or self.param not in dist.param_list:
+                continue
+            if lik is not None:
+                return None
+            lik = dist
+        if lik is None or not isinstance(prior, Normal) or type(lik) is not Normal or type(prior) is not Normal:
+            return None
+        if prior.is_mixture or lik.is_mixture or prior.domain_response_lower is not None or prior.domain_response_upper is not None:
+            return None
+        mean = lik.mean
+        if (not isinstance(mean, LinearCombinationWithTransform) or self.param not in mean.form or not mean._transformed(self.param)
+                or self.param in lik.precision.get_param_list() or mean.has_chain_terms(state, exclude=self.param)):
+            return None
+        A, resp = state[mean.form[self.param]], state[lik.response]
+        if is_chain(A) or is_chain(resp) or any(is_chain(state[k]) for k in prior.mean.get_param_list()):
+            return None
+        try:
+            st_l, st_p = lik.structure(state), prior.structure(state)
+        except NotImplementedError:
+            return None
+        for st in (st_l, st_p):
+            if st.scale_key is not None and not is_chain(state[st.scale_key]):
+                return None
+        # the host objects the statistics are made from: kept in the memo and compared with `is` (an id() alone can be reused)
+        made_from = [A, resp, st_l.matrix, st_p.matrix] + [state[k] for k in mean.get_param_list() if k != self.param] \
+            + [state[k] for k in prior.mean.get_param_list()]
+        memo = getattr(self, "_transform_memo", None)
+        if memo is None or len(memo[0]) != len(made_from) or any(a is not b for a, b in zip(memo[0], made_from)):
+            eng = self._need_engine()
+            dense = lambda M: M.toarray() if sparse.issparse(M) else np.asarray(M, dtype=np.float64)  # noqa: E731
+            Ad, Y = dense(A), np.asarray(resp, dtype=np.float64)
+            rest = mean.predictor_conditional(state, term_to_exclude=self.param)
+            ysum = (Y - (0.0 if isinstance(rest, int) else np.asarray(rest, dtype=np.float64))).sum(axis=1)
+            WA = np.asarray(st_l.matrix @ Ad, dtype=np.float64)
+            G = float(Y.shape[1]) * (Ad.T @ WA)
+            m0 = np.asarray(prior.mean.predictor(state), dtype=np.float64).reshape(-1)
+            # (the kernel reads element (i, j) at [j * p + i]: the transposes, so that it sees exactly these matrices)
+            stats = {"G": eng.to_device(np.ascontiguousarray(G.T)), "c": eng.to_device(WA.T @ ysum),
+                     "P": eng.to_device(np.ascontiguousarray(dense(st_p.matrix).T)),
+                     "m0": eng.to_device(m0) if np.any(m0) else None}
+            memo = self._transform_memo = (made_from, stats)
+        plan = dict(memo[1])
+        plan["tau"] = state[st_l.scale_key].scalar() if st_l.scale_key is not None else None
+        plan["lam"] = state[st_p.scale_key].scalar() if st_p.scale_key is not None else None
+        return plan
+
+    def _transform_step(self, current_state: dict, plan: dict) -> dict:
+        """metropolis_hastings.py:127-173 and :301-373 as one launch (omc_mala_transform_step): forward proposal, reverse
+        proposal and the accept test on the p x p statistics of `_transform_plan`; x is updated in place."""
+        eng = self.engine
+        x = current_state[self.param]
+        xv = x.vector()
+        Cn, p = xv.shape
+        z = self.inject(self, self._sweep) if self.inject is not None else None
+        u = self.inject_uniform(self, self._sweep) if self.inject_uniform is not None else None
+        prop = lq_f = lq_r = None
+        if self.trace is not None:
+            prop, lq_f, lq_r = eng.empty(Cn, p), eng.empty(Cn), eng.empty(Cn)
+            self.trace.setdefault("steps", []).append({"prop": prop, "lq_fwd": lq_f, "lq_rev": lq_r})
+        eng.mala_transform_step(plan["G"], plan["c"], plan["P"], float(self.step.item()), xv, m0=plan["m0"], tau=plan["tau"],
+                                lam=plan["lam"], z=None if z is None else z.reshape(Cn, p).contiguous(), u=u,
+                                draw_index=self._draw_index(), accept_count=self.accept_rate.accept,
+                                proposal_count=self.accept_rate.proposal, prop_out=prop, lq_fwd_out=lq_f, lq_rev_out=lq_r)
+        # x was updated in place; a new wrapper, so that anything keyed on the identity of a state entry sees it as replaced
+        current_state[self.param] = x.like(x.data)
+        return current_state
 
     def _diag_step(self, current_state: dict) -> dict:
         """Generic route when the Hessian is diagonal per chain (e.g. the mixture-Normal prior of a variable-size
@@ -606,8 +697,11 @@ class ManifoldMALA(MetropolisHastings):
             diag_only = x.ragged is not None or all(
                 getattr(d, "is_mixture", False) and k == self.param or type(d).__name__ == "NullDistribution"
                 for k, d in self.model.items())
+            plan = None if diag_only else self._transform_plan(current_state)
             if diag_only:
                 current_state = self._diag_step(current_state)
+            elif plan is not None:
+                current_state = self._transform_step(current_state, plan)
             else:
                 structured = all(hasattr(d, "grad_terms") and d.constant_hessian(self.param)
                                  for d in self.model.values() if self.param in d.param_list)

@@ -172,6 +172,9 @@ class NormalNormal(MCMCSampler):
                         raise TypeError("mean of the response does not depend on the parameter")
                     rest = 0.0
                 else:
+                    if dist._transformed_param(self.param):
+                        raise NotImplementedError(f"'{self.param}' enters the mean of '{key}' under the exponential transform: "
+                                                  "its conditional is not Gaussian (use ManifoldMALA)")
                     A = state[dist.mean.form[self.param]]
                     if not _is_identity(A, n):
                         piece["design"] = A
