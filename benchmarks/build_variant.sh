@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build a variant of libomcmc_hip.so with extra -D flags on omc_tridiag.hip (A/B timing, benchmarks/ab_headline.py):
 #   bash benchmarks/build_variant.sh NAME "-DOMC_WHATIF_NOSTORE=1"   ->  build/ab/libomcmc_hip_NAME.so
+# Switches (omc_tridiag_seg.h): OMC_PARK_OFF OMC_PARK_DIAG OMC_SHIFT_PARK_C OMC_PREFETCH_QUAD OMC_WHATIF_NOSTORE OMC_WHATIF_NOQLOAD OMC_NO_STAMPS
 set -e
 root=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; flags=$2

@@ -7,7 +7,7 @@
 
 2. Entry state of the self-restarting workgroups.  omc_gmrf_run's default launch form ends a sweep with `s_setpc_b64` to the
    kernel's first instruction after setting s[0:1] (kernel-argument pointer), s2 (workgroup id) and v0 (work-item id) by
-   hand (omc_tridiag.hip, OMC_REENTER).  That reproduces a fresh workgroup only while the kernel descriptor asks the
+   hand (omc_tridiag_seg.h, OMC_REENTER).  That reproduces a fresh workgroup only while the kernel descriptor asks the
    dispatcher for exactly those registers.  The descriptors of the two re-entered instantiations are taken from the code
    object this source compiles to and handed to the library's own test (omc_reentry_descriptor_ok -- the one the library
    applies at run time to the descriptors it reads back from the device); deliberately altered descriptors must fail it."""

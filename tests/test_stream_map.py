@@ -29,7 +29,7 @@ def sweep_draw(t, pos):
 def fused_run_draw(t0, t, gdraw):
     """omc_gmrf_run: sweep t of a run that starts at sweep t0 has rec.draw = draw_index0 + t * draws_per_sweep with
     draw_index0 = t0 * ns (mcmc.py), and its Gamma term k draws at rec.draw + gdraw[k], gdraw[k] = the block's position
-    (omc_tridiag.hip sweep_gamma_key)."""
+    (omc_tridiag_args.h sweep_gamma_key)."""
     return (t0 * NS + t * NS) + gdraw
 
 
