@@ -50,14 +50,29 @@ struct omc_ctx {
   double* dense_tmp; size_t dense_tmp_bytes;
   double* rj_tmp; size_t rj_tmp_bytes;   // omc_knot_loop: the proposals of all knots
   double* mh_work; size_t mh_work_bytes;  // omc_mala.hip
-  double* mala_prep; size_t mala_prep_bytes;  // cached drift matrix and L^{-T} of the current (Q, L, step)
-  const double* mala_Q; const double* mala_L; double mala_step; int64_t mala_d;
-  double* white_prep; size_t white_prep_bytes; const double* white_L; const double* white_mu; int64_t white_d;  // omc_mala_step_white
-  double* white_a; size_t white_a_bytes; const double* white_x; int64_t white_ld;  // a = L'(x - mu) of the state at white_x
-  double* white_traj; size_t white_traj_bytes;  // omc_mala_run_white: the whitened states of two blocks of steps [2][32][C][d]
-  hipEvent_t white_ev[4];  // ... trajectory of block b written (0, 1) / mapped back by the product on the side stream (2, 3)
-  double* rww_a; size_t rww_a_bytes; const double* rww_x; int64_t rww_ld; const double* rww_mu; double* rww_mu_neg; size_t rww_mu_bytes;  // omc_rw_step_white
-  double* rw_prep; size_t rw_prep_bytes; const double* rw_LQ; int64_t rw_d;  // omc_rw_step: LQ with a zero upper triangle
+  // What the fused Metropolis-Hastings steps (omc_mala.hip) keep between calls, one struct per route: device buffers, grown on
+  // demand and freed with the context, and the caller's pointers they were filled for.  reset() (omc_mh_invalidate) forgets
+  // the pointers and keeps the buffers.
+  struct {  // omc_mala_step
+    double* prep; size_t prep_bytes;  // cached drift matrix and L^{-T} of the current (Q, L, step)
+    const double* Q; const double* L; double step; int64_t d;
+    void reset() { Q = nullptr; L = nullptr; step = 0.0; d = 0; }
+  } mala;
+  struct {  // omc_mala_step_white, omc_mala_run_white
+    double* prep; size_t prep_bytes; const double* L; const double* mu; int64_t d;
+    double* a; size_t a_bytes; const double* x; int64_t ld;  // a = L'(x - mu) of the state at x
+    double* traj; size_t traj_bytes;  // omc_mala_run_white: the whitened states of two blocks of steps [2][32][C][d]
+    hipEvent_t ev[4];  // ... trajectory of block b written (0, 1) / mapped back by the product on the side stream (2, 3)
+    void reset() { L = nullptr; mu = nullptr; d = 0; x = nullptr; }
+  } white;
+  struct {  // omc_rw_step_white
+    double* a; size_t a_bytes; const double* x; int64_t ld; const double* mu; double* mu_neg; size_t mu_bytes;
+    void reset() { x = nullptr; mu = nullptr; }
+  } rww;
+  struct {  // omc_rw_step, omc_rw_step_white: LQ with a zero upper triangle, then its transpose
+    double* prep; size_t prep_bytes; const double* LQ; int64_t d;
+    void reset() { LQ = nullptr; d = 0; }
+  } rw;
   int tridiag_algo;  // 0 auto, 1 serial, 2 segmented
   int tridiag_seg;   // 0 auto, else nodes per lane
   int debug_zero_z;  // diagnostic: skip the draw generation (timing what-if only)
@@ -211,6 +226,13 @@ __device__ __forceinline__ uint4 omc_rng_block(const omc_rng_key& k, int64_t glo
 __device__ __forceinline__ double omc_u53(uint32_t lo, uint32_t hi) {
   unsigned long long v = (unsigned long long)lo ^ ((unsigned long long)hi << 21);
   return 0x1.0p-53 + (double)v * 0x1.0p-53;
+}
+// A chain's uniform for an accept decision: the injected u_in[idx], or words 0-1 of `block` of its uniform stream.
+__device__ __forceinline__ double omc_chain_uniform(const double* u_in, int64_t idx, const omc_rng_key& key, int64_t global_chain,
+                                                    uint32_t block) {
+  if (u_in) return u_in[idx];
+  const uint4 w = omc_rng_block(key, global_chain, block);
+  return omc_u53(w.x, w.y);
 }
 
 // ---- lean fp64 elementary functions for the Box-Muller transform -------------------------------

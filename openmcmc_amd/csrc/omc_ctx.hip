@@ -48,13 +48,7 @@ omc_status omc_ctx_create(int32_t device, int64_t n_chains, uint64_t seed, int64
   c->dense_tmp = nullptr; c->dense_tmp_bytes = 0;
   c->rj_tmp = nullptr; c->rj_tmp_bytes = 0;
   c->mh_work = nullptr; c->mh_work_bytes = 0;
-  c->white_prep = nullptr; c->white_prep_bytes = 0; c->white_L = nullptr; c->white_mu = nullptr; c->white_d = 0;
-  c->white_a = nullptr; c->white_a_bytes = 0; c->white_x = nullptr; c->white_ld = 0;
-  c->white_traj = nullptr; c->white_traj_bytes = 0;
-  for (int i = 0; i < 4; ++i) c->white_ev[i] = nullptr;
-  c->rww_a = nullptr; c->rww_a_bytes = 0; c->rww_x = nullptr; c->rww_ld = 0; c->rww_mu = nullptr; c->rww_mu_neg = nullptr; c->rww_mu_bytes = 0;
-  c->rw_prep = nullptr; c->rw_prep_bytes = 0; c->rw_LQ = nullptr; c->rw_d = 0;
-  c->mala_prep = nullptr; c->mala_prep_bytes = 0; c->mala_Q = nullptr; c->mala_L = nullptr; c->mala_step = 0.0; c->mala_d = 0;
+  c->mala = {}; c->white = {}; c->rww = {}; c->rw = {};  // no buffers, no events, nothing cached
   c->tridiag_algo = 0;
   c->tridiag_seg = 0;
   c->tridiag_generic = 0;
@@ -113,13 +107,13 @@ omc_status omc_ctx_destroy(omc_ctx* ctx) {
   if (ctx->dense_tmp) hipFree(ctx->dense_tmp);
   if (ctx->rj_tmp) hipFree(ctx->rj_tmp);
   if (ctx->mh_work) hipFree(ctx->mh_work);
-  if (ctx->mala_prep) hipFree(ctx->mala_prep);
-  if (ctx->white_prep) hipFree(ctx->white_prep);
-  if (ctx->white_a) hipFree(ctx->white_a);
-  if (ctx->white_traj) hipFree(ctx->white_traj);
-  if (ctx->rww_a) hipFree(ctx->rww_a);
-  if (ctx->rww_mu_neg) hipFree(ctx->rww_mu_neg);
-  if (ctx->rw_prep) hipFree(ctx->rw_prep);
+  if (ctx->mala.prep) hipFree(ctx->mala.prep);
+  if (ctx->white.prep) hipFree(ctx->white.prep);
+  if (ctx->white.a) hipFree(ctx->white.a);
+  if (ctx->white.traj) hipFree(ctx->white.traj);
+  if (ctx->rww.a) hipFree(ctx->rww.a);
+  if (ctx->rww.mu_neg) hipFree(ctx->rww.mu_neg);
+  if (ctx->rw.prep) hipFree(ctx->rw.prep);
   omc_dense_release(ctx);
   hipFree(ctx->d_bad_chain);
   if (ctx->own_stream) hipStreamDestroy(ctx->stream);

@@ -593,7 +593,7 @@ void omc_dense_release(omc_ctx* ctx) {
     hipEventDestroy(ctx->ev_join);
     hipStreamDestroy(ctx->aux_stream);
     for (int i = 0; i < 4; ++i)
-      if (ctx->white_ev[i]) { hipEventDestroy(ctx->white_ev[i]); ctx->white_ev[i] = nullptr; }
+      if (ctx->white.ev[i]) { hipEventDestroy(ctx->white.ev[i]); ctx->white.ev[i] = nullptr; }
     ctx->blas_aux = nullptr;
   }
 }

@@ -121,13 +121,7 @@ __global__ void k_mh_accept(int64_t C, int64_t chain_offset, const double* lp_cu
     return;
   }
   const double la = lp_prop[c] + (lq_rev ? lq_rev[c] : 0.0) - (lp_cur[c] + (lq_fwd ? lq_fwd[c] : 0.0));
-  double u;
-  if (u_in) {
-    u = u_in[c];
-  } else {
-    const uint4 w = omc_rng_block(key, chain_offset + c, sub);
-    u = omc_u53(w.x, w.y);
-  }
+  const double u = omc_chain_uniform(u_in, c, key, chain_offset + c, sub);
   const int acc = log(u) < la;  // NaN log_alpha rejects, as in the reference
   accept[c] = acc;
   if (log_alpha) log_alpha[c] = la;

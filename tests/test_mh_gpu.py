@@ -513,10 +513,16 @@ def test_whitened_steps_are_in_the_write_log(kind):
 
 
 @pytest.mark.parametrize("d,C,steps,inject", [(5, 3, 7, True), (500, 33, 70, False), (137, 70, 40, True), (1100, 5, 9, False),
-                                              (500, 140, 37, False), (137, 131, 33, False)])
+                                              (500, 140, 37, False), (137, 131, 33, False),
+                                              # the orders at which the run goes from one pair of elements per thread to two and to four
+                                              (512, 3, 11, False), (513, 3, 7, False), (1025, 3, 11, False)])
 def test_whitened_mala_run_is_the_single_steps_in_a_row(d, C, steps, inject):
     """omc_mala_run_white (a block of steps per launch, one product per block into the store) against `steps` calls of
-    omc_mala_step_white on the same draws or streams: stored states, state left behind, counters and log densities bit for bit."""
+    omc_mala_step_white on the same draws or streams: stored states, state left behind, counters and log densities bit for bit.
+
+    The cases with d = 512, 513 and 1025 sit where the run's kernel changes its pairs of elements per thread.  Their step counts are the
+    smallest for which a chain rejects its first proposal (the test wants a chain that still holds the caller's x0): 11, 7 and 11,
+    found with the host model of the streams (tests/philox_model.py) and the step written out in NumPy."""
     import torch
 
     rng = np.random.default_rng(d + steps)
@@ -528,7 +534,10 @@ def test_whitened_mala_run_is_the_single_steps_in_a_row(d, C, steps, inject):
     x0 = mu + np.linalg.solve(np.linalg.cholesky(Qh).T, rng.standard_normal((d, C))).T  # a draw from the target
     zs = rng.standard_normal((steps, C, d)) if inject else None
     us = rng.random((steps, C)) if inject else None
-    eng = make_engine(C, seed=21)
+    # The uniform of a chain's first step is a function of (seed, chain, draw index) alone, and those of chains 0-2 of seed 21
+    # (0.450, 0.037, 0.461; chain 3: 0.997) accept from any state drawn from the target: with three chains and streamed draws the
+    # seed follows `steps`, as the NumPy inputs above do, so that a first rejection can be had by choosing `steps`.
+    eng = make_engine(C, seed=21 if C > 3 or inject else 21 + steps)
     L, sl = eng.dense_cholesky(eng.to_device(Qh), 1.0 / step**2)
     dmu = eng.to_device(mu)
     # the single steps
