@@ -100,6 +100,7 @@ omc_status omc_ctx_synchronize(omc_ctx* ctx);
  * restarting form is taken when the chains fill the CUs in whole rounds and the (sweep, chain) grid otherwise, an
  * explicit setting holds for every chain count),
  * "diag_algo" (0 auto; 1 the short-series form of omc_store_rhat_ess, M <= 64; 2 its blocks of lags),
+ * "hist_algo" (0 auto; 1 omc_store_histogram always finds the bin by bisection, also with evenly spaced edges: same counts),
  * "band_algo" (0 auto; 1 narrow bands one lane per chain in ONE piece; 2 one workgroup per chain, a column per step; 3 one
  * workgroup per chain in blocks of 16 columns, the next block factorised ahead, the window update on the matrix cores -- auto
  * takes it from w = 9, and from w = 4 on up to 3072 chains, where a lane per chain leaves the SIMDs to lone waves), "band_seg_overlap"
@@ -825,6 +826,38 @@ omc_status omc_store_cov(omc_ctx* ctx, int64_t n_iter,
                          int64_t size_a, const double* store_a, const int64_t* idx_a, int64_t n_a,
                          int64_t size_b, const double* store_b, const int64_t* idx_b, int64_t n_b,
                          int32_t pooled, int32_t correlation, double* out);
+/* Range of the same store per element, np.nanmin / np.nanmax of MCMC.store[param] (host arrays in the reference:
+ * mcmc.py:105-111), with the layout conventions of omc_store_cov: idx [n_idx] (device) the elements that take part, in that order,
+ * repeats allowed, NULL = all of them (n_idx must then equal size); an index outside [0, size) is OMC_INVALID_ARG, found on the
+ * device before any output is written.
+ *   pooled != 0: min_out / max_out / count_out [n_idx] over all n_iter C draws; pooled == 0: [C][n_idx], chain c over its own.
+ *   count_out (int64) = the non-NaN draws; an element without one gives NaN, NaN, 0; +-inf are ordinary values; any output may
+ *   be NULL.  One read of the selected columns; per-slice partials joined in a fixed order (workspace from the context).   */
+omc_status omc_store_minmax(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                            int32_t pooled, double* min_out, double* max_out, int64_t* count_out);
+/* Marginal histogram of every selected element of the same store: np.histogram(MCMC.store[param][i], bins=edges) of the
+ * reference's host arrays (mcmc.py:105-111) for all i at once; store, idx, n_idx, pooled as omc_store_minmax.
+ *   edges   (device) [n_bins + 1] shared by all elements, or [n_idx][n_bins + 1] when edges_per_element != 0; non-decreasing,
+ *           equal neighbours and +-inf allowed (as in numpy).  A NaN edge or a decreasing pair is OMC_INVALID_ARG, found on the
+ *           device before anything is counted: the outputs are then untouched.  1 <= n_bins <= 1024, else OMC_INVALID_ARG.
+ *   The bin rule is numpy's, comparisons with the edges alone: v falls in bin j when edges[j] <= v < edges[j + 1], the last bin
+ *   is closed (edges[n_bins - 1] <= v <= edges[n_bins]); with equal neighbours that is the last j with edges[j] <= v,
+ *   np.searchsorted(edges, v, 'right') - 1.  Evenly spaced edges get an arithmetic guess of the bin, put right by comparing with
+ *   the neighbouring edges (option "hist_algo" = 1: always the bisection; same counts).
+ *   counts_out  int64 [n_idx][n_bins] pooled, [C][n_idx][n_bins] per chain;
+ *   outside_out int64 [..][3] = draws below edges[0], draws above edges[n_bins], NaN draws; may be NULL.
+ *   Every row: sum(counts) + sum(outside) = the draws taken, n_iter C pooled, n_iter per chain.  Outputs are overwritten.
+ * One read of the selected columns: 32-bit counters in LDS per workgroup, added to the zeroed outputs with 64-bit integer
+ * atomics -- integer sums do not depend on the order: repeated calls and both forms are bit-equal.  n_iter C >= 2^32 (a
+ * workgroup's counters) is OMC_UNSUPPORTED.  Runs on the context's stream; the host reads two words back (the validation).  */
+omc_status omc_store_histogram(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                               int32_t pooled, int32_t n_bins, const double* edges, int32_t edges_per_element, int64_t* counts_out,
+                               int64_t* outside_out);
+/* [host, no GPU] The tiling and LDS image omc_store_histogram takes at n_bins (1..1024, else OMC_INVALID_ARG): out[10] = {TE
+ * (elements of a workgroup's tile), RB (rows of a slice), stride of an element's edges (doubles; 0 when shared), stride of an
+ * element's counters (words), byte offsets of the edges, the counters and the outside counts, end of the image = bytes launched,
+ * the budget the tile was chosen for, threads of a workgroup}.                                                           */
+omc_status omc_store_histogram_layout(int32_t n_bins, int32_t edges_per_element, int32_t* out);
 /* Thinned copy of the store for a thinned gather: out[j] = store[first + j * every] (slabs of C * size doubles),
  * j = 0 .. ceil((n_iter - first) / every) - 1 (that count is left in *n_out when n_out is not NULL, host).           */
 omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int64_t first, int64_t every,

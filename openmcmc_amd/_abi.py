@@ -155,6 +155,9 @@ SIGNATURES = {
     "omc_store_thin": (i32, [C.c_void_p, i64, i64, c_dp, i64, i64, c_dp, C.POINTER(i64)]),
     "omc_store_rhat_ess": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, c_dp, C.c_void_p]),
     "omc_store_cov": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i64, c_dp, c_dp, i64, i32, i32, c_dp]),
+    "omc_store_minmax": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i32, c_dp, c_dp, c_dp]),
+    "omc_store_histogram": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i32, i32, c_dp, i32, c_dp, c_dp]),
+    "omc_store_histogram_layout": (i32, [i32, i32, C.POINTER(i32)]),
     "omc_band_sample_canonical": (
         i32, [C.c_void_p, i64, i64, C.POINTER(BandTerms), c_dp, i64, c_dp, i64, u64, c_dp, i64, c_dp, i64, c_dp]),
     "omc_band_quadform": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, c_dp, i64, c_dp]),

@@ -31,7 +31,7 @@ struct omc_ctx {
   double* long_quad; size_t long_quad_bytes;  // ... and the sweep's quadratic forms [term][chain]
   double* workspace;       // scratch for the serial kernel (l vectors), grown on demand
   size_t workspace_bytes;
-  void* store_ws; size_t store_ws_bytes;  // omc_store.hip: histograms / partial moments of the store summaries
+  void* store_ws; size_t store_ws_bytes;  // omc_store.hip, omc_hist.hip: histograms / partial moments of the store summaries
   double* cov_ws; size_t cov_ws_bytes;  // omc_cov.hip: means, variances and partial tiles of omc_store_cov
   // dense path (omc_dense.hip): rocBLAS handle and workspaces, created on first use
   void* blas;
@@ -82,6 +82,7 @@ struct omc_ctx {
   int tridiag_generic;  // 1: never take the structure-specialised instantiation of the segmented kernel (tests)
   int band_algo;  // 0 auto, 1 lane-per-chain in one piece (narrow bands), 2 workgroup-per-chain
   int diag_algo;  // omc_store_rhat_ess: 0 auto, 1 short-series form (M <= 64), 2 blocks of lags
+  int hist_algo;  // omc_store_histogram: 0 auto (arithmetic guess of the bin when the edges are evenly spaced), 1 always the bisection
   int band_seg_overlap;  // segmented lane kernel: columns of warm-up before a segment (default 192)
   int band_seg_count;    // segmented lane kernel: number of segments (0 = chosen for the SIMDs; tuning and tests)
   int band_blocked_threads;  // blocked band kernel: 0 = form chosen by what fits a CU; 512, 4, 8, 16 force one (A/B, tests; band_blocked_choose)

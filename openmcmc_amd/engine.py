@@ -1241,6 +1241,62 @@ class Engine:
                                 int(bool(pooled)), int(bool(correlation)), self._p(out)))
         return out
 
+    @staticmethod
+    def hist_tile(n_bins, per_element=False):
+        """(TE, RB) of omc_store_histogram at n_bins: a workgroup counts a tile of TE consecutive selected elements over slices
+        of RB rows (openmcmc_amd/csrc/omc_hist_layout.h through omc_store_histogram_layout; needs no GPU)."""
+        return tuple(Engine.hist_layout(n_bins, per_element)[:2])
+
+    @staticmethod
+    def hist_layout(n_bins, per_element=False):
+        """The ten numbers of omc_store_histogram_layout: TE, RB, edge stride, counter stride, byte offsets of the edges, the
+        counters and the outside counts, bytes launched, the budget, threads of a workgroup."""
+        out = (C.c_int32 * 10)()
+        check(lib.omc_store_histogram_layout(int(n_bins), int(bool(per_element)), out))
+        return list(out)
+
+    def store_minmax(self, store, index=None, pooled=True):
+        """(min, max, count) of the non-NaN draws of every selected element of a device store (n_iter, C, size), on the device
+        (omc_store_minmax): np.nanmin, np.nanmax and the number of non-NaN draws, shape (n_idx,) pooled over chains and
+        iterations, else (C, n_idx); count is int64; an element without a non-NaN draw gives NaN, NaN, 0."""
+        torch = _torch()
+        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
+            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        n_iter, _, size = store.shape
+        idx, n = self._store_index(index, size)
+        shape = (n,) if pooled else (self.n_chains, n)
+        mn, mx = self.empty(*shape), self.empty(*shape)
+        cnt = torch.empty(shape, dtype=torch.int64, device=self.device)
+        check(lib.omc_store_minmax(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n,
+                                   int(bool(pooled)), self._p(mn), self._p(mx), cnt.data_ptr()))
+        return mn, mx, cnt
+
+    def store_histogram(self, store, edges, index=None, pooled=True):
+        """(counts, outside) of a device store (n_iter, C, size), on the device (omc_store_histogram): counts int64
+        (n_idx, n_bins) pooled, else (C, n_idx, n_bins) = np.histogram(draws of the element, bins=edges)[0]; outside int64
+        (.., 3) = draws below edges[0], above edges[-1], NaN.  edges: 1-D (n_bins + 1,) shared by all elements or 2-D
+        (n_idx, n_bins + 1) per element, a host array (uploaded synchronously) or a device tensor; non-decreasing, no NaN."""
+        torch = _torch()
+        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
+            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        n_iter, _, size = store.shape
+        idx, n = self._store_index(index, size)
+        if isinstance(edges, torch.Tensor):
+            e = edges.to(device=self.device, dtype=torch.float64).contiguous()
+        else:  # (torch.tensor copies from the numpy array before it returns: no asynchronous read of a temporary)
+            e = torch.tensor(np.ascontiguousarray(edges, dtype=np.float64), dtype=torch.float64, device=self.device)
+        if e.dim() not in (1, 2) or (e.dim() == 2 and e.shape[0] != n):
+            raise ValueError("edges must be (n_bins + 1,) or (number of selected elements, n_bins + 1)")
+        n_bins = e.shape[-1] - 1
+        if not 1 <= n_bins <= 1024:
+            raise ValueError("between 1 and 1024 bins")
+        lead = (n,) if pooled else (self.n_chains, n)
+        counts = torch.empty(lead + (n_bins,), dtype=torch.int64, device=self.device)
+        outside = torch.empty(lead + (3,), dtype=torch.int64, device=self.device)
+        check(lib.omc_store_histogram(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n,
+                                      int(bool(pooled)), n_bins, e.data_ptr(), int(e.dim() == 2), counts.data_ptr(), outside.data_ptr()))
+        return counts, outside
+
     def store_thin(self, store, every, first=0):
         """store[first::every] of a device store (n_iter, C, ...) as a packed device tensor (one launch)."""
         if store.dim() < 2 or store.shape[1] != self.n_chains or not store.is_contiguous():

@@ -421,6 +421,78 @@ class MCMC:
         and clipped to [-1, 1]; an element that never moved gives NaN in its row and column."""
         return self.covariance(key, other=other, index=index, other_index=other_index, pooled=pooled, correlation=True)
 
+    def histogram(self, key, bins=10, range=None, index=None, pooled=True, density=False):
+        """np.histogram of the stored draws of every selected element of store[key] at once, counted on the device (one read
+        of the store, no gather): (hist, edges) as host arrays.  hist is (n_idx, n_bins) pooled over chains and iterations,
+        else (C, n_idx, n_bins); int64 counts, or with density=True hist / (hist.sum() * np.diff(edges)) per row in fp64, divided
+        in np.histogram's order (by the widths, then by the sum), so that the densities are bit-equal to numpy's.
+        bins: an array of shared edges (n_bins + 1,) or of per-element edges (n_idx, n_bins + 1), which is returned as given;
+        or an int: with range=(lo, hi) the shared edges np.linspace(lo, hi, bins + 1), without a range every element gets
+        the edges numpy would give it, np.linspace over its own minimum and maximum (widened by 0.5 either way when they are
+        equal, (0, 1) for an element without a draw; an infinite draw raises ValueError as in numpy) -- edges (n_idx, bins + 1).
+        That range is the element's over ALL chains also with pooled=False, so that one element's chains share their edges.
+        NaN draws (the padding of variable-size parameters) are left out.  index selects elements (in that order, repeats
+        allowed); a 2-D entry ("log_post") counts as one element.  Under a sharded multi-GPU run these are the counts of this
+        rank's chains only; counts of several ranks over the same edges can simply be added."""
+        self._whole_store_on_device("histogram")
+        t = self._store_3d(key)
+        if np.ndim(bins) == 0:
+            n_bins = int(bins)
+            if n_bins != bins or not 1 <= n_bins <= 1024:
+                raise ValueError("bins must be an integer between 1 and 1024 or an array of edges")
+            if range is not None:
+                lo, hi = (float(v) for v in range)
+                if lo > hi:
+                    raise ValueError("max must be larger than min in range parameter.")  # np.histogram's own messages
+                if not (np.isfinite(lo) and np.isfinite(hi)):
+                    raise ValueError(f"supplied range of [{lo}, {hi}] is not finite")
+                if lo == hi:
+                    lo, hi = lo - 0.5, hi + 0.5
+                edges = np.linspace(lo, hi, n_bins + 1)
+            else:
+                mn, mx, cnt = (v.cpu().numpy() for v in self.engine.store_minmax(t, index=index, pooled=True))
+                lo, hi = np.where(cnt > 0, mn, 0.0), np.where(cnt > 0, mx, 1.0)
+                if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+                    raise ValueError("autodetected range is not finite")
+                same = lo == hi
+                lo, hi = np.where(same, lo - 0.5, lo), np.where(same, hi + 0.5, hi)
+                edges = np.stack([np.linspace(a, b, n_bins + 1) for a, b in zip(lo, hi)])
+        else:
+            edges = np.array(bins, dtype=np.float64)
+            if edges.ndim not in (1, 2) or edges.shape[-1] < 2:
+                raise ValueError("bins must be an integer, (n_bins + 1,) edges or (n_idx, n_bins + 1) edges")
+            if np.isnan(edges).any() or (np.diff(edges, axis=-1) < 0).any():
+                raise ValueError("`bins` must increase monotonically, when an array")
+        counts, _ = self.engine.store_histogram(t, edges, index=index, pooled=pooled)
+        hist = counts.cpu().numpy()
+        if density:
+            hist = hist / np.diff(edges, axis=-1) / hist.sum(axis=-1, keepdims=True)  # (np.histogram's order of operations)
+        return hist, edges
+
+    def exceedance(self, key, thresholds, index=None, pooled=True):
+        """P(x > t) of every selected element of store[key] for every threshold t, from one histogram pass on the device:
+        (n_t, n_idx) pooled over chains and iterations, else (n_t, C, n_idx).  The numerator counts the draws strictly greater
+        than t, the denominator the non-NaN draws; NaN where an element has none.  thresholds: a scalar or a sequence in any
+        order (at most 1024, no NaN).  Under a sharded multi-GPU run: this rank's chains only."""
+        self._whole_store_on_device("exceedance")
+        t = self._store_3d(key)
+        th = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        if th.ndim != 1 or not 1 <= th.size <= 1024 or np.isnan(th).any():
+            raise ValueError("thresholds must be a scalar or a sequence of at most 1024 values without NaN")
+        order = np.argsort(th, kind="stable")
+        # v >= nextafter(t, +inf) is exactly v > t: bin j holds the draws in (t_j, t_{j+1}], the last one those above the largest t
+        edges = np.concatenate([np.nextafter(th[order], np.inf), [np.inf]])
+        counts, outside = self.engine.store_histogram(t, edges, index=index, pooled=pooled)
+        counts, outside = counts.cpu().numpy(), outside.cpu().numpy()
+        above = np.cumsum(counts[..., ::-1], axis=-1)[..., ::-1]  # suffix sums: draws > t_j
+        above[..., np.isposinf(th[order])] = 0  # (the closed last bin holds the +inf draws: none of them exceeds +inf)
+        valid = counts.sum(axis=-1) + outside[..., 0] + outside[..., 1]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            p = np.where(valid[..., None] > 0, above / valid[..., None], np.nan)
+        out = np.empty_like(p)
+        out[..., order] = p
+        return np.moveaxis(out, -1, 0)
+
     def _thinned(self, every):
         """{key: device tensor (ceil(n_iter / every), C, ...)}: every `every`-th stored iteration, packed on the device"""
         self._whole_store_on_device("a thinned transfer")
