@@ -229,6 +229,10 @@ __device__ inline double omc_truncnorm_ppf(double u, double a, double b) {
   // of a scan whose sites sit many conditional standard deviations inside their limits (a smoother under a positivity
   // constraint), and it costs one rational approximation instead of ten transcendental evaluations.
   if (a < -13.0 && b > 13.0 && u > 1e-15 && u < 1.0 - 1e-15) return omc_ndtri_as241(u);
+  // u = 0 and u = 1 are the limits themselves.  The inversion below comes back within an ulp of a finite limit, but on
+  // either side of it, and the clamp only catches the outside: the quantile of 1 was 1 ulp short of b
+  if (u <= 0.0) return a;
+  if (u >= 1.0) return b;
   const double l1 = log1p(-u), l0 = log(u);
   // log Phi(x); the two tails satisfy exp(yp) + exp(yq) = 1, so "yp is the smaller one" is yp <= log(1/2) and the
   // upper tail is only worked out when it is the one to invert
