@@ -8,20 +8,36 @@
 struct Mob { double a, b, c, d; };  // 2x2 matrix [[a,b],[c,d]] acting as D -> (aD+b)/(cD+d)
 struct Aff { double p, q; };        // v -> p + q v
 
-__device__ __forceinline__ Mob mob_norm(Mob m) {
-  double mx = fmax(fmax(fabs(m.a), fabs(m.b)), fmax(fabs(m.c), fabs(m.d)));
-  int e = (mx > 0.0 && mx < INFINITY) ? ilogb(mx) : 0;
-  double s = ldexp(1.0, -e);  // exact power of two: the map is unchanged
-  return Mob{m.a * s, m.b * s, m.c * s, m.d * s};
-}
 // later-after-earlier composition.  The Moebius product is left unscaled: a product of k matrices whose
-// largest entries lie in [1, 2) has entries below 2^(2k-1), so the scans rescale (`renorm`, an exact power
-// of two: the map is unchanged) once per 16-lane row pass and per fold, not once per product.
+// largest entries lie in [1, 2) has entries below 2^(2k-1) -- below 2^(k (s + 1) - 1) for entries below 2^s --, so the
+// scans rescale (`renorm`, an exact power of two: the map is unchanged) once per 16-lane row pass, not once per product.
 __device__ __forceinline__ Mob compose(const Mob& L, const Mob& E) {
   return Mob{fma(L.a, E.a, L.b * E.c), fma(L.a, E.b, L.b * E.d), fma(L.c, E.a, L.d * E.c), fma(L.c, E.b, L.d * E.d)};
 }
 __device__ __forceinline__ Aff compose(const Aff& L, const Aff& E) { return Aff{fma(L.q, E.p, L.p), L.q * E.q}; }
-__device__ __forceinline__ Mob renorm(const Mob& m) { return mob_norm(m); }
+// The scans' rescaling: by the exponent of the LEADING entry alone (v_frexp_exp, a negation, four v_ldexp: 6 instructions in a
+// dependent chain of three, against 15 in a chain of eight for the maximum over four entries, ilogb and four multiplies it
+// replaces; the scan sits between two barriers, where every wave pays the chain's latency).  Any exact power of two serves:
+// it cancels in (a D + b)/(c D + d), and fma and multiply commute with it, so the choice changes no bit of a start value as
+// long as nothing leaves the normal range.
+// The guard is the instruction's own: v_frexp_exp_i32_f64 returns 0 for an input that is 0, infinite or NaN, so such a
+// matrix is left alone (ldexp by 0) -- the guard inside the local product (k_tridiag_seg) relies on the same.  A
+// compare and a select in front of it were measured: 0.36 us per sweep of the headline for four instructions (A/B in
+// profiles/r09_ab_headline.txt).
+// Why the leading entry will do.  For a stretch of a positive definite chain with pivots D (started from an infinite
+// incoming pivot) and D' (the same stretch without its first node), couplings b0 into it:
+//   a = prod D,  c = a / D_last,  b = -b0^2 prod D',  d = b / D'_last,
+// so every entry lies within 2^s of a, s = log2 of the largest of D, 1/D, b0^2/D, b0^2/(D D') over the chain (31 for a
+// precision scale of 1e9 against a unit identity term, 54 for 1e-8: there a ~ 1, b ~ 1e-16); a is positive and never the
+// small difference of large terms.  Rescaled: a in [1/2, 1), every entry below 2^s.
+// A product of two rescaled factors has the leading entry a_L a_E (1 - b^2/(D D')) with the pivots on either side of the
+// join: smaller than a_L a_E by up to 2^-sigma, sigma <= 53 (about log2 sqrt(lambda/tau) + 1 on the random-walk smoother:
+// 16 at 1e9) -- that factor per product is what underflowed unscaled products of wave totals at lambda >= 1e6.
+__device__ __forceinline__ Mob mob_rescale(const Mob& m) {
+  const int ex = -__builtin_amdgcn_frexp_exp(m.a);
+  return Mob{ldexp(m.a, ex), ldexp(m.b, ex), ldexp(m.c, ex), ldexp(m.d, ex)};
+}
+__device__ __forceinline__ Mob renorm(const Mob& m) { return mob_rescale(m); }
 __device__ __forceinline__ Aff renorm(const Aff& f) { return f; }
 
 __device__ __forceinline__ Mob shfl(const Mob& v, int d, int w, bool rev) {
@@ -143,7 +159,16 @@ __device__ __forceinline__ Mob read_lane(const Mob& v, int l) {
 __device__ __forceinline__ Aff read_lane(const Aff& v, int l) { return Aff{read_lane(v.p, l), read_lane(v.q, l)}; }
 
 // inclusive scan inside each row of 16 lanes, forward (REV = false) or from the high lane down
-template <class T, bool REV>
+// NORM: rescale the result (mob_rescale; the bounds in its terms s and sigma).  Inside the pass the fifteen products are left
+// unscaled either way: leading entry above 2^-(16 + 15 sigma), entries below 2^s of it.
+//   NORM = true, the row pass inside a wave: three more products follow inside the wave (two folds, the shift's exclusive
+//     prefix) and sixteen wave totals meet in wave 0 -- 2^-(64 sigma) per wave if nothing were rescaled on the way.  Rescaled
+//     here: a wave total's leading entry stays above 2^-(4 + 3 sigma).
+//   NORM = false, wave 0's pass over the (rescaled) wave totals.  ONE product with a wave's exclusive prefix (above
+//     2^-(4 + 3 sigma)), the product with the lane's own factor and the quotient that forms the start pivot follow: nothing
+//     below 2^-(22 + 20 sigma + 2 s) -- 2^-450 at sigma = 16, s = 54; the pass itself goes as low as 2^-(16 + 15 sigma) with
+//     or without a rescaling behind it -- and nothing above 2^(2 s + 1).  Left as it is.
+template <class T, bool REV, bool NORM = true>
 __device__ __forceinline__ T row_scan(T v, const T& id) {
   if (!REV) {
     v = compose(v, dpp_mov<DPP_ROW_SHR(1)>(v, id));
@@ -156,7 +181,7 @@ __device__ __forceinline__ T row_scan(T v, const T& id) {
     v = compose(v, dpp_mov<DPP_ROW_SHL(4)>(v, id));
     v = compose(v, dpp_mov<DPP_ROW_SHL(8)>(v, id));
   }
-  return renorm(v);
+  return NORM ? renorm(v) : v;
 }
 
 // Workgroup barrier that orders LDS traffic only.  `__syncthreads()` is a fence as well: it waits for every
@@ -198,10 +223,11 @@ __device__ __forceinline__ T excl_scan_wg(T v, const T id, T* lds, int lane, int
       if (w == 0) {
         // The wave totals arrive unscaled from two folds; products of Moebius matrices of a precision of magnitude
         // lambda shrink by ~1/lambda per factor, so sixteen of them in a row underflowed for lambda >= 1e6 on chains of
-        // twelve and more waves (0/0 start values).  Rescaled here, the row pass sees factors in [1, 2) like the one
-        // inside a wave.
+        // twelve and more waves (0/0 start values).  Rescaled here, the row pass sees leading entries in [1/2, 1) like the
+        // one inside a wave (a wave total is a product of four rescaled rows: leading entry above 2^-(4 + 3 sigma)); its own
+        // result needs no rescaling any more (row_scan, NORM = false).
         T t = (lane < nw) ? renorm(lds[lane]) : id;
-        t = row_scan<T, REV>(t, id);
+        t = row_scan<T, REV, false>(t, id);
         if (lane < nw) lds2[lane] = t;
       }
       lds_barrier();

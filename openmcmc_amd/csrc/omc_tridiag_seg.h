@@ -553,7 +553,9 @@ __global__ void __launch_bounds__(MAXT) k_tridiag_seg(TriArgs A, int G) {
         m = Mob{ldexp(m.a, ex), ldexp(m.b, ex), ldexp(m.c, ex), ldexp(m.d, ex)};
       }
     }
-    m = mob_norm(m);
+    // (up to 7 steps since the guard above: entries as large as |a|^7, and sixteen such factors meet in the row pass.
+    // Rescaled, the row pass sees leading entries in [1/2, 1) and entries below 2^s: see mob_rescale)
+    m = mob_rescale(m);
     OMC_STAMP(4);
     const Mob idm{1.0, 0.0, 0.0, 1.0};
     const Mob E = MULTI ? excl_scan_wg<Mob, false, true>(m, idm, lds_mob, lane, wave, nw, lds_mob2)
