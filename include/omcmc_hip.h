@@ -101,6 +101,8 @@ omc_status omc_ctx_synchronize(omc_ctx* ctx);
  * explicit setting holds for every chain count),
  * "diag_algo" (0 auto; 1 the short-series form of omc_store_rhat_ess, M <= 64; 2 its blocks of lags),
  * "hist_algo" (0 auto; 1 omc_store_histogram always finds the bin by bisection, also with evenly spaced edges: same counts),
+ * "rank_tile" (0 = 8192, or a power of two 64 .. 8192: keys of an LDS tile of the sort behind omc_store_ranks; same results bit for
+ * bit), "rank_chunk" (0 auto, else the elements omc_store_ranks / omc_store_rank_diagnostics work on at a time),
  * "band_algo" (0 auto; 1 narrow bands one lane per chain in ONE piece; 2 one workgroup per chain, a column per step; 3 one
  * workgroup per chain in blocks of 16 columns, the next block factorised ahead, the window update on the matrix cores -- auto
  * takes it from w = 9, and from w = 4 on up to 3072 chains, where a lane per chain leaves the SIMDs to lone waves), "band_seg_overlap"
@@ -858,6 +860,53 @@ omc_status omc_store_histogram(omc_ctx* ctx, int64_t n_iter, int64_t size, const
  * element's counters (words), byte offsets of the edges, the counters and the outside counts, end of the image = bytes launched,
  * the budget the tile was chosen for, threads of a workgroup}.                                                           */
 omc_status omc_store_histogram_layout(int32_t n_bins, int32_t edges_per_element, int32_t* out);
+/* Ranks of the draws of every selected element of the same store; store, idx, n_idx, the NULL convention and the out-of-range rule
+ * as omc_store_minmax (an index outside [0, size) is OMC_INVALID_ARG, found on the device before any output is written).
+ * With N = n_iter >= 4: M = N / 2, J = 2 C, S = J M; the SPLIT DRAWS of an element are the first M and the last M iterations of
+ * every chain (the middle row of an odd N is dropped, as omc_store_rhat_ess drops it).
+ *   rank_out [N][C][n_idx] fp64: the 1-based average rank of the draw x among the element's draws y,
+ *            r = #{y < x} + (#{y == x} + 1) / 2 -- scipy.stats.rankdata(method="average"), bit for bit (integers and halves);
+ *   split != 0: among the S split draws, the dropped middle row is written as NaN, N >= 4 (else OMC_INVALID_ARG);
+ *   split == 0: among all N C draws, N >= 1.
+ *   -0.0 and +0.0 are equal; +-inf are ordinary values; an element with any NaN draw (the dropped row included) gets NaN in its
+ *   whole column and affects nothing else.
+ * A chunk of elements at a time: their draws are gathered as order-preserving 64-bit keys into columns padded to the next power of
+ * two P >= S, every column is sorted by a key-only bitonic network (data-independent addressing; strides inside a tile of T keys
+ * in LDS, larger strides one pass over global memory each: omc_store_rank_schedule), and every draw finds the keys below and equal
+ * to its own by bisection.  Options "rank_tile" (T) and "rank_chunk" (elements per chunk; by default what fits a workspace of
+ * 1 GiB at 8 P bytes per element, at least one): same results bit for bit.  Workspace from the context (its own, not the one of
+ * the other store summaries).  With d = log2(P / T) the sort is d + 1 launches over tiles and d (d + 1) / 2 global passes of 16
+ * bytes per key: meant for the elements one inspects, not for every element of a long store.                              */
+omc_status omc_store_ranks(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                           int32_t split, double* rank_out);
+/* Rank-normalised convergence diagnostics of the same store (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; what Stan and
+ * ArviZ report by default), per selected element; store, idx, n_idx as omc_store_ranks, N = n_iter >= 4 (else OMC_INVALID_ARG).
+ * E(.) and R(.) are the ess and the rhat omc_store_rhat_ess defines for an [N][C] series; all of its edge rules carry over.
+ *   z        = ndtri((r - 3/8) / (S + 1/4)), r the split rank of the draw (the dropped middle row is 0: it is never read);
+ *   ess_bulk = E(z);
+ *   f = |x - med|, med = np.median of the split draws ((a + b) / 2 of the two middle order statistics), zf = f rank-normalised
+ *            the same way;  rhat = max(R(z), R(zf)), NaN when either is NaN;
+ *   q_p      = np.quantile of the split draws, default "linear" method, p = 0.05 and 0.95 (the two order statistics read from the
+ *            sorted column, numpy's interpolation operation by operation as in omc_store_quantiles: bit-equal);
+ *            I_p = (x <= q_p) ? 1 : 0;  ess_tail = min(E(I_05), E(I_95)).
+ *   An element with any non-finite draw (NaN or +-inf, any chain, any iteration) gives NaN in all three outputs and affects nothing
+ *   else.  A constant element gives rhat = NaN and ess = S (the rules of omc_store_rhat_ess on constant series).
+ *   rhat_out, ess_bulk_out, ess_tail_out [n_idx]; any of them may be NULL.
+ * Per chunk of elements: the sort of omc_store_ranks twice (the draws, the folded draws), the four series z, zf, I_05, I_95 side
+ * by side as a store [N][C][4 Kc], and one call of omc_store_rhat_ess over them (options "diag_algo" applies).  The chunk is what
+ * fits 1 GiB at 8 P + 32 N C bytes per element ("rank_chunk" forces it: same results to rounding, the grouping of the lag sums
+ * depends on the size).  Deterministic: repeated calls are bit-equal.                                                       */
+omc_status omc_store_rank_diagnostics(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx,
+                                      int64_t n_idx, double* rhat_out, double* ess_bulk_out, double* ess_tail_out);
+/* [host, no GPU] The launches that sort columns of S keys with tiles of `tile` keys (0 = 8192, or a power of two 64 .. 8192, else
+ * OMC_INVALID_ARG; S >= 1): P = the next power of two >= S, T = min(tile, P); out [cap][3] = (kind, k, j) per launch, *n_out their
+ * number (set also when cap is too small, which is OMC_INVALID_ARG).  A compare-exchange at stride j of stage k orders the keys at
+ * positions i and i + j (bit j of i clear) ascending where bit k of i is clear, descending otherwise.
+ *   kind 0: every tile, all stages k' = 2, 4 .. k (= T), each with its strides k' / 2 .. 1 (j = T / 2 is given for information);
+ *   kind 1: one stride j >= T of stage k over global memory;
+ *   kind 2: every tile, the strides j (= T / 2), j / 2 .. 1 of stage k.
+ * P = 1 needs no launch; otherwise 1 + d launches of kinds 0 and 2 and d (d + 1) / 2 of kind 1, d = log2(P / T).            */
+omc_status omc_store_rank_schedule(int64_t S, int32_t tile, int64_t* out, int64_t cap, int64_t* n_out);
 /* Thinned copy of the store for a thinned gather: out[j] = store[first + j * every] (slabs of C * size doubles),
  * j = 0 .. ceil((n_iter - first) / every) - 1 (that count is left in *n_out when n_out is not NULL, host).           */
 omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int64_t first, int64_t every,

@@ -33,6 +33,7 @@ struct omc_ctx {
   size_t workspace_bytes;
   void* store_ws; size_t store_ws_bytes;  // omc_store.hip, omc_hist.hip: histograms / partial moments of the store summaries
   double* cov_ws; size_t cov_ws_bytes;  // omc_cov.hip: means, variances and partial tiles of omc_store_cov
+  void* rank_ws; size_t rank_ws_bytes;  // omc_rank.hip: keys, series and per-element words of a chunk (its own: it calls omc_store_rhat_ess, which uses store_ws)
   // dense path (omc_dense.hip): rocBLAS handle and workspaces, created on first use
   void* blas;
   // blocked dense factorisation: second half of the chains on a side stream (forked from / joined into `stream` by events),
@@ -83,6 +84,8 @@ struct omc_ctx {
   int band_algo;  // 0 auto, 1 lane-per-chain in one piece (narrow bands), 2 workgroup-per-chain
   int diag_algo;  // omc_store_rhat_ess: 0 auto, 1 short-series form (M <= 64), 2 blocks of lags
   int hist_algo;  // omc_store_histogram: 0 auto (arithmetic guess of the bin when the edges are evenly spaced), 1 always the bisection
+  int rank_tile;  // omc_rank.hip: keys of an LDS tile of the sort, a power of two 64 .. 8192 (0: 8192)
+  int64_t rank_chunk;  // omc_rank.hip: elements per chunk (0: what fits the workspace budget)
   int band_seg_overlap;  // segmented lane kernel: columns of warm-up before a segment (default 192)
   int band_seg_count;    // segmented lane kernel: number of segments (0 = chosen for the SIMDs; tuning and tests)
   int band_blocked_threads;  // blocked band kernel: 0 = form chosen by what fits a CU; 512, 4, 8, 16 force one (A/B, tests; band_blocked_choose)

@@ -41,6 +41,7 @@ omc_status omc_ctx_create(int32_t device, int64_t n_chains, uint64_t seed, int64
   c->blas = nullptr;
   c->store_ws = nullptr; c->store_ws_bytes = 0;
   c->cov_ws = nullptr; c->cov_ws_bytes = 0;
+  c->rank_ws = nullptr; c->rank_ws_bytes = 0;
   c->dense_factor = nullptr; c->dense_factor_bytes = 0;
   c->dense_winv = nullptr; c->dense_winv_bytes = 0; c->dense_panel_old = 0;
   c->dense_info = nullptr; c->dense_info_bytes = 0;
@@ -70,6 +71,7 @@ omc_status omc_ctx_create(int32_t device, int64_t n_chains, uint64_t seed, int64
   c->mh_gemm_ksplit = 4;
   c->diag_algo = 0;
   c->hist_algo = 0;
+  c->rank_tile = 0; c->rank_chunk = 0;
   c->band_algo = 0; c->band_seg_overlap = 192; c->band_seg_count = 0; c->band_blocked_threads = 0;
   if (c->own_stream) {
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -97,6 +99,7 @@ omc_status omc_ctx_destroy(omc_ctx* ctx) {
   if (ctx->workspace) hipFree(ctx->workspace);
   if (ctx->store_ws) hipFree(ctx->store_ws);
   if (ctx->cov_ws) hipFree(ctx->cov_ws);
+  if (ctx->rank_ws) hipFree(ctx->rank_ws);
   if (ctx->long_band) hipFree(ctx->long_band);
   if (ctx->long_quad) hipFree(ctx->long_quad);
   if (ctx->d_gamma_tab) hipFree(ctx->d_gamma_tab);
@@ -273,6 +276,16 @@ omc_status omc_ctx_set_option(omc_ctx* ctx, const char* name, int64_t value) {
   if (!strcmp(name, "hist_algo")) {
     if (value < 0 || value > 1) return OMC_INVALID_ARG;
     ctx->hist_algo = (int)value;
+    return OMC_OK;
+  }
+  if (!strcmp(name, "rank_tile")) {
+    if (value != 0 && (value < 64 || value > 8192 || (value & (value - 1)))) return OMC_INVALID_ARG;
+    ctx->rank_tile = (int)value;
+    return OMC_OK;
+  }
+  if (!strcmp(name, "rank_chunk")) {
+    if (value < 0) return OMC_INVALID_ARG;
+    ctx->rank_chunk = value;
     return OMC_OK;
   }
   if (!strcmp(name, "band_seg_overlap")) {

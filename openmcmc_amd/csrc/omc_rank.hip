@@ -1,0 +1,455 @@
+// Ranks of the device-resident store and the rank-normalised diagnostics built on them (Vehtari, Gelman, Simpson, Carpenter,
+// Buerkner 2021): rank-normalised split R-hat (bulk and folded), bulk-ESS and tail-ESS, without moving the store off the GPU.
+// The contract is in include/omcmc_hip.h (omc_store_ranks, omc_store_rank_diagnostics, omc_store_rank_schedule).
+//
+// store is [N][C][size].  A chunk of Kc selected elements is worked on at a time:
+//   k_rank_gather  reads the draws of the chunk where they lie (16 adjacent elements of a row per 128 bytes), turns them into
+//                  order-preserving 64-bit keys (-0.0 first made +0.0) and writes them, transposed through LDS, into columns
+//                  keys [Kc][P], P the next power of two >= the S draws of a column, the rest of a column the all-ones key;
+//                  it notes per element whether a NaN (bit 0) or an infinity (bit 1) was seen.  With `fold` the value is
+//                  |x - med|, med the element's median from k_rank_stats.
+//   k_rank_sort_tile / k_rank_sort_global
+//                  a bitonic network over every column, keys only.  Its addressing depends on P and the tile T alone, never on
+//                  the data.  Stage k (k = 2, 4, .. P) compare-exchanges at strides j = k / 2 .. 1, ascending where the
+//                  position within the column has bit k clear.  Strides inside a tile of T keys run in LDS, one workgroup per
+//                  tile: the first launch sorts every tile (all stages up to T), and each later stage ends in one launch that
+//                  does its strides T / 2 .. 1; strides of 64 and more go through LDS with a barrier per stride, the last six
+//                  (32 .. 1) stay inside a wave, a key per lane exchanged by __shfl_xor.  Every stride >= T is one pass over
+//                  global memory.  rank_schedule() lists the launches; the entry points walk that list and
+//                  omc_store_rank_schedule hands it to the tests, which replay it in numpy.
+//   k_rank_emit    for every draw the number of smaller and of equal keys by bisection in its sorted column (ties are exact, no
+//                  payload is carried through the sort; the second bisection only where the next key is equal): the average rank, or z = ndtri((r - 3/8) / (S + 1/4)), and with the
+//                  same read of the store the tail indicators x <= q05, x <= q95.
+//   k_rank_stats   median and the two tail quantiles from the sorted column, numpy's interpolation (omc_quantile.h).
+// The four series of a chunk -- z, z of the folded draws, the two indicators -- lie side by side as one store [N][C][4 Kc], and
+// ONE call of omc_store_rhat_ess runs over them (it uses ctx->store_ws; everything here lives in ctx->rank_ws).
+//
+// Kc: the workspace of a chunk is Kc (8 P + 32 N C + 100) bytes -- keys, the four series, per-element words -- and Kc is what fits
+// RANK_BUDGET = 1 GiB (a choice, not a measurement: large enough for a few hundred elements of a store with a million pooled
+// draws, small beside the store), at least 1; option "rank_chunk" forces it.
+#include <math.h>
+
+#include <vector>
+
+#include "omc_common.h"
+#include "omc_quantile.h"
+#include "omc_truncnorm.h"
+
+namespace {
+
+constexpr size_t RANK_BUDGET = (size_t)1 << 30;
+constexpr int64_t RANK_KC_MAX = (int64_t)1 << 17;  // elements of a chunk at most (grid.y of k_rank_emit: Kc / 4)
+constexpr int RANK_TILE_DEFAULT = 8192;            // keys of an LDS tile: 64 KiB
+constexpr int G_TE = 16, G_TS = 64;                // k_rank_gather: elements x draws of a workgroup's tile
+
+struct RankLaunch { int64_t kind, k, j; };  // kind 0: sort every tile (stages 2 .. k); 1: global pass (k, j); 2: tile strides j .. 1 of stage k
+
+int64_t rank_pow2(int64_t S) {
+  int64_t P = 1;
+  while (P < S) P <<= 1;
+  return P;
+}
+
+// the launches that sort columns of P keys with tiles of T (both powers of two)
+std::vector<RankLaunch> rank_schedule(int64_t P, int64_t T) {
+  std::vector<RankLaunch> L;
+  if (P < 2) return L;
+  if (T > P) T = P;
+  L.push_back({0, T, T / 2});
+  for (int64_t k = 2 * T; k <= P; k <<= 1) {
+    for (int64_t j = k / 2; j >= T; j >>= 1) L.push_back({1, k, j});
+    L.push_back({2, k, T / 2});
+  }
+  return L;
+}
+
+__device__ __forceinline__ uint64_t rank_key(double v) {
+  if (v == 0.0) v = 0.0;  // -0.0 and +0.0 are one value
+  return q_key(v);
+}
+
+// words[0] = 1: an index outside [0, size)
+__global__ void k_rank_check(const int64_t* __restrict__ idx, int64_t n_idx, int64_t size, int32_t* __restrict__ words) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n_idx && (idx[t] < 0 || idx[t] >= size)) words[0] = 1;
+}
+
+// Draw s of a column (s < S) is row s of the store seen as [N C][size] when s < first, else row s + skip: the two halves of a
+// split store, with the middle row of an odd N (rows [mid_row0, mid_row0 + C), mid_row0 < 0: none) read for its NaN / inf only.
+__global__ void __launch_bounds__(256) k_rank_gather(const double* __restrict__ store, const int64_t* __restrict__ idx, int64_t k0, int64_t Kc,
+                                                     int64_t size, int64_t C, int64_t S, int64_t P, int64_t first, int64_t skip,
+                                                     int64_t mid_row0, const double* __restrict__ stats, uint64_t* __restrict__ keys,
+                                                     int32_t* __restrict__ flags) {
+  __shared__ uint64_t tile[G_TE][G_TS + 1];
+  const int tid = threadIdx.x, e_l = tid & (G_TE - 1), d_l = tid / G_TE;
+  const int64_t e0 = (int64_t)blockIdx.y * G_TE, s0 = (int64_t)blockIdx.x * G_TS;
+  const int64_t e = e0 + e_l;
+  const bool live = e < Kc;
+  const int64_t col = live ? (idx ? idx[k0 + e] : k0 + e) : 0;
+  const bool fold = stats != nullptr;
+  const double med = (fold && live) ? stats[3 * e] : 0.0;
+  const double inf = __longlong_as_double(0x7ff0000000000000LL);
+  int32_t bits = 0;
+  double v[G_TS / (256 / G_TE)];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int64_t s = s0 + d_l + 16 * u;
+    v[u] = (live && s < S) ? store[(s < first ? s : s + skip) * size + col] : 0.0;
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int64_t s = s0 + d_l + 16 * u;
+    uint64_t key = ~0ull;
+    if (live && s < S) {
+      const double x = fold ? fabs(v[u] - med) : v[u];
+      if (x != x) bits |= 1;
+      else if (fabs(x) == inf) bits |= 2;
+      key = rank_key(x);
+    }
+    tile[e_l][d_l + 16 * u] = key;
+  }
+  if (mid_row0 >= 0 && blockIdx.x == 0 && live)
+    for (int64_t c = d_l; c < C; c += 256 / G_TE) {
+      const double x = store[(mid_row0 + c) * size + col];
+      if (x != x) bits |= 1;
+      else if (fabs(x) == inf) bits |= 2;
+    }
+  if (flags && bits) atomicOr(&flags[e], bits);
+  __syncthreads();
+  const int s_l = tid & (G_TS - 1);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int el = (tid >> 6) + 4 * u;
+    if (e0 + el < Kc && s0 + s_l < P) keys[(e0 + el) * P + s0 + s_l] = tile[el][s_l];
+  }
+}
+
+// compare-exchange at stride j <= 32 of stage k inside a wave: lane l holds the key at position pos (pos & 63 == l)
+__device__ __forceinline__ uint64_t rank_wave_step(uint64_t v, int64_t pos, int j, int64_t k) {
+  const uint64_t o = __shfl_xor((unsigned long long)v, j, 64);
+  const bool up = (pos & k) == 0, low = (pos & j) == 0;
+  const uint64_t mn = v < o ? v : o, mx = v < o ? o : v;
+  return low == up ? mn : mx;
+}
+
+// strides jtop .. 1 of stage k on the tile in LDS; c0 = the tile's first position within its column
+__device__ __forceinline__ void rank_tile_stage(uint64_t* __restrict__ t, int T, int64_t c0, int64_t k, int jtop) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int j = jtop; j >= 64; j >>= 1) {
+    for (int p = tid; p < T / 2; p += nt) {
+      const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), i2 = i | j;
+      const uint64_t a = t[i], b = t[i2];
+      if ((a > b) == (((c0 + i) & k) == 0)) { t[i] = b; t[i2] = a; }
+    }
+    __syncthreads();
+  }
+  const int Tr = T < 64 ? 64 : T;
+  for (int base = tid; base < Tr; base += nt) {  // (T < 64 or a multiple of 64, nt a multiple of 64: whole waves take a step)
+    uint64_t v = base < T ? t[base] : ~0ull;
+    for (int j = jtop < 32 ? jtop : 32; j >= 1; j >>= 1) v = rank_wave_step(v, c0 + base, j, k);
+    if (base < T) t[base] = v;
+  }
+  __syncthreads();
+}
+
+// One workgroup per tile of T keys (T <= P, both powers of two; tiles of all columns lie one behind the other).
+// whole != 0: stages 2 .. T (the tile comes out sorted, ascending where its position has bit T clear -- bit P is never set);
+// whole == 0: strides T / 2 .. 1 of stage k.
+__global__ void __launch_bounds__(1024) k_rank_sort_tile(uint64_t* __restrict__ keys, int T, int64_t P, int64_t k, int whole) {
+  extern __shared__ uint64_t rank_lds[];
+  uint64_t* g = keys + (int64_t)blockIdx.x * T;
+  const int64_t c0 = ((int64_t)blockIdx.x * T) & (P - 1);
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int i = tid; i < T; i += nt) rank_lds[i] = g[i];
+  __syncthreads();
+  if (whole) {
+    // stages up to 64 never leave the wave
+    const int Tr = T < 64 ? 64 : T, kw = T < 64 ? T : 64;
+    for (int base = tid; base < Tr; base += nt) {
+      uint64_t v = base < T ? rank_lds[base] : ~0ull;
+      for (int kk = 2; kk <= kw; kk <<= 1)
+        for (int j = kk >> 1; j >= 1; j >>= 1) v = rank_wave_step(v, c0 + base, j, kk);
+      if (base < T) rank_lds[base] = v;
+    }
+    __syncthreads();
+    for (int kk = 128; kk <= T; kk <<= 1) rank_tile_stage(rank_lds, T, c0, kk, kk >> 1);
+  } else {
+    rank_tile_stage(rank_lds, T, c0, k, T >> 1);
+  }
+  for (int i = tid; i < T; i += nt) g[i] = rank_lds[i];
+}
+
+// stride j >= T of stage k over all columns: one thread per pair, n_pairs = Kc P / 2
+__global__ void __launch_bounds__(256) k_rank_sort_global(uint64_t* __restrict__ keys, int64_t n_pairs, int64_t P, int64_t k, int64_t j) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n_pairs) return;
+  const int64_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), i2 = i | j;  // j < P: both in the same column, i2 < 2 n_pairs
+  const uint64_t a = keys[i], b = keys[i2];
+  if ((a > b) == (((i & (P - 1)) & k) == 0)) { keys[i] = b; keys[i2] = a; }
+}
+
+// stats [Kc][3] = median ((a + b) / 2 of the two middle order statistics: S is even), q05, q95 of the S sorted draws
+__global__ void k_rank_stats(int64_t Kc, int64_t S, int64_t P, const uint64_t* __restrict__ keys, double* __restrict__ stats) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= Kc) return;
+  const uint64_t* col = keys + e * P;
+  stats[3 * e] = (q_val(col[S / 2 - 1]) + q_val(col[S / 2])) / 2.0;
+  for (int t = 0; t < 2; ++t) {
+    int64_t lo, hi;
+    double fr;
+    q_ranks(S, t ? 0.95 : 0.05, lo, hi, fr);
+    stats[3 * e + 1 + t] = q_lerp(q_val(col[lo]), q_val(col[hi]), fr);
+  }
+}
+
+// keys of a sorted column (P of them, a power of two) that are < key (upper == false) or <= key (upper == true): every read is at
+// an index below P whatever the keys hold
+__device__ __forceinline__ int64_t rank_bound(const uint64_t* __restrict__ col, int64_t P, uint64_t key, bool upper) {
+  int64_t lo = 0;
+  for (int64_t step = P >> 1; step >= 1; step >>= 1) {
+    const uint64_t c = col[lo + step - 1];
+    if (upper ? c <= key : c < key) lo += step;
+  }
+  const uint64_t c = col[lo];
+  return lo + ((upper ? c <= key : c < key) ? 1 : 0);
+}
+
+enum { RANK_EMIT_RANKS = 0, RANK_EMIT_Z = 1, RANK_EMIT_ZFOLD = 2 };
+struct RankEmit {
+  const double* store; const int64_t* idx; const uint64_t* keys; const int32_t* flags; const double* stats; double* out;
+  int64_t k0, Kc, size, C, S, P, n_rows, mid_row0, ld_out;
+  int mode;
+};
+
+// One thread per (row of the store, element of the chunk): a wave takes 64 consecutive rows of ONE element, the four waves of a
+// workgroup four adjacent elements over the same rows, and the workgroups walk the rows first.  What is in flight at a time then
+// bisects in a handful of columns, which stay in L2; with the elements on consecutive lanes instead, every lane of a load looked into
+// another column and the lower levels of every bisection missed L2, a 128-byte line for 8 bytes (6.1 ms per launch for 204
+// columns of 131 072 keys, against 2.1 ms for sorting them).  The four waves read neighbouring 8-byte pieces of the same lines of the
+// store and write neighbouring pieces of the output rows.
+//   RANKS: out[row ld_out + k0 + e] = average rank, NaN in the middle row and for an element with a NaN draw;
+//   Z:     out = series [n_rows][4 Kc]: z at e, the indicators x <= q05 at 2 Kc + e and x <= q95 at 3 Kc + e;
+//   ZFOLD: z of |x - med| at Kc + e.  (Z, ZFOLD: zeros in the middle row and for an element with a non-finite draw.)
+__global__ void __launch_bounds__(256) k_rank_emit(RankEmit a) {
+  const int64_t row = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63), e = (int64_t)blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= a.n_rows || e >= a.Kc) return;
+  const bool mid = a.mid_row0 >= 0 && row >= a.mid_row0 && row < a.mid_row0 + a.C;
+  const int32_t fl = a.flags[e];
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const bool dead = mid || (a.mode == RANK_EMIT_RANKS ? (fl & 1) != 0 : fl != 0);
+  double r = 0.0, x = 0.0;
+  if (!dead) {
+    x = a.store[row * a.size + (a.idx ? a.idx[a.k0 + e] : a.k0 + e)];
+    const double v = a.mode == RANK_EMIT_ZFOLD ? fabs(x - a.stats[3 * e]) : x;
+    const uint64_t key = rank_key(v);
+    const uint64_t* col = a.keys + e * a.P;
+    // the draw is in its column, so col[less] == key; where the next key is already larger -- nearly always with continuous draws --
+    // the second bisection is not needed
+    const int64_t less = rank_bound(col, a.P, key, false);
+    const int64_t le = (less + 1 >= a.P || col[less + 1] > key) ? less + 1 : rank_bound(col, a.P, key, true);
+    r = (double)less + 0.5 * (double)(le - less + 1);
+  }
+  if (a.mode == RANK_EMIT_RANKS) {
+    a.out[row * a.ld_out + a.k0 + e] = dead ? nan : r;
+    return;
+  }
+  const double z = dead ? 0.0 : omc_ndtri_as241((r - 0.375) / ((double)a.S + 0.25));
+  double* o = a.out + row * 4 * a.Kc + e;
+  if (a.mode == RANK_EMIT_ZFOLD) {
+    o[a.Kc] = z;
+  } else {
+    o[0] = z;
+    o[2 * a.Kc] = (!dead && x <= a.stats[3 * e + 1]) ? 1.0 : 0.0;
+    o[3 * a.Kc] = (!dead && x <= a.stats[3 * e + 2]) ? 1.0 : 0.0;
+  }
+}
+
+// rh4, es4 [4 Kc]: omc_store_rhat_ess of the four series
+__global__ void k_rank_combine(int64_t Kc, int64_t k0, const int32_t* __restrict__ flags, const double* __restrict__ rh4,
+                               const double* __restrict__ es4, double* __restrict__ rhat_out, double* __restrict__ bulk_out,
+                               double* __restrict__ tail_out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= Kc) return;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const bool bad = flags[e] != 0;
+  const double ra = rh4[e], rb = rh4[Kc + e], ta = es4[2 * Kc + e], tb = es4[3 * Kc + e];
+  if (rhat_out) rhat_out[k0 + e] = (bad || ra != ra || rb != rb) ? nan : (ra > rb ? ra : rb);
+  if (bulk_out) bulk_out[k0 + e] = bad ? nan : es4[e];
+  if (tail_out) tail_out[k0 + e] = (bad || ta != ta || tb != tb) ? nan : (ta < tb ? ta : tb);
+}
+
+dim3 rank_emit_grid(const RankEmit& a) { return dim3((unsigned)((a.n_rows + 63) / 64), (unsigned)((a.Kc + 3) / 4)); }
+
+int64_t rank_tile_of(const omc_ctx* ctx, int64_t P) {
+  const int64_t T = ctx->rank_tile ? ctx->rank_tile : RANK_TILE_DEFAULT;
+  return T < P ? T : P;
+}
+
+// sorts the Kc columns of P keys
+omc_status rank_sort(omc_ctx* ctx, uint64_t* keys, int64_t Kc, int64_t P) {
+  const int64_t T = rank_tile_of(ctx, P);
+  const int64_t blocks = Kc * P / T, n_pairs = Kc * P / 2;
+  if (blocks > 0x7fffffffLL || (n_pairs + 255) / 256 > 0x7fffffffLL) return OMC_INVALID_ARG;
+  const size_t lds = (size_t)T * sizeof(uint64_t);
+  static bool lds_raised[64];  // per device: the tile kernel may take more than the default 48 KiB of dynamic LDS (asked for once)
+  if (lds > 48 * 1024 && !(ctx->device >= 0 && ctx->device < 64 && lds_raised[ctx->device])) {
+    OMC_HIP_CHECK(hipFuncSetAttribute((const void*)k_rank_sort_tile, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      RANK_TILE_DEFAULT * (int)sizeof(uint64_t)));
+    if (ctx->device >= 0 && ctx->device < 64) lds_raised[ctx->device] = true;
+  }
+  int64_t nt = T / 8;  // eight keys per thread, whole waves
+  if (nt < 64) nt = 64;
+  if (nt > 1024) nt = 1024;
+  for (const RankLaunch& l : rank_schedule(P, T)) {
+    if (l.kind == 1)
+      hipLaunchKernelGGL(k_rank_sort_global, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, ctx->stream, keys, n_pairs, P, l.k, l.j);
+    else
+      hipLaunchKernelGGL(k_rank_sort_tile, dim3((unsigned)blocks), dim3((unsigned)nt), lds, ctx->stream, keys, (int)T, P, l.k,
+                         (int)(l.kind == 0));
+  }
+  OMC_HIP_CHECK(hipGetLastError());
+  return OMC_OK;
+}
+
+// the layout of a column's draws (k_rank_gather)
+struct RankGeom { int64_t S, P, first, skip, mid_row0; };
+RankGeom rank_geom(int64_t N, int64_t C, bool split) {
+  RankGeom g;
+  const int64_t M = N / 2;
+  g.S = split ? 2 * C * M : N * C;
+  g.P = rank_pow2(g.S);
+  g.first = split ? M * C : g.S;
+  g.skip = split ? (N - 2 * M) * C : 0;
+  g.mid_row0 = (split && (N & 1)) ? M * C : -1;
+  return g;
+}
+
+omc_status rank_gather(omc_ctx* ctx, const double* store, const int64_t* idx, int64_t k0, int64_t kc, int64_t size, const RankGeom& g,
+                       const double* stats, uint64_t* keys, int32_t* flags) {
+  const dim3 grid((unsigned)((g.P + G_TS - 1) / G_TS), (unsigned)((kc + G_TE - 1) / G_TE));
+  hipLaunchKernelGGL(k_rank_gather, grid, dim3(256), 0, ctx->stream, store, idx, k0, kc, size, ctx->n_chains, g.S, g.P, g.first, g.skip,
+                     g.mid_row0, stats, keys, flags);
+  OMC_HIP_CHECK(hipGetLastError());
+  return OMC_OK;
+}
+
+// index check on the device, one word read back before anything is written; words = the head of the workspace
+omc_status rank_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64_t size, int32_t* words) {
+  if (!idx) return OMC_OK;
+  OMC_HIP_CHECK(hipMemsetAsync(words, 0, sizeof(int32_t), ctx->stream));
+  hipLaunchKernelGGL(k_rank_check, dim3((unsigned)((n_idx + 255) / 256)), dim3(256), 0, ctx->stream, idx, n_idx, size, words);
+  OMC_HIP_CHECK(hipGetLastError());
+  int32_t got = 0;
+  OMC_HIP_CHECK(hipMemcpyAsync(&got, words, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return got ? OMC_INVALID_ARG : OMC_OK;
+}
+
+int64_t rank_chunk(const omc_ctx* ctx, size_t per_elem, int64_t n_idx) {
+  int64_t Kc = ctx->rank_chunk > 0 ? ctx->rank_chunk : (int64_t)(RANK_BUDGET / per_elem);
+  if (Kc < 1) Kc = 1;
+  if (Kc > RANK_KC_MAX) Kc = RANK_KC_MAX;
+  return Kc < n_idx ? Kc : n_idx;
+}
+
+constexpr size_t RANK_HEAD = 64;  // bytes in front of the per-element arrays: the word of rank_check
+
+}  // namespace
+
+extern "C" omc_status omc_store_rank_schedule(int64_t S, int32_t tile, int64_t* out, int64_t cap, int64_t* n_out) {
+  if (S < 1 || !n_out || cap < 0 || (cap > 0 && !out)) return OMC_INVALID_ARG;
+  if (tile != 0 && (tile < 64 || tile > RANK_TILE_DEFAULT || (tile & (tile - 1)))) return OMC_INVALID_ARG;
+  const std::vector<RankLaunch> L = rank_schedule(rank_pow2(S), tile ? tile : RANK_TILE_DEFAULT);
+  *n_out = (int64_t)L.size();
+  if ((int64_t)L.size() > cap) return OMC_INVALID_ARG;
+  for (size_t i = 0; i < L.size(); ++i) {
+    out[3 * i] = L[i].kind; out[3 * i + 1] = L[i].k; out[3 * i + 2] = L[i].j;
+  }
+  return OMC_OK;
+}
+
+extern "C" omc_status omc_store_ranks(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                                      int32_t split, double* rank_out) {
+  if (!ctx || n_iter < (split ? 4 : 1) || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size) || !rank_out) return OMC_INVALID_ARG;
+  const int64_t N = n_iter, C = ctx->n_chains;
+  const RankGeom g = rank_geom(N, C, split != 0);
+  if ((N * C + 63) / 64 > 0x7fffffffLL) return OMC_INVALID_ARG;
+  OMC_HIP_CHECK(hipSetDevice(ctx->device));
+  const size_t per_elem = (size_t)g.P * sizeof(uint64_t) + sizeof(int32_t);
+  const int64_t Kc = rank_chunk(ctx, per_elem, n_idx);
+  omc_status st = omc_ensure_bytes(ctx, &ctx->rank_ws, &ctx->rank_ws_bytes, RANK_HEAD + (size_t)Kc * per_elem + 64);
+  if (st != OMC_OK) return st;
+  char* ws = (char*)ctx->rank_ws;
+  uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
+  int32_t* flags = (int32_t*)(ws + RANK_HEAD + (size_t)Kc * g.P * sizeof(uint64_t));
+  st = rank_check(ctx, idx, n_idx, size, (int32_t*)ws);
+  if (st != OMC_OK) return st;
+  for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {
+    const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc;
+    OMC_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)kc * sizeof(int32_t), ctx->stream));
+    st = rank_gather(ctx, store, idx, k0, kc, size, g, nullptr, keys, flags);
+    if (st != OMC_OK) return st;
+    st = rank_sort(ctx, keys, kc, g.P);
+    if (st != OMC_OK) return st;
+    RankEmit a;
+    a.store = store; a.idx = idx; a.keys = keys; a.flags = flags; a.stats = nullptr; a.out = rank_out;
+    a.k0 = k0; a.Kc = kc; a.size = size; a.C = C; a.S = g.S; a.P = g.P; a.n_rows = N * C; a.mid_row0 = g.mid_row0; a.ld_out = n_idx;
+    a.mode = RANK_EMIT_RANKS;
+    hipLaunchKernelGGL(k_rank_emit, rank_emit_grid(a), dim3(256), 0, ctx->stream, a);
+    OMC_HIP_CHECK(hipGetLastError());
+  }
+  return OMC_OK;
+}
+
+extern "C" omc_status omc_store_rank_diagnostics(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx,
+                                                 int64_t n_idx, double* rhat_out, double* ess_bulk_out, double* ess_tail_out) {
+  if (!ctx || n_iter < 4 || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size)) return OMC_INVALID_ARG;
+  const int64_t N = n_iter, C = ctx->n_chains;
+  const RankGeom g = rank_geom(N, C, true);
+  if ((N * C + 63) / 64 > 0x7fffffffLL) return OMC_INVALID_ARG;
+  OMC_HIP_CHECK(hipSetDevice(ctx->device));
+  // per element: keys [P], the four series [N C][4], median and two quantiles, R-hat and ESS of the four series, the flag word
+  const size_t per_elem = (size_t)g.P * sizeof(uint64_t) + (size_t)N * C * 4 * sizeof(double) + (3 + 8) * sizeof(double) + sizeof(int32_t);
+  const int64_t Kc = rank_chunk(ctx, per_elem, n_idx);
+  omc_status st = omc_ensure_bytes(ctx, &ctx->rank_ws, &ctx->rank_ws_bytes, RANK_HEAD + (size_t)Kc * per_elem + 64);
+  if (st != OMC_OK) return st;
+  char* ws = (char*)ctx->rank_ws;
+  uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
+  double* series = (double*)(keys + (size_t)Kc * g.P);
+  double* stats = series + (size_t)N * C * 4 * Kc;
+  double* rh4 = stats + 3 * Kc;
+  double* es4 = rh4 + 4 * Kc;
+  int32_t* flags = (int32_t*)(es4 + 4 * Kc);
+  st = rank_check(ctx, idx, n_idx, size, (int32_t*)ws);
+  if (st != OMC_OK) return st;
+  hipStream_t s = ctx->stream;
+  for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {
+    const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc;
+    OMC_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)kc * sizeof(int32_t), s));
+    RankEmit a;
+    a.store = store; a.idx = idx; a.keys = keys; a.flags = flags; a.stats = stats; a.out = series;
+    a.k0 = k0; a.Kc = kc; a.size = size; a.C = C; a.S = g.S; a.P = g.P; a.n_rows = N * C; a.mid_row0 = g.mid_row0; a.ld_out = 0;
+    // the draws: z and the tail indicators
+    st = rank_gather(ctx, store, idx, k0, kc, size, g, nullptr, keys, flags);
+    if (st != OMC_OK) return st;
+    st = rank_sort(ctx, keys, kc, g.P);
+    if (st != OMC_OK) return st;
+    hipLaunchKernelGGL(k_rank_stats, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, s, kc, g.S, g.P, keys, stats);
+    a.mode = RANK_EMIT_Z;
+    hipLaunchKernelGGL(k_rank_emit, rank_emit_grid(a), dim3(256), 0, s, a);
+    // the folded draws |x - med|
+    st = rank_gather(ctx, store, idx, k0, kc, size, g, stats, keys, nullptr);
+    if (st != OMC_OK) return st;
+    st = rank_sort(ctx, keys, kc, g.P);
+    if (st != OMC_OK) return st;
+    a.mode = RANK_EMIT_ZFOLD;
+    hipLaunchKernelGGL(k_rank_emit, rank_emit_grid(a), dim3(256), 0, s, a);
+    OMC_HIP_CHECK(hipGetLastError());
+    st = omc_store_rhat_ess(ctx, N, 4 * kc, series, rh4, es4, nullptr);
+    if (st != OMC_OK) return st;
+    hipLaunchKernelGGL(k_rank_combine, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, s, kc, k0, flags, rh4, es4, rhat_out, ess_bulk_out,
+                       ess_tail_out);
+    OMC_HIP_CHECK(hipGetLastError());
+  }
+  return OMC_OK;
+}

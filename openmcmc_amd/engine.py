@@ -1297,6 +1297,47 @@ class Engine:
                                       int(bool(pooled)), n_bins, e.data_ptr(), int(e.dim() == 2), counts.data_ptr(), outside.data_ptr()))
         return counts, outside
 
+    @staticmethod
+    def rank_schedule(n_draws, tile=0):
+        """The launches that sort columns of n_draws keys with LDS tiles of `tile` keys (0: the default 8192), as
+        omc_store_rank_schedule lists them: [(kind, k, j), ...] (include/omcmc_hip.h; needs no GPU)."""
+        n = C.c_int64(0)
+        cap = 1024
+        out = (C.c_int64 * (3 * cap))()
+        check(lib.omc_store_rank_schedule(int(n_draws), int(tile), out, cap, C.byref(n)))
+        return [tuple(out[3 * i: 3 * i + 3]) for i in range(n.value)]
+
+    def store_ranks(self, store, index=None, split=False):
+        """Average ranks of the draws of every selected element of a device store (n_iter, C, size), on the device
+        (omc_store_ranks): a device tensor (n_iter, C, n_idx), scipy.stats.rankdata(method="average") of the element's
+        n_iter * C draws, bit for bit.  split=True: ranks among the split draws (first and last n_iter // 2 iterations of
+        every chain, n_iter >= 4), NaN in the dropped middle row of an odd n_iter.  An element with a NaN draw gives NaN."""
+        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
+            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        n_iter, _, size = store.shape
+        if n_iter < (4 if split else 1):
+            raise ValueError("split ranks need at least 4 stored iterations")
+        idx, n = self._store_index(index, size)
+        out = self.empty(n_iter, self.n_chains, n)
+        check(lib.omc_store_ranks(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n,
+                                  int(bool(split)), self._p(out)))
+        return out
+
+    def store_rank_diagnostics(self, store, index=None):
+        """Rank-normalised split R-hat, bulk-ESS and tail-ESS (Vehtari et al. 2021) of every selected element of a device
+        store (n_iter, C, size), on the device (omc_store_rank_diagnostics): (rhat, ess_bulk, ess_tail) as device tensors
+        of shape (n_idx,).  n_iter >= 4; an element with a NaN or infinite draw gives NaN."""
+        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
+            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        n_iter, _, size = store.shape
+        if n_iter < 4:
+            raise ValueError("rank-normalised R-hat and ESS need at least 4 stored iterations")
+        idx, n = self._store_index(index, size)
+        rhat, bulk, tail = self.empty(n), self.empty(n), self.empty(n)
+        check(lib.omc_store_rank_diagnostics(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n,
+                                             self._p(rhat), self._p(bulk), self._p(tail)))
+        return rhat, bulk, tail
+
     def store_thin(self, store, every, first=0):
         """store[first::every] of a device store (n_iter, C, ...) as a packed device tensor (one launch)."""
         if store.dim() < 2 or store.shape[1] != self.n_chains or not store.is_contiguous():

@@ -399,6 +399,27 @@ class MCMC:
         rhat, ess, var = rhat.cpu().numpy(), ess.cpu().numpy(), var.cpu().numpy()
         return {"rhat": rhat, "ess": ess, "mcse_mean": np.sqrt(var) / np.sqrt(ess)}
 
+    def rank_diagnostics(self, key, index=None):
+        """Rank-normalised convergence diagnostics of store[key] (Vehtari et al. 2021, the defaults of Stan and ArviZ),
+        computed on the device (no gather of the store): a dict of host arrays of shape (n_idx,) -- "rhat" (the larger of
+        the rank-normalised split R-hat of the draws and of the draws folded around their median), "ess_bulk" and
+        "ess_tail" (the smaller ESS of the indicators of the 5 % and 95 % quantiles).  They see differences in scale and
+        in the tails that `diagnostics` (means and variances of the raw draws) does not.  index selects elements (in that
+        order, repeats allowed); a 2-D entry ("log_post") counts as one element.  An element with a NaN or infinite draw
+        gives NaN.  Every element is sorted: meant for the elements one inspects.  Under a sharded multi-GPU run these are
+        diagnostics of this rank's chains only."""
+        self._whole_store_on_device("rank diagnostics")
+        rhat, bulk, tail = self.engine.store_rank_diagnostics(self._store_3d(key), index=index)
+        return {"rhat": rhat.cpu().numpy(), "ess_bulk": bulk.cpu().numpy(), "ess_tail": tail.cpu().numpy()}
+
+    def ranks(self, key, index=None, split=False):
+        """Average ranks of the stored draws of every selected element of store[key] among all chains and iterations
+        (scipy.stats.rankdata(method="average") per element), computed on the device: a host array (n_iter, C, n_idx), the
+        store's own layout -- ranks[:, c, i] is what a rank histogram of chain c shows.  split=True ranks among the split
+        draws the diagnostics use (NaN in the dropped middle row of an odd n_iter).  An element with a NaN draw gives NaN."""
+        self._whole_store_on_device("ranks")
+        return self.engine.store_ranks(self._store_3d(key), index=index, split=split).cpu().numpy()
+
     def _store_3d(self, key):
         t = self.store[key]
         return (t.unsqueeze(-1) if t.dim() == 2 else t.reshape(t.shape[0], t.shape[1], -1)).contiguous()

@@ -1,0 +1,37 @@
+"""Compile-time guard for the rank kernels (omc_rank.hip; no GPU needed: hipcc cross-compiles): the gather, the two sort
+kernels, the bisection and the rest keep everything in registers -- no scratch, no spilled VGPRs."""
+
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+
+
+def test_rank_kernels_need_no_scratch(tmp_path):
+    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", f"-I{ROOT}/include",
+           "-mllvm", "-instcombine-max-copied-from-constant-users=100000",  # as openmcmc_amd/csrc/Makefile
+           "-c", f"{ROOT}/openmcmc_amd/csrc/omc_rank.hip", "-o", str(tmp_path / "omc_rank.o"),
+           "-Rpass-analysis=kernel-resource-usage"]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    usage, name = {}, None
+    for line in (out.stderr + out.stdout).splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            usage[name] = {}
+        m = re.search(r"(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
+        if m and name:
+            usage[name][m.group(1)] = int(m.group(2))
+    kernels = {k: v for k, v in usage.items() if "k_rank_" in k}
+    # index check, gather, tile sort, global pass, quantiles, emit, combine
+    assert len(kernels) >= 7, sorted(usage)
+    bad = {k: v for k, v in kernels.items() if v.get("ScratchSize [bytes/lane]") != 0 or v.get("VGPRs Spill") != 0}
+    assert not bad, bad
