@@ -101,6 +101,8 @@ omc_status omc_ctx_synchronize(omc_ctx* ctx);
  * explicit setting holds for every chain count),
  * "diag_algo" (0 auto; 1 the short-series form of omc_store_rhat_ess, M <= 64; 2 its blocks of lags),
  * "hist_algo" (0 auto; 1 omc_store_histogram always finds the bin by bisection, also with evenly spaced edges: same counts),
+ * "hist2d_algo" (0 auto; bit 0: omc_store_histogram2d always takes the direct form, atomic adds to the output without counters in
+ * LDS; bit 1: it always finds the bins by bisection; same counts either way),
  * "rank_tile" (0 = 8192, or a power of two 64 .. 8192: keys of an LDS tile of the sort behind omc_store_ranks; same results bit for
  * bit), "rank_chunk" (0 auto, else the elements omc_store_ranks / omc_store_rank_diagnostics work on at a time),
  * "band_algo" (0 auto; 1 narrow bands one lane per chain in ONE piece; 2 one workgroup per chain, a column per step; 3 one
@@ -860,6 +862,43 @@ omc_status omc_store_histogram(omc_ctx* ctx, int64_t n_iter, int64_t size, const
  * element's counters (words), byte offsets of the edges, the counters and the outside counts, end of the image = bytes launched,
  * the budget the tile was chosen for, threads of a workgroup}.                                                           */
 omc_status omc_store_histogram_layout(int32_t n_bins, int32_t edges_per_element, int32_t* out);
+/* Joint histogram of pairs of elements of the same store(s): np.histogram2d(x, y, bins=[edges_x, edges_y]) of two rows of the
+ * reference's host arrays MCMC.store[param] (mcmc.py:105-111), for all pairs at once; layout conventions of omc_store_histogram.
+ *   store_x [n_iter][C][size_x], store_y [n_iter][C][size_y] (device): the same tensor or two; pair k = (element idx_x[k] of
+ *           store_x, element idx_y[k] of store_y) read from the same row.  idx_x, idx_y [n_pairs] (device), in that order, repeats
+ *           allowed; NULL = all elements (n_pairs must then equal that store's size).
+ *   pooled != 0: one batch of R = n_iter C rows; pooled == 0: C batches, chain c over its own n_iter rows.
+ *   edges_x [nx + 1], edges_y [ny + 1] (device) shared by all pairs, or [n_pairs][nx + 1], [n_pairs][ny + 1] when
+ *           edges_per_pair != 0 (one flag for both axes; per-pair shape only).  1 <= nx, ny <= 1024.  Non-decreasing, equal
+ *           neighbours and +-inf allowed.  A NaN edge, a decreasing pair of edges or an index outside [0, size) is
+ *           OMC_INVALID_ARG, found on the device before anything is written: the outputs are then untouched.
+ *   Per axis the bin rule is omc_store_histogram's (the last j with edges[j] <= v, the last bin closed; an arithmetic guess with
+ *   evenly spaced edges, put right by comparisons).  A pair is counted in cell (jx, jy) when both coordinates lie inside their
+ *   edge ranges: a NaN in either coordinate drops the pair, as np.histogram2d does.
+ *   pool_pairs == 0: counts_out int64 [batches][n_pairs][nx][ny], outside_out int64 [batches][n_pairs][2];
+ *   pool_pairs != 0: all pairs into one grid, counts_out [batches][nx][ny], outside_out [batches][2] -- the map of a ragged
+ *           (NaN-padded) parameter; occupied_out int64 [batches][nx][ny] (NULL = not wanted; pooled pairs only, else
+ *           OMC_INVALID_ARG) = the rows, (iteration, chain) states, in which the cell received at least one of the row's
+ *           pairs: the sum over stored states of np.histogramdd(...) > 0.  occupied <= counts cell by cell, occupied <= R.
+ *           With occupied_out, n_pairs > 256 is OMC_UNSUPPORTED (a row's cells are compared within one wave).
+ *   outside = {pairs with both coordinates non-NaN and at least one outside its edge range, pairs with a NaN coordinate}; may be
+ *   NULL.  Every output row: sum(counts) + outside[0] + outside[1] = the pairs taken.  Outputs are overwritten.
+ * One read of the selected columns.  LDS form: 32-bit counters per workgroup, the non-zero ones added to the zeroed outputs with
+ * 64-bit integer atomics.  Direct form: those atomic adds straight from the counting loop -- taken when the counters of one pair
+ * do not fit the LDS budget, when the rows a workgroup walks times the pairs pooled into one counter reach 2^32, or with option
+ * "hist2d_algo" bit 0.  Integer sums do not depend on the order: repeated calls and both forms are bit-equal; no
+ * floating-point atomics.  Runs on the context's stream; the host reads two words back per axis (the validation).          */
+omc_status omc_store_histogram2d(omc_ctx* ctx, int64_t n_iter, int64_t size_x, const double* store_x, const int64_t* idx_x,
+                                 int64_t size_y, const double* store_y, const int64_t* idx_y, int64_t n_pairs, int32_t pooled,
+                                 int32_t pool_pairs, int32_t nx, const double* edges_x, int32_t ny, const double* edges_y,
+                                 int32_t edges_per_pair, int64_t* counts_out, int64_t* outside_out, int64_t* occupied_out);
+/* [host, no GPU] The tiling and LDS image omc_store_histogram2d takes at (nx, ny) (each 1..1024, else OMC_INVALID_ARG);
+ * pool_pairs: 0 a grid per pair, 1 pooled pairs, 2 pooled pairs with the occupancy grid (edges_per_pair must then be 0).
+ * out[14] = {form (0 LDS, 1 direct: the counters of one pair do not fit), TE (pairs of a workgroup's tile; 1 pooled), RB (rows of
+ * a slice), strides of a pair's x and y edges (doubles; 0 when shared), stride of a pair's counters (words; 0 in the direct
+ * form), byte offsets of the x edges, the y edges, the counters, the occupancy counters and the outside counts, end of the
+ * image = bytes launched, the budget the tile was chosen for, threads of a workgroup}.                                  */
+omc_status omc_store_histogram2d_layout(int32_t nx, int32_t ny, int32_t edges_per_pair, int32_t pool_pairs, int32_t* out);
 /* Ranks of the draws of every selected element of the same store; store, idx, n_idx, the NULL convention and the out-of-range rule
  * as omc_store_minmax (an index outside [0, size) is OMC_INVALID_ARG, found on the device before any output is written).
  * With N = n_iter >= 4: M = N / 2, J = 2 C, S = J M; the SPLIT DRAWS of an element are the first M and the last M iterations of

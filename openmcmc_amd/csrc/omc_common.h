@@ -84,6 +84,7 @@ struct omc_ctx {
   int band_algo;  // 0 auto, 1 lane-per-chain in one piece (narrow bands), 2 workgroup-per-chain
   int diag_algo;  // omc_store_rhat_ess: 0 auto, 1 short-series form (M <= 64), 2 blocks of lags
   int hist_algo;  // omc_store_histogram: 0 auto (arithmetic guess of the bin when the edges are evenly spaced), 1 always the bisection
+  int hist2d_algo;  // omc_store_histogram2d: bit 0 always the direct form (atomic adds to the output, no LDS counters), bit 1 always the bisection
   int rank_tile;  // omc_rank.hip: keys of an LDS tile of the sort, a power of two 64 .. 8192 (0: 8192)
   int64_t rank_chunk;  // omc_rank.hip: elements per chunk (0: what fits the workspace budget)
   int band_seg_overlap;  // segmented lane kernel: columns of warm-up before a segment (default 192)
@@ -118,6 +119,9 @@ omc_status omc_dgemm_wide(omc_ctx* ctx, int M, int N, const double* A, int64_t l
                           const double* addv, double* Cout, int64_t ldc);
 omc_status omc_ensure_aux(omc_ctx* ctx);  // side stream + its events and BLAS handle, made on first use (omc_dense.hip)
 omc_status omc_col_moments(omc_ctx* ctx, const double* data, int64_t R, int64_t K, double* mean_out, double* var_out);  // omc_store.hip
+// omc_hist.hip: got[0] = 1: an index outside [0, size), a NaN edge or a decreasing pair of edges; got[1] = 1: some row of edges is not evenly spaced
+omc_status omc_hist_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64_t size, const double* edges, int64_t edge_rows, int n_bins,
+                          int32_t got[2]);
 extern "C" omc_status omc_gram_mfma_launch(omc_ctx* ctx, int64_t n, int64_t p, const double* X, const double* w, double* G_out);  // omc_gram.hip  // destroys the rocBLAS handle if one was created
 
 #define OMC_HIP_CHECK(expr)                  \

@@ -211,9 +211,11 @@ __global__ void k_hist_minmax_join(int64_t cols, int parts, const double* __rest
   if (count_out) count_out[o] = cnt;
 }
 
-// the two words of k_hist_check, read back: the launches behind it write nothing before the host has seen them
-omc_status hist_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64_t size, const double* edges, int64_t edge_rows, int n_bins,
-                      int32_t got[2]) {
+}  // namespace
+
+// the two words of k_hist_check, read back: the launches behind it write nothing before the host has seen them (also omc_hist2d.hip)
+omc_status omc_hist_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64_t size, const double* edges, int64_t edge_rows, int n_bins,
+                          int32_t got[2]) {
   got[0] = got[1] = 0;
   if (!idx && !edges) return OMC_OK;
   omc_status st = omc_ensure_bytes(ctx, &ctx->store_ws, &ctx->store_ws_bytes, 64);
@@ -229,8 +231,6 @@ omc_status hist_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64_t s
   OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return OMC_OK;
 }
-
-}  // namespace
 
 extern "C" omc_status omc_store_histogram_layout(int32_t n_bins, int32_t edges_per_element, int32_t* out) {
   if (n_bins < 1 || n_bins > HIST_MAX_BINS || !out) return OMC_INVALID_ARG;
@@ -249,7 +249,7 @@ extern "C" omc_status omc_store_minmax(omc_ctx* ctx, int64_t n_iter, int64_t siz
   if (tiles * batches > 0x7fffffffLL) return OMC_INVALID_ARG;
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   int32_t got[2];
-  omc_status st = hist_check(ctx, idx, n_idx, size, nullptr, 0, 0, got);
+  omc_status st = omc_hist_check(ctx, idx, n_idx, size, nullptr, 0, 0, got);
   if (st != OMC_OK) return st;
   if (got[0]) return OMC_INVALID_ARG;
   const int64_t slices = (R + HIST_MM_RB - 1) / HIST_MM_RB;
@@ -291,7 +291,7 @@ extern "C" omc_status omc_store_histogram(omc_ctx* ctx, int64_t n_iter, int64_t 
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   int32_t got[2];
-  omc_status st = hist_check(ctx, idx, n_idx, size, edges, per ? n_idx : 1, n_bins, got);
+  omc_status st = omc_hist_check(ctx, idx, n_idx, size, edges, per ? n_idx : 1, n_bins, got);
   if (st != OMC_OK) return st;
   if (got[0]) return OMC_INVALID_ARG;
   OMC_HIP_CHECK(hipMemsetAsync(counts_out, 0, (size_t)batches * n_idx * n_bins * sizeof(int64_t), s));

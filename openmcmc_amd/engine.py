@@ -1281,10 +1281,7 @@ class Engine:
             raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
         n_iter, _, size = store.shape
         idx, n = self._store_index(index, size)
-        if isinstance(edges, torch.Tensor):
-            e = edges.to(device=self.device, dtype=torch.float64).contiguous()
-        else:  # (torch.tensor copies from the numpy array before it returns: no asynchronous read of a temporary)
-            e = torch.tensor(np.ascontiguousarray(edges, dtype=np.float64), dtype=torch.float64, device=self.device)
+        e = self._store_edges(edges)
         if e.dim() not in (1, 2) or (e.dim() == 2 and e.shape[0] != n):
             raise ValueError("edges must be (n_bins + 1,) or (number of selected elements, n_bins + 1)")
         n_bins = e.shape[-1] - 1
@@ -1296,6 +1293,74 @@ class Engine:
         check(lib.omc_store_histogram(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n,
                                       int(bool(pooled)), n_bins, e.data_ptr(), int(e.dim() == 2), counts.data_ptr(), outside.data_ptr()))
         return counts, outside
+
+    @staticmethod
+    def hist2d_tile(nx, ny, per_pair=False, pool_pairs=False):
+        """(TE, RB) of omc_store_histogram2d at an nx x ny grid: a workgroup counts a tile of TE consecutive pairs (1 with
+        pool_pairs: one grid for all pairs) over slices of RB rows (openmcmc_amd/csrc/omc_hist2d_layout.h through
+        omc_store_histogram2d_layout; needs no GPU).  pool_pairs: False / 0 a grid per pair, True / 1 pooled pairs, 2 pooled
+        pairs with the occupancy grid."""
+        return tuple(Engine.hist2d_layout(nx, ny, per_pair, pool_pairs)[1:3])
+
+    @staticmethod
+    def hist2d_layout(nx, ny, per_pair=False, pool_pairs=False):
+        """The fourteen numbers of omc_store_histogram2d_layout: form (0 LDS counters, 1 direct), TE, RB, strides of a pair's
+        x and y edges and of its counters, byte offsets of the x edges, the y edges, the counters, the occupancy counters and
+        the outside counts, bytes launched, the budget, threads of a workgroup."""
+        out = (C.c_int32 * 14)()
+        check(lib.omc_store_histogram2d_layout(int(nx), int(ny), int(bool(per_pair)), int(pool_pairs), out))
+        return list(out)
+
+    def _store_edges(self, edges):
+        torch = _torch()
+        if isinstance(edges, torch.Tensor):
+            return edges.to(device=self.device, dtype=torch.float64).contiguous()
+        # (torch.tensor copies from the numpy array before it returns: no asynchronous read of a temporary)
+        return torch.tensor(np.ascontiguousarray(edges, dtype=np.float64), dtype=torch.float64, device=self.device)
+
+    def store_histogram2d(self, store_x, store_y, edges_x, edges_y, index_x=None, index_y=None, pooled=True, pool_pairs=False,
+                          occupancy=False):
+        """(counts, outside[, occupied]) of pairs of elements of device stores (n_iter, C, size_x) and (n_iter, C, size_y) -- the
+        same tensor or two --, on the device (omc_store_histogram2d).  Pair k is (element index_x[k] of store_x, element
+        index_y[k] of store_y) of the same row; the two selections must be equally long.  counts int64 (n_pairs, nx, ny) pooled
+        over chains and iterations, else (C, n_pairs, nx, ny) = np.histogram2d(x, y, bins=[edges_x, edges_y])[0] of the pair's
+        draws; with pool_pairs all pairs are counted into one grid, (nx, ny) or (C, nx, ny).  outside int64 (.., 2) = pairs
+        with a coordinate outside its edges, pairs with a NaN coordinate (left out, as in numpy).  occupancy=True (pool_pairs
+        only, at most 256 pairs): occupied int64, the shape of counts = the rows (iteration, chain) in which the cell holds at
+        least one of the row's pairs.  edges_x (nx + 1,), edges_y (ny + 1,) shared by all pairs, or (n_pairs, nx + 1) and
+        (n_pairs, ny + 1) per pair (both or neither; not with pool_pairs); host arrays (uploaded synchronously) or device
+        tensors; non-decreasing, no NaN."""
+        torch = _torch()
+        for t in (store_x, store_y):
+            if t.dim() != 3 or t.shape[1] != self.n_chains or not t.is_contiguous():
+                raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        if store_y.shape[0] != store_x.shape[0]:
+            raise ValueError("store_x and store_y must hold the same number of iterations")
+        n_iter, _, size_x = store_x.shape
+        size_y = store_y.shape[2]
+        idx_x, n = self._store_index(index_x, size_x)
+        idx_y, n_y = self._store_index(index_y, size_y)
+        if n != n_y:
+            raise ValueError(f"{n} elements of x against {n_y} of y: pairs need equally many")
+        ex, ey = self._store_edges(edges_x), self._store_edges(edges_y)
+        if ex.dim() != ey.dim() or ex.dim() not in (1, 2) or (ex.dim() == 2 and (ex.shape[0] != n or ey.shape[0] != n)):
+            raise ValueError("edges must be (nx + 1,) and (ny + 1,), or (number of pairs, nx + 1) and (number of pairs, ny + 1)")
+        if ex.dim() == 2 and pool_pairs:
+            raise ValueError("pooled pairs share their edges")
+        if occupancy and not pool_pairs:
+            raise ValueError("occupancy is that of the pooled pairs: pool_pairs=True")
+        nx, ny = ex.shape[-1] - 1, ey.shape[-1] - 1
+        if not (1 <= nx <= 1024 and 1 <= ny <= 1024):
+            raise ValueError("between 1 and 1024 bins per axis")
+        lead = (() if pooled else (self.n_chains,)) + (() if pool_pairs else (n,))
+        counts = torch.empty(lead + (nx, ny), dtype=torch.int64, device=self.device)
+        outside = torch.empty(lead + (2,), dtype=torch.int64, device=self.device)
+        occupied = torch.empty(lead + (nx, ny), dtype=torch.int64, device=self.device) if occupancy else None
+        check(lib.omc_store_histogram2d(self._ctx, n_iter, size_x, self._p(store_x), None if idx_x is None else idx_x.data_ptr(),
+                                        size_y, self._p(store_y), None if idx_y is None else idx_y.data_ptr(), n, int(bool(pooled)),
+                                        int(bool(pool_pairs)), nx, ex.data_ptr(), ny, ey.data_ptr(), int(ex.dim() == 2),
+                                        counts.data_ptr(), outside.data_ptr(), None if occupied is None else occupied.data_ptr()))
+        return (counts, outside, occupied) if occupancy else (counts, outside)
 
     @staticmethod
     def rank_schedule(n_draws, tile=0):

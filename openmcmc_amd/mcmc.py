@@ -514,6 +514,100 @@ class MCMC:
         out[..., order] = p
         return np.moveaxis(out, -1, 0)
 
+    def _axis_edges(self, t, index, bins, rng, pool_elements):
+        """Edges of one axis of histogram2d: (n + 1,) shared by all pairs or (n_pairs, n + 1), by np.histogramdd's rules"""
+        if np.ndim(bins) == 0:
+            n = int(bins)
+            if n != bins or not 1 <= n <= 1024:
+                raise ValueError("bins must be integers between 1 and 1024 or arrays of edges")
+            if rng is not None:
+                lo, hi = (float(v) for v in rng)
+                if lo > hi:
+                    raise ValueError("max must be larger than min in range parameter.")  # np.histogramdd's own messages
+                if not (np.isfinite(lo) and np.isfinite(hi)):
+                    raise ValueError(f"supplied range of [{lo}, {hi}] is not finite")
+                lo, hi = np.array([lo]), np.array([hi])
+            else:
+                mn, mx, cnt = (v.cpu().numpy() for v in self.engine.store_minmax(t, index=index, pooled=True))
+                lo, hi = np.where(cnt > 0, mn, 0.0), np.where(cnt > 0, mx, 1.0)
+                if pool_elements:  # one range over all selected elements: that of the flattened draws
+                    have = cnt > 0
+                    lo, hi = (np.array([lo[have].min()]), np.array([hi[have].max()])) if have.any() else (np.zeros(1), np.ones(1))
+                if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+                    raise ValueError("autodetected range is not finite")
+            same = lo == hi
+            lo, hi = np.where(same, lo - 0.5, lo), np.where(same, hi + 0.5, hi)
+            edges = np.stack([np.linspace(a, b, n + 1) for a, b in zip(lo, hi)])
+            return edges[0] if (rng is not None or pool_elements) else edges
+        edges = np.array(bins, dtype=np.float64)
+        if edges.ndim not in (1, 2) or edges.shape[-1] < 2 or (edges.ndim == 2 and pool_elements):
+            raise ValueError("bins must be integers, (n + 1,) edges or, without pool_elements, (n_pairs, n + 1) edges")
+        if np.isnan(edges).any() or (np.diff(edges, axis=-1) < 0).any():
+            raise ValueError("`bins` must increase monotonically, when an array")
+        return edges
+
+    def _hist2d(self, key_x, key_y, index_x, index_y, bins, range, pooled, pool_elements, occupancy):
+        tx = self._store_3d(key_x)
+        ty = tx if key_y is None else self._store_3d(key_y)
+        try:
+            n_given = len(bins)
+        except TypeError:
+            n_given = 1
+        if n_given != 2:  # (np.histogram2d: an int, or one array of edges for both axes)
+            bins = [bins, bins]
+        rngs = [None, None] if range is None else list(range)
+        if len(rngs) != 2:
+            raise ValueError("range must be [[xlo, xhi], [ylo, yhi]]")
+        ex = self._axis_edges(tx, index_x, bins[0], rngs[0], pool_elements)
+        ey = self._axis_edges(ty, index_y, bins[1], rngs[1], pool_elements)
+        gx, gy = ex, ey
+        if ex.ndim != ey.ndim:  # per-pair edges on one axis only: the other axis' edges for every pair
+            n = max(ex.shape[0] if ex.ndim == 2 else 0, ey.shape[0] if ey.ndim == 2 else 0)
+            gx = ex if ex.ndim == 2 else np.broadcast_to(ex, (n, ex.size))
+            gy = ey if ey.ndim == 2 else np.broadcast_to(ey, (n, ey.size))
+        out = self.engine.store_histogram2d(tx, ty, gx, gy, index_x=index_x, index_y=index_y, pooled=pooled,
+                                            pool_pairs=pool_elements, occupancy=occupancy)
+        return [v.cpu().numpy() for v in out], ex, ey, tx.shape[0] * (tx.shape[1] if pooled else 1)
+
+    def histogram2d(self, key_x, key_y=None, index_x=None, index_y=None, bins=10, range=None, pooled=True, pool_elements=False,
+                    density=False):
+        """np.histogram2d of the stored draws of pairs of elements, counted on the device (one read of the selected columns, no
+        gather): (hist, xedges, yedges) as host arrays.  Pair k is element index_x[k] of store[key_x] against element index_y[k]
+        of store[key_y] in the same (iteration, chain) state (key_y=None: two elements of store[key_x]; index None: all elements;
+        in that order, repeats allowed; a 2-D entry ("log_post") counts as one element; both sides equally many).  hist is
+        (n_pairs, nx, ny) pooled over chains and iterations, else (C, n_pairs, nx, ny); with pool_elements=True all pairs are
+        counted into one map, (nx, ny) or (C, nx, ny) -- the joint map of a variable-size parameter, locations against
+        coefficients.  int64 counts, or with density=True fp64, divided in np.histogramdd's order (by the x widths, by the y
+        widths, then by the sum), so that the densities are bit-equal to numpy's.
+        bins, as numpy takes them: an int, (nx, ny), one array of edges for both axes, or [xedges, yedges]; an axis' edges are
+        (n + 1,) shared by all pairs or (n_pairs, n + 1) per pair (not with pool_elements) and are returned as given.  An int
+        axis with range=[[xlo, xhi], [ylo, yhi]] gets the shared edges np.linspace(lo, hi, n + 1); without a range (or with None
+        in its place) every coordinate gets the edges numpy would give it, np.linspace over its own non-NaN minimum and maximum
+        over ALL chains (widened by 0.5 either way when they are equal, (0, 1) without a draw; an infinite draw raises ValueError
+        as in numpy) -- edges (n_pairs, n + 1), or with pool_elements (n + 1,) over all selected elements.
+        A pair with a NaN coordinate (the padding of variable-size parameters) is left out.  Under a sharded multi-GPU run these
+        are the counts of this rank's chains only; counts of several ranks over the same edges can simply be added."""
+        self._whole_store_on_device("histogram2d")
+        (counts, _), ex, ey, _ = self._hist2d(key_x, key_y, index_x, index_y, bins, range, pooled, pool_elements, False)
+        hist = counts
+        if density:  # (np.histogramdd's order of operations)
+            s = counts.sum(axis=(-2, -1), keepdims=True).astype(np.float64)
+            hist = counts.astype(np.float64) / np.diff(ex, axis=-1)[..., :, None] / np.diff(ey, axis=-1)[..., None, :]
+            hist /= s
+        return hist, ex, ey
+
+    def occupancy(self, key_x, key_y=None, index_x=None, index_y=None, bins=10, range=None, pooled=True):
+        """In what share of the stored states a cell of the (x, y) grid holds at least one of the selected pairs: (prob, xedges,
+        yedges), prob fp64 (nx, ny) over all chains and iterations, else (C, nx, ny) -- per state np.histogram2d(...)[0] > 0,
+        averaged over the states, counted on the device.  What a variable-size parameter has in place of marginals: where its
+        components (knots, sources) lie, location against coefficient or x against y.  Pairs, bins and range as `histogram2d`
+        with pool_elements=True (the elements always share their edges); at most 256 pairs; NaN-padded components are left
+        out.  Under a sharded multi-GPU run: this rank's chains only; prob times the states adds across ranks over the same
+        edges."""
+        self._whole_store_on_device("occupancy")
+        (_, _, occupied), ex, ey, rows = self._hist2d(key_x, key_y, index_x, index_y, bins, range, pooled, True, True)
+        return occupied / rows, ex, ey
+
     def _thinned(self, every):
         """{key: device tensor (ceil(n_iter / every), C, ...)}: every `every`-th stored iteration, packed on the device"""
         self._whole_store_on_device("a thinned transfer")
