@@ -104,7 +104,7 @@ omc_status omc_ctx_synchronize(omc_ctx* ctx);
  * "hist2d_algo" (0 auto; bit 0: omc_store_histogram2d always takes the direct form, atomic adds to the output without counters in
  * LDS; bit 1: it always finds the bins by bisection; same counts either way),
  * "rank_tile" (0 = 8192, or a power of two 64 .. 8192: keys of an LDS tile of the sort behind omc_store_ranks; same results bit for
- * bit), "rank_chunk" (0 auto, else the elements omc_store_ranks / omc_store_rank_diagnostics work on at a time),
+ * bit), "rank_chunk" (0 auto, else the elements omc_store_ranks / omc_store_rank_diagnostics / omc_store_hdi work on at a time),
  * "band_algo" (0 auto; 1 narrow bands one lane per chain in ONE piece; 2 one workgroup per chain, a column per step; 3 one
  * workgroup per chain in blocks of 16 columns, the next block factorised ahead, the window update on the matrix cores -- auto
  * takes it from w = 9, and from w = 4 on up to 3072 chains, where a lane per chain leaves the SIMDs to lone waves), "band_seg_overlap"
@@ -946,6 +946,30 @@ omc_status omc_store_rank_diagnostics(omc_ctx* ctx, int64_t n_iter, int64_t size
  *   kind 2: every tile, the strides j (= T / 2), j / 2 .. 1 of stage k.
  * P = 1 needs no launch; otherwise 1 + d launches of kinds 0 and 2 and d (d + 1) / 2 of kind 1, d = log2(P / T).            */
 omc_status omc_store_rank_schedule(int64_t S, int32_t tile, int64_t* out, int64_t cap, int64_t* n_out);
+/* Highest-density intervals of the same store: per selected column of draws the shortest interval that holds a share `prob` of
+ * them (ArviZ's unimodal hdi, what az.summary prints as hdi_3% / hdi_97%); store, idx, n_idx, the NULL convention and the
+ * out-of-range rule as omc_store_ranks.  A column is all n_iter * C draws of an element (per_chain == 0) or the n_iter draws of
+ * one chain of it (per_chain != 0).  For a column with n valid draws sorted ascending x[0 .. n) and 0 < prob < 1:
+ *   m    = min(floor(prob * n), n - 1)              (the fp64 product, as numpy's float64 * int)
+ *   w[i] = x[i + m] - x[i],  i = 0 .. n - m - 1     (one fp64 subtraction each)
+ *   i*   = the FIRST index of the minimum of w      (np.argmin)
+ *   hdi  = (x[i*], x[i* + m])
+ *   Both limits are stored draws, no arithmetic is done on them: results are exact.  -0.0 and +0.0 are one value (a zero limit
+ *   comes out as +0.0).  m == 0 (prob * n < 1) gives (x[0], x[0]); n == 0 gives (NaN, NaN); a column with a +-inf draw gives
+ *   (NaN, NaN) and affects nothing else.  omit_nan != 0: NaN draws are left out and n is the number of the others;
+ *   omit_nan == 0: a column with any NaN draw gives (NaN, NaN).
+ *   probs [n_probs] on the HOST, 1 <= n_probs <= 8, every one inside (0, 1), else OMC_INVALID_ARG (NaN included);
+ *   out [n_probs][n_idx][2] or, per chain, [n_probs][C][n_idx][2] fp64: lower and upper limit;
+ *   n_valid_out (may be NULL) [n_idx] or [C][n_idx] int64: the non-NaN draws of the column, whatever omit_nan says.
+ * A chunk of elements at a time (per chain: C columns per element): the gather and the sort of omc_store_ranks, with NaN draws on
+ * the all-ones key of the padding, n by bisection for that key, and one pass over the sorted column for all probabilities that
+ * keeps the minimum of the pairs (w, i) in lexicographic order, compared as integers, so that ties go to the lowest i in whatever
+ * order lanes, waves and workgroups are combined: repeated calls are bit-equal.  A column of up to 4096 draws is one wave's work; longer ones are
+ * cut into slices of 16384 windows, a workgroup each, with a second small launch where there are several; the slicing depends on the column length alone.  Options "rank_tile" and
+ * "rank_chunk" apply: same results bit for bit.  Workspace as omc_store_ranks (8 P bytes per column and a few words).        */
+omc_status omc_store_hdi(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                         const double* probs, int32_t n_probs, int32_t per_chain, int32_t omit_nan, double* out,
+                         int64_t* n_valid_out);
 /* Thinned copy of the store for a thinned gather: out[j] = store[first + j * every] (slabs of C * size doubles),
  * j = 0 .. ceil((n_iter - first) / every) - 1 (that count is left in *n_out when n_out is not NULL, host).           */
 omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int64_t first, int64_t every,

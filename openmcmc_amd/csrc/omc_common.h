@@ -33,7 +33,7 @@ struct omc_ctx {
   size_t workspace_bytes;
   void* store_ws; size_t store_ws_bytes;  // omc_store.hip, omc_hist.hip: histograms / partial moments of the store summaries
   double* cov_ws; size_t cov_ws_bytes;  // omc_cov.hip: means, variances and partial tiles of omc_store_cov
-  void* rank_ws; size_t rank_ws_bytes;  // omc_rank.hip: keys, series and per-element words of a chunk (its own: it calls omc_store_rhat_ess, which uses store_ws)
+  void* rank_ws; size_t rank_ws_bytes;  // omc_rank.hip, omc_hdi.hip: keys, series and per-element words of a chunk (its own: it calls omc_store_rhat_ess, which uses store_ws)
   // dense path (omc_dense.hip): rocBLAS handle and workspaces, created on first use
   void* blas;
   // blocked dense factorisation: second half of the chains on a side stream (forked from / joined into `stream` by events),

@@ -33,7 +33,7 @@ __device__ __forceinline__ void q_ranks(int64_t nv, double q, int64_t& lo, int64
 
 // numpy's _lerp (lib/_function_base_impl.py), operation by operation: a + (b - a) t, and b - (b - a)(1 - t) where t >= 0.5.
 // (HIP's __dmul_rn / __dadd_rn are plain operators the compiler may still fuse into an fma: contraction is switched off here)
-__device__ __noinline__ double q_lerp(double a, double b, double t) {
+[[maybe_unused]] __device__ __noinline__ double q_lerp(double a, double b, double t) {
 #pragma clang fp contract(off)
   const double diff = b - a;
   const double up = a + diff * t, down = b - diff * (1.0 - t);

@@ -1403,6 +1403,32 @@ class Engine:
                                              self._p(rhat), self._p(bulk), self._p(tail)))
         return rhat, bulk, tail
 
+    def store_hdi(self, store, prob, index=None, pooled=True, omit_nan=True):
+        """Highest-density intervals of every selected element of a device store (n_iter, C, size), on the device
+        (omc_store_hdi): (hdi, n_valid) as device tensors.  hdi is fp64 (n_prob, n_idx, 2) pooled over chains and iterations,
+        else (n_prob, C, n_idx, 2) per chain, [..., 0] the lower and [..., 1] the upper limit of the shortest interval that
+        holds floor(prob * n) + 1 of the column's n valid draws (ArviZ's unimodal hdi: both limits are stored draws);
+        n_valid is int64 (n_idx,) or (C, n_idx), the draws that are not NaN.  prob: a number or a sequence of at most 8,
+        each inside (0, 1); a scalar is one probability (n_prob = 1).  omit_nan leaves NaN draws out; without it a column
+        with a NaN gives NaN.  A column with an infinite draw or without a valid draw gives NaN."""
+        torch = _torch()
+        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
+            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        n_iter, _, size = store.shape
+        probs = np.atleast_1d(np.asarray(prob, dtype=np.float64))
+        if probs.ndim != 1 or not 1 <= probs.size <= 8:
+            raise ValueError("prob must be a number or a sequence of 1 to 8 numbers")
+        if not np.all((probs > 0) & (probs < 1)):
+            raise ValueError("every prob must lie inside (0, 1)")
+        idx, n = self._store_index(index, size)
+        lead = (probs.size,) if pooled else (probs.size, self.n_chains)
+        out = self.empty(*lead, n, 2)
+        cnt = torch.empty(lead[1:] + (n,), dtype=torch.int64, device=self.device)
+        host = (C.c_double * probs.size)(*probs.tolist())
+        check(lib.omc_store_hdi(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n, host, probs.size,
+                                int(not pooled), int(bool(omit_nan)), self._p(out), cnt.data_ptr()))
+        return out, cnt
+
     def store_thin(self, store, every, first=0):
         """store[first::every] of a device store (n_iter, C, ...) as a packed device tensor (one launch)."""
         if store.dim() < 2 or store.shape[1] != self.n_chains or not store.is_contiguous():
