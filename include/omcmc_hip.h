@@ -101,6 +101,8 @@ omc_status omc_ctx_synchronize(omc_ctx* ctx);
  * explicit setting holds for every chain count),
  * "diag_algo" (0 auto; 1 the short-series form of omc_store_rhat_ess, M <= 64; 2 its blocks of lags),
  * "hist_algo" (0 auto; 1 omc_store_histogram always finds the bin by bisection, also with evenly spaced edges: same counts),
+ * "reduce_algo" (0 auto; 1 omc_store_reduce takes the short-row form, rows staged in LDS, where a row fits; 2 always a wave per row:
+ * same results, SUM to rounding),
  * "hist2d_algo" (0 auto; bit 0: omc_store_histogram2d always takes the direct form, atomic adds to the output without counters in
  * LDS; bit 1: it always finds the bins by bisection; same counts either way),
  * "rank_tile" (0 = 8192, or a power of two 64 .. 8192: keys of an LDS tile of the sort behind omc_store_ranks; same results bit for
@@ -970,6 +972,41 @@ omc_status omc_store_rank_schedule(int64_t S, int32_t tile, int64_t* out, int64_
 omc_status omc_store_hdi(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                          const double* probs, int32_t n_probs, int32_t per_chain, int32_t omit_nan, double* out,
                          int64_t* n_valid_out);
+/* Per-draw reductions of the same store: one number per stored state (iteration, chain) over the selected elements of its row --
+ * np.nansum(MCMC.store[param], axis=0) and kin (np.nanmax, np.nanargmax, np.count_nonzero(x > t, axis=0) ...) on the reference's
+ * host arrays (mcmc.py:105-111): the field's maximum and where it sits, the area above a threshold, a contrast w'x, the live size
+ * and the total of a NaN-padded variable-size parameter, the maximal standardised deviation behind a simultaneous band.  The
+ * result is shaped like log_post, so every other summary of the store applies to it.
+ *   store, idx, n_idx and the NULL convention as omc_store_minmax (order kept, repeats allowed, n_idx may exceed size); an index
+ *   outside [0, size) is OMC_INVALID_ARG, found on the device before any output is written.  Selection position k = 0 .. n_idx - 1
+ *   is element idx[k] of the row (k itself without an index) with value x.
+ *   a, b      (device) [n_idx], aligned with the selection (position k), not with size; NULL where the op does not need them.
+ *   out       [n_iter][C] fp64;  count_out (may be NULL) [n_iter][C] int64: the selected elements of the row whose TERM is not NaN.
+ *     op                     term of position k                     result of the row
+ *     OMC_REDUCE_SUM         a[k] * x  (a == NULL: x)               the sum of the terms
+ *     OMC_REDUCE_MIN / MAX   x                                      the smallest / largest term
+ *     OMC_REDUCE_ARGMIN / ARGMAX  x                                 the position k (as a double) of the FIRST smallest / largest term
+ *     OMC_REDUCE_COUNT_ABOVE x                                      the number of positions with x > a[k]  (a required)
+ *     OMC_REDUCE_SUPNORM     fabs(x - a[k]) / b[k]                  the largest term  (a and b required; one IEEE subtraction and
+ *                                                                   one IEEE division per term: nothing fused, no reciprocal)
+ *   NaN terms (a NaN draw; 0 / 0 under SUPNORM for an element that never moved):
+ *     omit_nan != 0: they are left out.  A row without a term left gives 0 for SUM (np.nansum) and for COUNT_ABOVE, NaN otherwise.
+ *     omit_nan == 0: a NaN term makes SUM, MIN, MAX and SUPNORM NaN; ARGMIN / ARGMAX give the position of the first NaN term
+ *                    (numpy's rule); COUNT_ABOVE does not count it.
+ *   +-inf are ordinary values; -0.0 and +0.0 are equal (the first of them is the extreme).
+ *   OMC_INVALID_ARG, with a text in omc_last_error: an unknown op, a required vector that is NULL, n_iter < 1, size < 1.
+ * Everything but SUM is exact and does not depend on how the work is cut.  SUM adds the terms a lane owns in ascending position and
+ * the lanes in a fixed butterfly: |SUM - exact sum of the terms| <= n_idx 2^-53 sum |term| (products rounded or fused), and the order
+ * depends on the form, on (size, n_idx) and on the row's alignment to 16 bytes only: repeated calls are bit-equal.  No atomics.
+ * Two forms, option "reduce_algo" (0 automatic, 1 short, 2 long): long rows get one wave each (four from 32768 selected elements), 16-byte
+ * loads without an index, a gathered 8-byte load per lane with one; short rows (automatic: size <= 128) are staged, a tile of
+ * consecutive rows at a time, into LDS with 16-byte loads and reduced there by a power-of-two group of lanes per row.  A row
+ * that does not fit 48 KiB of LDS takes the long form whatever the option says.  One read of the store, 8 or 16 bytes written
+ * per row.  Runs on the context's stream; with an index the host reads one word back (the validation; workspace store_ws).        */
+enum { OMC_REDUCE_SUM = 0, OMC_REDUCE_MIN = 1, OMC_REDUCE_MAX = 2, OMC_REDUCE_ARGMIN = 3, OMC_REDUCE_ARGMAX = 4,
+       OMC_REDUCE_COUNT_ABOVE = 5, OMC_REDUCE_SUPNORM = 6 };
+omc_status omc_store_reduce(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                            int32_t op, int32_t omit_nan, const double* a, const double* b, double* out, int64_t* count_out);
 /* Thinned copy of the store for a thinned gather: out[j] = store[first + j * every] (slabs of C * size doubles),
  * j = 0 .. ceil((n_iter - first) / every) - 1 (that count is left in *n_out when n_out is not NULL, host).           */
 omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int64_t first, int64_t every,

@@ -84,6 +84,7 @@ struct omc_ctx {
   int band_algo;  // 0 auto, 1 lane-per-chain in one piece (narrow bands), 2 workgroup-per-chain
   int diag_algo;  // omc_store_rhat_ess: 0 auto, 1 short-series form (M <= 64), 2 blocks of lags
   int hist_algo;  // omc_store_histogram: 0 auto (arithmetic guess of the bin when the edges are evenly spaced), 1 always the bisection
+  int reduce_algo;  // omc_store_reduce: 0 auto, 1 short rows staged in LDS, 2 a wave per row
   int hist2d_algo;  // omc_store_histogram2d: bit 0 always the direct form (atomic adds to the output, no LDS counters), bit 1 always the bisection
   int rank_tile;  // omc_rank.hip: keys of an LDS tile of the sort, a power of two 64 .. 8192 (0: 8192)
   int64_t rank_chunk;  // omc_rank.hip: elements per chunk (0: what fits the workspace budget)

@@ -72,6 +72,7 @@ omc_status omc_ctx_create(int32_t device, int64_t n_chains, uint64_t seed, int64
   c->diag_algo = 0;
   c->hist_algo = 0;
   c->hist2d_algo = 0;
+  c->reduce_algo = 0;
   c->rank_tile = 0; c->rank_chunk = 0;
   c->band_algo = 0; c->band_seg_overlap = 192; c->band_seg_count = 0; c->band_blocked_threads = 0;
   if (c->own_stream) {
@@ -277,6 +278,11 @@ omc_status omc_ctx_set_option(omc_ctx* ctx, const char* name, int64_t value) {
   if (!strcmp(name, "hist_algo")) {
     if (value < 0 || value > 1) return OMC_INVALID_ARG;
     ctx->hist_algo = (int)value;
+    return OMC_OK;
+  }
+  if (!strcmp(name, "reduce_algo")) {
+    if (value < 0 || value > 2) return OMC_INVALID_ARG;
+    ctx->reduce_algo = (int)value;
     return OMC_OK;
   }
   if (!strcmp(name, "hist2d_algo")) {

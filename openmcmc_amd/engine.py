@@ -1429,6 +1429,50 @@ class Engine:
                                 int(not pooled), int(bool(omit_nan)), self._p(out), cnt.data_ptr()))
         return out, cnt
 
+    REDUCE_OPS = {"sum": 0, "min": 1, "max": 2, "argmin": 3, "argmax": 4, "count_above": 5, "supnorm": 6}
+
+    def _reduce_vector(self, v, n, what):
+        """device fp64 (n,) of a vector aligned with the selection: a host array or a device tensor, a scalar is broadcast"""
+        if v is None:
+            return None
+        torch = _torch()
+        if isinstance(v, torch.Tensor):
+            t = v.to(device=self.device, dtype=torch.float64)
+        else:  # (torch.tensor copies from the numpy array before it returns: no asynchronous read of a temporary)
+            t = torch.tensor(np.ascontiguousarray(v, dtype=np.float64), dtype=torch.float64, device=self.device)
+        if t.numel() == 1:
+            t = t.reshape(1).expand(n)
+        if t.dim() != 1 or t.shape[0] != n:
+            raise ValueError(f"{what} must be a scalar or hold one value per selected element ({n}), got shape {tuple(t.shape)}")
+        return t.contiguous()
+
+    def store_reduce(self, store, op, index=None, omit_nan=True, a=None, b=None):
+        """Per-draw reduction of a device store (n_iter, C, size) over the selected elements of every row, on the device
+        (omc_store_reduce): (out, count) as device tensors (n_iter, C), fp64 and int64 -- shaped like log_post.  op, with x the
+        element at selection position k: "sum" of a[k] * x (a=None: of x), "min" / "max" of x, "argmin" / "argmax" the position
+        in the selection of the first smallest / largest x, "count_above" the number with x > a[k], "supnorm" the largest
+        fabs(x - a[k]) / b[k].  count is the number of terms that are not NaN.  omit_nan leaves NaN terms out (np.nansum, np.nanmax,
+        ...; a row without a term gives 0 for "sum" and "count_above", NaN otherwise); without it a NaN term makes the result NaN,
+        "argmin" / "argmax" the position of the first NaN.  a, b: host arrays or device tensors with one value per SELECTED
+        element, scalars are broadcast.  "sum" is within n_idx 2^-53 sum|terms| of the exact sum, everything else is exact."""
+        torch = _torch()
+        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
+            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        code = self.REDUCE_OPS.get(op)
+        if code is None:
+            raise ValueError(f"unknown reduction {op!r}: one of {', '.join(self.REDUCE_OPS)}")
+        n_iter, _, size = store.shape
+        idx, n = self._store_index(index, size)
+        av, bv = self._reduce_vector(a, n, "a"), self._reduce_vector(b, n, "b")
+        out = self.empty(n_iter, self.n_chains)
+        cnt = torch.empty((n_iter, self.n_chains), dtype=torch.int64, device=self.device)
+        st = lib.omc_store_reduce(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n, code,
+                                  int(bool(omit_nan)), self._p(av), self._p(bv), self._p(out), cnt.data_ptr())
+        if st == _abi.INVALID_ARG:  # the library says which argument
+            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
+        check(st)
+        return out, cnt
+
     def store_thin(self, store, every, first=0):
         """store[first::every] of a device store (n_iter, C, ...) as a packed device tensor (one launch)."""
         if store.dim() < 2 or store.shape[1] != self.n_chains or not store.is_contiguous():

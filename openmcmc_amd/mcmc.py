@@ -85,6 +85,7 @@ class MCMC:
         self.store["log_post"] = eng.full((self._n_dev, C), float("nan"))
         self._fused = self._fusion_plan() if self.fuse else None
         self._sweeps_done = 0
+        self._derived = set()  # names of the store entries `derive` made
         if self.store_ring:
             self._drain = _RingDrain(self)
 
@@ -441,6 +442,74 @@ class MCMC:
                  for i in range(0, flat.size, 8)]  # at most 8 probabilities per call of omc_store_hdi
         out = np.concatenate(parts, axis=0)
         return out[0] if probs.ndim == 0 else out
+
+    def derive(self, key, reduce, index=None, weights=None, threshold=None, center=None, scale=None, omit_nan=True, name=None):
+        """A per-draw derived quantity of store[key], computed on the device (one read of the store, no gather): every stored
+        state (iteration, chain) is reduced over the selected elements of its row, as Stan's generated quantities are -- a
+        host array (n_iter, C), shaped like log_post.  reduce, with x the elements at the selected positions:
+        "sum" (np.nansum; with weights w the contrast or regional total sum of w[k] * x[k]), "mean" (np.nanmean: sum / count,
+        NaN where nothing is left), "count" (the elements that are not NaN: the live size of a variable-size parameter),
+        "min", "max", "argmin", "argmax" (the position in the selection of the first extreme), "count_above" (the number with
+        x[k] > threshold[k]: the area above a level), "supnorm" (the largest |x[k] - center[k]| / scale[k]; a term 0 / 0 counts as
+        NaN).  weights, threshold, center and scale are scalars or hold one value per SELECTED element.  index selects
+        elements (in that order, repeats allowed); a 2-D entry ("log_post") counts as one element.  omit_nan: NaN terms (the
+        padding of variable-size parameters) are left out; False propagates them like numpy's plain reductions ("argmin" /
+        "argmax" then give the first NaN).  "sum" and "mean" are within n 2^-53 sum|terms| of the exact sum, the rest is exact.
+        With name the device result is kept as store[name], shaped (n_iter, C, 1): `summary`, `quantiles`, `diagnostics`,
+        `rank_diagnostics`, `hdi`, `histogram` ... accept it as a key (R-hat and ESS of a derived quantity), and `collect()` /
+        `gather()` carry it as a scalar parameter (C, 1, n_iter).  A derived entry describes the store AT THE TIME OF THE CALL:
+        it is not updated by a later run.  A name may be derived again, but a name that is a store entry of the run raises
+        ValueError.  Under a sharded multi-GPU run every rank must derive the same names before `gather`."""
+        self._whole_store_on_device("derive")
+        if name is not None and name in self.store and name not in self._derived:
+            raise ValueError(f"{name!r} is a store entry of the run: choose another name for the derived quantity")
+        ops = {"sum": "sum", "mean": "sum", "count": "sum", "min": "min", "max": "max", "argmin": "argmin", "argmax": "argmax",
+               "count_above": "count_above", "supnorm": "supnorm"}
+        if reduce not in ops:
+            raise ValueError(f"unknown reduce {reduce!r}: one of {', '.join(ops)}")
+        takes = {"sum": ("weights",), "mean": ("weights",), "count_above": ("threshold",), "supnorm": ("center", "scale")}
+        given = {"weights": weights, "threshold": threshold, "center": center, "scale": scale}
+        for arg, v in given.items():
+            if v is not None and arg not in takes.get(reduce, ()):
+                raise ValueError(f"{arg} does not apply to reduce={reduce!r}")
+        a = {"sum": weights, "mean": weights, "count_above": threshold, "supnorm": center}.get(reduce)
+        out, cnt = self.engine.store_reduce(self._store_3d(key), ops[reduce], index=index, omit_nan=omit_nan, a=a, b=scale)
+        if reduce == "count":
+            out = cnt.to(out.dtype)
+        elif reduce == "mean":
+            out = out / cnt  # (0 / 0: NaN where no term is left)
+        if name is not None:
+            self.store[name] = out.unsqueeze(-1).contiguous()
+            self._derived.add(name)
+        return out.cpu().numpy()
+
+    def simultaneous_band(self, key, prob=0.95, index=None):
+        """A simultaneous credible band of the selected elements of store[key], computed on the device (two reads of the
+        store, no gather): a dict of host arrays "lower", "upper", "mean", "sd" of shape (n_idx,) and "critical" (a float).
+        The band of the maximal standardised deviation, as the simultaneous bands of Ruppert, Wand and Carroll
+        (Semiparametric Regression, 2003, section 6.5): with the pooled posterior mean and standard deviation (the root of
+        the unbiased variance) of every element, m = max_k |x[k] - mean[k]| / sd[k] is taken in every stored draw,
+        critical = np.quantile(m, prob) over all draws, and the band is mean -/+ critical * sd.  It holds WHOLE posterior curves
+        with probability prob: a share prob of the stored draws lies inside it at every selected element at once.  The
+        intervals of `hdi` and `quantiles` are pointwise -- each holds its own element's draws with probability prob -- and
+        drawn as a band they cover a whole curve far less often; critical is accordingly larger than the pointwise normal
+        quantile (1.96 at 0.95).  An element that never moved (sd = 0) or that holds a NaN draw (the padding of a
+        variable-size parameter) does not enter m and gets a degenerate or NaN band of its own.  index selects elements (in
+        that order, repeats allowed).  Under a sharded multi-GPU run this is the band of this rank's chains only."""
+        self._whole_store_on_device("simultaneous_band")
+        if not 0.0 < float(prob) < 1.0:
+            raise ValueError("prob must lie inside (0, 1)")
+        t = self._store_3d(key)
+        mean, var = self.engine.store_moments(t, pooled=True)
+        idx, _ = self.engine._store_index(index, t.shape[2])
+        if idx is not None:
+            if int(idx.min()) < 0 or int(idx.max()) >= t.shape[2]:
+                raise ValueError("index out of range")
+            mean, var = mean[idx], var[idx]
+        mean, sd = mean.cpu().numpy(), np.sqrt(var.cpu().numpy())  # (n_idx values: the root is numpy's, on the host)
+        m, _ = self.engine.store_reduce(t, "supnorm", index=idx, a=mean, b=sd, omit_nan=True)
+        critical = float(self.engine.store_quantiles(m.unsqueeze(-1).contiguous(), float(prob), pooled=True, omit_nan=True).cpu().numpy()[0, 0])
+        return {"lower": mean - critical * sd, "upper": mean + critical * sd, "mean": mean, "sd": sd, "critical": critical}
 
     def _store_3d(self, key):
         t = self.store[key]
