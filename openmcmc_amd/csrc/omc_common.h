@@ -31,7 +31,10 @@ struct omc_ctx {
   double* long_quad; size_t long_quad_bytes;  // ... and the sweep's quadratic forms [term][chain]
   double* workspace;       // scratch for the serial kernel (l vectors), grown on demand
   size_t workspace_bytes;
-  void* store_ws; size_t store_ws_bytes;  // omc_store.hip, omc_hist.hip: histograms / partial moments of the store summaries
+  // scratch of a store summary that is consumed before the call returns or the next summary starts: the word(s) of the index and
+  // edge checks (omc_store_shared.hip, omc_hist.hip), partial column moments (omc_store_shared.hip: omc_store_moments and
+  // omc_store_cov), radix histograms (omc_store.hip), partial minima / maxima (omc_hist.hip), lag sums and Geyer state (omc_diag.hip)
+  void* store_ws; size_t store_ws_bytes;
   double* cov_ws; size_t cov_ws_bytes;  // omc_cov.hip: means, variances and partial tiles of omc_store_cov
   void* rank_ws; size_t rank_ws_bytes;  // omc_rank.hip, omc_hdi.hip: keys, series and per-element words of a chunk (its own: it calls omc_store_rhat_ess, which uses store_ws)
   // dense path (omc_dense.hip): rocBLAS handle and workspaces, created on first use
@@ -119,8 +122,8 @@ omc_status omc_ensure_bytes(omc_ctx* ctx, void** buf, size_t* have, size_t need)
 omc_status omc_dgemm_wide(omc_ctx* ctx, int M, int N, const double* A, int64_t lda, const double* B, int64_t ldb, int K, int tri,
                           const double* addv, double* Cout, int64_t ldc);
 omc_status omc_ensure_aux(omc_ctx* ctx);  // side stream + its events and BLAS handle, made on first use (omc_dense.hip)
-omc_status omc_col_moments(omc_ctx* ctx, const double* data, int64_t R, int64_t K, double* mean_out, double* var_out);  // omc_store.hip
-// omc_hist.hip: got[0] = 1: an index outside [0, size), a NaN edge or a decreasing pair of edges; got[1] = 1: some row of edges is not evenly spaced
+// omc_hist.hip: one read-back for a selection and its edges.  got[0] = 1: an index outside [0, size), a NaN edge or a decreasing pair of
+// edges; got[1] = 1: some row of edges is not evenly spaced
 omc_status omc_hist_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64_t size, const double* edges, int64_t edge_rows, int n_bins,
                           int32_t got[2]);
 extern "C" omc_status omc_gram_mfma_launch(omc_ctx* ctx, int64_t n, int64_t p, const double* X, const double* w, double* G_out);  // omc_gram.hip  // destroys the rocBLAS handle if one was created

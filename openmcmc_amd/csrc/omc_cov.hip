@@ -5,8 +5,8 @@
 //   pooled:    one matrix over the R = n_iter C rows, row r at r * size;
 //   per chain: C matrices, chain c over its n_iter rows at (it * C + c) * size  -- "batch" b, row stride C * size.
 // out[b][i][j] = sum_r (a[r][ia_i] - ma_i)(b[r][ib_j] - mb_j) / (rows - 1), two passes:
-//   1. means (and variances, for the correlation) of the selected columns: omc_col_moments when every column takes part,
-//      k_cov_means_* (the same Chan combination over row slices, gathered columns) under an index;
+//   1. means (and variances, for the correlation) of the selected columns: omc_col_moments (omc_store_shared.hip), the pass
+//      behind omc_store_moments, with or without an index;
 //   2. k_cov_mfma: the tiling of k_gram_mfma (omc_gram.hip: 128 x 128 output tile per workgroup, 4 waves in 2 x 2 of
 //      64 x 64 = 4 x 4 MFMA tiles, 128 accumulator registers; slab of 16 rows x 128 columns per panel, the next one fetched
 //      into registers under the multiplications; LDS row stride 128 + 16), with these differences:
@@ -27,18 +27,17 @@
 //      mirrors the lower triangle in the symmetric form.
 // NaN needs no code: a NaN draw makes its column's mean NaN, so every centred value of the column, so its row / column.
 #include "omc_common.h"
+#include "omc_store_view.h"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
 #define CV_TS 128  // output tile
 #define CV_BK 16   // rows per slab
 #define CV_LD (CV_TS + 16)
-#define CV_MC 16   // k_cov_means_part: columns and row lanes of a workgroup
-#define CV_MR 16
 
 namespace {
 
-// one operand: rows of a store and the columns of it that take part
+// one operand: rows of a store and the columns of it that take part (the fields of its StoreView, and the means)
 struct CovSide {
   const double* data;
   const int64_t* idx;  // [n] or NULL
@@ -46,66 +45,6 @@ struct CovSide {
   int64_t row_stride, batch_stride;
   int n;
 };
-
-__global__ void k_cov_check_index(const int64_t* __restrict__ idx, int64_t n, int64_t size, int32_t* __restrict__ bad) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < n && (idx[j] < 0 || idx[j] >= size)) *bad = 1;
-}
-
-// moments of the selected columns of every batch over row slices: part [slices][batches][3][n] (count, mean, m2)
-__global__ void __launch_bounds__(256) k_cov_means_part(const double* __restrict__ data, int64_t row_stride, int64_t batch_stride,
-                                                        int64_t R, const int64_t* __restrict__ idx, int64_t n, int64_t tiles,
-                                                        int64_t rows_per_block, double* __restrict__ part) {
-  __shared__ double sm[3][CV_MR][CV_MC];
-  const int tid = threadIdx.x, col = tid & (CV_MC - 1), rr = tid >> 4;
-  const int64_t batch = blockIdx.x / tiles, tile = blockIdx.x - batch * tiles, batches = gridDim.x / tiles;
-  const int64_t j = tile * CV_MC + col;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-  const int64_t r1 = (r0 + rows_per_block < R) ? r0 + rows_per_block : R;
-  double cnt = 0.0, mean = 0.0, m2 = 0.0;
-  if (j < n) {
-    const double* p = data + batch * batch_stride + idx[j];
-    for (int64_t r = r0 + rr; r < r1; r += CV_MR) {
-      const double v = p[r * row_stride];
-      cnt += 1.0;
-      const double d = v - mean;
-      mean += d / cnt;
-      m2 = fma(d, v - mean, m2);
-    }
-  }
-  sm[0][rr][col] = cnt; sm[1][rr][col] = mean; sm[2][rr][col] = m2;
-  __syncthreads();
-  if (rr == 0 && j < n) {
-    for (int q = 1; q < CV_MR; ++q) {
-      const double cb = sm[0][q][col], mb = sm[1][q][col], qb = sm[2][q][col];
-      if (cb == 0.0) continue;
-      const double tot = cnt + cb, d = mb - mean;
-      mean += d * (cb / tot);
-      m2 += qb + d * d * (cnt * cb / tot);
-      cnt = tot;
-    }
-    double* o = part + ((int64_t)blockIdx.y * batches + batch) * 3 * n;
-    o[j] = cnt; o[n + j] = mean; o[2 * n + j] = m2;
-  }
-}
-__global__ void k_cov_means_join(int64_t batches, int64_t n, int slices, const double* __restrict__ part, double* __restrict__ mean_out,
-                                 double* __restrict__ var_out) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= batches * n) return;
-  const int64_t batch = e / n, j = e - batch * n;
-  double cnt = 0.0, mean = 0.0, m2 = 0.0;
-  for (int s = 0; s < slices; ++s) {
-    const double* o = part + ((int64_t)s * batches + batch) * 3 * n;
-    const double cb = o[j], mb = o[n + j], qb = o[2 * n + j];
-    if (cb == 0.0) continue;
-    const double tot = cnt + cb, d = mb - mean;
-    mean += d * (cb / tot);
-    m2 += qb + d * d * (cnt * cb / tot);
-    cnt = tot;
-  }
-  mean_out[e] = mean;
-  var_out[e] = cnt > 1.0 ? m2 / (cnt - 1.0) : 0.0;
-}
 
 // partial tile of one (batch, tile, slice): part[slice][batch][i][j] = sum over the slice's rows of centred a_i b_j
 __global__ void __launch_bounds__(256, 2) k_cov_mfma(int64_t R, CovSide sa, CovSide sb, int symmetric, int tiles_b, int pairs,
@@ -234,31 +173,6 @@ __global__ void __launch_bounds__(256) k_cov_join(int64_t batches, int n_a, int 
   }
 }
 
-// row slices of an indexed means pass: about 2048 workgroups, no slice shorter than 256 rows (a function of the shape only)
-int64_t cov_means_slices(int64_t n, int64_t batches, int64_t R) {
-  const int64_t groups = (n + CV_MC - 1) / CV_MC * batches;
-  int64_t slices = (2048 + groups - 1) / groups;
-  if (slices > (R + 255) / 256) slices = (R + 255) / 256;
-  if (slices < 1) slices = 1;
-  if (slices > 1024) slices = 1024;
-  return slices;
-}
-// means and variances [batches][n] of one side's selected columns; scratch [slices][batches][3][n] under an index
-omc_status cov_moments(omc_ctx* ctx, const double* store, int64_t n_iter, int64_t size, const int64_t* idx, int64_t n, bool pooled,
-                       double* scratch, double* mean, double* var) {
-  const int64_t C = ctx->n_chains;
-  const int64_t R = pooled ? n_iter * C : n_iter, batches = pooled ? 1 : C;
-  if (!idx) return omc_col_moments(ctx, store, R, batches * size, mean, var);
-  const int64_t tiles = (n + CV_MC - 1) / CV_MC, slices = cov_means_slices(n, batches, R);
-  const int64_t rpb = (R + slices - 1) / slices;
-  hipLaunchKernelGGL(k_cov_means_part, dim3((unsigned)(tiles * batches), (unsigned)slices), dim3(256), 0, ctx->stream, store,
-                     pooled ? size : C * size, size, R, idx, n, tiles, rpb, scratch);
-  hipLaunchKernelGGL(k_cov_means_join, dim3((unsigned)((batches * n + 255) / 256)), dim3(256), 0, ctx->stream, batches, n, (int)slices,
-                     scratch, mean, var);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
-}
-
 }  // namespace
 
 extern "C" omc_status omc_store_cov(omc_ctx* ctx, int64_t n_iter, int64_t size_a, const double* store_a, const int64_t* idx_a,
@@ -268,8 +182,9 @@ extern "C" omc_status omc_store_cov(omc_ctx* ctx, int64_t n_iter, int64_t size_a
   const bool symmetric = store_b == nullptr;
   if (symmetric) { store_b = store_a; size_b = size_a; idx_b = idx_a; n_b = n_a; }
   if (size_b < 1 || n_b < 1 || (!idx_a && n_a != size_a) || (!idx_b && n_b != size_b)) return OMC_INVALID_ARG;
-  const int64_t C = ctx->n_chains;
-  const int64_t R = pooled ? n_iter * C : n_iter, batches = pooled ? 1 : C;
+  const StoreView va = omc_store_view(ctx, n_iter, size_a, pooled != 0, store_a, idx_a, n_a);
+  const StoreView vb = omc_store_view(ctx, n_iter, size_b, pooled != 0, store_b, idx_b, n_b);
+  const int64_t R = va.R, batches = va.batches;
   const int64_t ta = (n_a + CV_TS - 1) / CV_TS, tb = (n_b + CV_TS - 1) / CV_TS;
   const int64_t pairs = symmetric ? ta * (ta + 1) / 2 : ta * tb;
   if (n_a > 0x7fffffffLL || n_b > 0x7fffffffLL || pairs * batches > 0x7fffffffLL) return OMC_INVALID_ARG;
@@ -285,13 +200,8 @@ extern "C" omc_status omc_store_cov(omc_ctx* ctx, int64_t n_iter, int64_t size_a
   kchunk = (kchunk + CV_BK - 1) / CV_BK * CV_BK;
   splits = (R + kchunk - 1) / kchunk;
   // workspace: means and variances of both sides, the word of the index check, then the partial tiles [splits][batches][n_a][n_b]
-  // -- the partial moments of an indexed means pass lie in the same place: they are consumed before the first tile is written
   const size_t n_ma = (size_t)batches * n_a, n_mb = symmetric ? 0 : (size_t)batches * n_b;
-  size_t n_part = (size_t)splits * batches * n_a * n_b;
-  const size_t n_sa = idx_a ? (size_t)cov_means_slices(n_a, batches, R) * batches * 3 * n_a : 0;
-  const size_t n_sb = idx_b ? (size_t)cov_means_slices(n_b, batches, R) * batches * 3 * n_b : 0;
-  if (n_sa > n_part) n_part = n_sa;
-  if (n_sb > n_part) n_part = n_sb;
+  const size_t n_part = (size_t)splits * batches * n_a * n_b;
   omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->cov_ws, &ctx->cov_ws_bytes, (2 * n_ma + 2 * n_mb + 1 + n_part) * sizeof(double));
   if (st != OMC_OK) return st;
   double* mean_a = ctx->cov_ws;
@@ -301,25 +211,17 @@ extern "C" omc_status omc_store_cov(omc_ctx* ctx, int64_t n_iter, int64_t size_a
   int32_t* bad = (int32_t*)(var_a + n_ma + 2 * n_mb);
   double* part = (double*)bad + 1;
 
-  if (idx_a || (idx_b && !symmetric)) {  // an index outside the store is found before anything reads through it
-    OMC_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int32_t), s));
-    if (idx_a) hipLaunchKernelGGL(k_cov_check_index, dim3((unsigned)((n_a + 255) / 256)), dim3(256), 0, s, idx_a, n_a, size_a, bad);
-    if (idx_b && !symmetric)
-      hipLaunchKernelGGL(k_cov_check_index, dim3((unsigned)((n_b + 255) / 256)), dim3(256), 0, s, idx_b, n_b, size_b, bad);
-    OMC_HIP_CHECK(hipGetLastError());
-    int32_t any = 0;
-    OMC_HIP_CHECK(hipMemcpyAsync(&any, bad, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    OMC_HIP_CHECK(hipStreamSynchronize(s));
-    if (any) return OMC_INVALID_ARG;
-  }
-  st = cov_moments(ctx, store_a, n_iter, size_a, idx_a, n_a, pooled != 0, part, mean_a, var_a);
+  // an index outside the store is found before anything reads through it: one read-back for both sides
+  st = omc_store_check_index(ctx, bad, idx_a, n_a, size_a, symmetric ? nullptr : idx_b, n_b, size_b);
+  if (st != OMC_OK) return st;
+  st = omc_col_moments(ctx, va, mean_a, var_a);
   if (st != OMC_OK) return st;
   if (!symmetric) {
-    st = cov_moments(ctx, store_b, n_iter, size_b, idx_b, n_b, pooled != 0, part, mean_b, var_b);
+    st = omc_col_moments(ctx, vb, mean_b, var_b);
     if (st != OMC_OK) return st;
   }
-  const CovSide sa = {store_a, idx_a, mean_a, pooled ? size_a : C * size_a, pooled ? 0 : size_a, (int)n_a};
-  const CovSide sb = {store_b, idx_b, mean_b, pooled ? size_b : C * size_b, pooled ? 0 : size_b, (int)n_b};
+  const CovSide sa = {va.data, va.idx, mean_a, va.row_stride, va.batch_stride, (int)va.n};
+  const CovSide sb = {vb.data, vb.idx, mean_b, vb.row_stride, vb.batch_stride, (int)vb.n};
   hipLaunchKernelGGL(k_cov_mfma, dim3((unsigned)(pairs * batches), (unsigned)splits), dim3(256), 0, s, R, sa, sb, (int)symmetric, (int)tb,
                      (int)pairs, kchunk, part);
   OMC_HIP_CHECK(hipGetLastError());

@@ -8,7 +8,7 @@
 //   rho(t) = 1 - (W - S(t) / (J M)) / var_plus, and Geyer's initial monotone sequence on rho for the ESS.
 //
 // Series means are taken around the series' first draw (m = x[0] + mean(x - x[0])), and the variance of the means by
-// Welford / Chan updates: a constant series then has deviations of exactly zero, equal means a variance of exactly zero, so
+// Welford / Chan updates (omc_moments.h): a constant series then has deviations of exactly zero, equal means a variance of exactly zero, so
 // the edge cases of the contract (every draw equal; W == 0 < B_M) are exact tests, not tolerances.
 //
 // Lag sums, one lane per (series, element), consecutive lanes on consecutive elements (every row load a coalesced run of
@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "omc_common.h"
+#include "omc_moments.h"
 
 namespace {
 
@@ -53,21 +54,6 @@ __device__ __forceinline__ void d_lag_block(int64_t t0, int64_t M, F y, double (
       for (int l = 0; l < L; ++l) acc[l] = fma(a, ring[(u - l + L) % L], acc[l]);
     }
   }
-}
-
-// Welford update and Chan combination of (count, mean, m2): exact for equal values (the mean stays, m2 stays 0)
-__device__ __forceinline__ void d_welford(double& n, double& mean, double& m2, double v) {
-  n += 1.0;
-  const double d = v - mean;
-  mean += d / n;
-  m2 = fma(d, v - mean, m2);
-}
-__device__ __forceinline__ void d_chan(double& n, double& mean, double& m2, double nb, double mb, double qb) {
-  if (nb == 0.0) return;
-  const double tot = n + nb, d = mb - mean;
-  mean += d * (nb / tot);
-  m2 += qb + d * d * (n * nb / tot);
-  n = tot;
 }
 
 // Long form, pass 1: the two split means of every (chain, element); the middle draw of an odd N only for its NaN.
@@ -124,7 +110,7 @@ __global__ void __launch_bounds__(256) k_diag_lags(const double* __restrict__ st
     const double m = means[s * size + kc];
     const double* q = store + (s >> 1) * size + kc + ((s & 1) ? N - M : 0) * row;
     d_lag_block<L>(t0, M, [&](int64_t i) { return q[i * row] - m; }, acc);
-    if (t0 == 0) d_welford(bn, bm, bq, m);
+    if (t0 == 0) omc_welford(bn, bm, bq, m);
   }
   // the four waves' sums in a fixed order: ((w3 + w2) + w1) + w0
   for (int w = 3; w >= 0; --w) {
@@ -136,7 +122,7 @@ __global__ void __launch_bounds__(256) k_diag_lags(const double* __restrict__ st
         else if (k < size) part[((int64_t)g * L + l) * size + k] = v;
       }
       if (t0 == 0) {
-        if (w < 3) d_chan(bn, bm, bq, redb[0][lane], redb[1][lane], redb[2][lane]);
+        if (w < 3) omc_chan(bn, bm, bq, redb[0][lane], redb[1][lane], redb[2][lane]);
         if (w > 0) {
           redb[0][lane] = bn; redb[1][lane] = bm; redb[2][lane] = bq;
         } else if (k < size) {
@@ -183,7 +169,7 @@ __global__ void __launch_bounds__(512) k_diag_short(const double* __restrict__ s
     double m = x0 + s / (double)M;
     if (mid[lane] != mid[lane]) m = mid[lane];
     d_lag_block<S_L>(S_L * blk, M, [&](int64_t i) { return xh[i * D_TILE] - m; }, acc);
-    if (blk == 0) d_welford(bn, bm, bq, m);
+    if (blk == 0) omc_welford(bn, bm, bq, m);
     __syncthreads();
   }
   // lag 16 blk + l: half 0 (wave blk) + half 1 (wave 4 + blk); moments of the means: wave 0, then wave 4
@@ -198,7 +184,7 @@ __global__ void __launch_bounds__(512) k_diag_short(const double* __restrict__ s
 #pragma unroll
     for (int l = 0; l < S_L; ++l) part[((int64_t)g * D_SHORT + blk * S_L + l) * size + k] = acc[l] + red[(blk * S_L + l) * D_TILE + lane];
     if (blk == 0) {
-      d_chan(bn, bm, bq, redb[0][lane], redb[1][lane], redb[2][lane]);
+      omc_chan(bn, bm, bq, redb[0][lane], redb[1][lane], redb[2][lane]);
       double* o = part_b + (int64_t)g * 3 * size;
       o[k] = bn; o[size + k] = bm; o[2 * size + k] = bq;
     }
@@ -236,7 +222,7 @@ __global__ void __launch_bounds__(64) k_diag_step(int64_t size, int64_t M, int64
       double bn = 0.0, bm = 0.0, bq = 0.0;
       for (int gg = 0; gg < G; ++gg) {
         const double* o = part_b + (int64_t)gg * 3 * size;
-        d_chan(bn, bm, bq, o[k], o[size + k], o[2 * size + k]);
+        omc_chan(bn, bm, bq, o[k], o[size + k], o[2 * size + k]);
       }
       const double BM = bq / (double)(J - 1);
       const double S0 = S(0);

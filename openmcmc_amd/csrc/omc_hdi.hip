@@ -4,13 +4,10 @@
 // store is [N][C][size].  A column is all N C draws of an element (pooled, S = N C) or the N draws of one chain of it (per
 // chain, S = N, CC = C columns per element).  A chunk of Kc selected elements, Kc CC columns, is worked on at a time; column
 // q = c Kc + e of the chunk belongs to chain c (0 when pooled) of element e:
-//   k_hdi_gather   reads the draws where they lie (16 adjacent elements of a row per 128 bytes), turns them into the
-//                  order-preserving keys of omc_rank_sort.h and writes them, transposed through LDS, into columns keys [Kc CC][P],
-//                  P the next power of two >= S.  A NaN draw takes the all-ones key, which is also the padding: both sort behind
-//                  every number.  It notes per column whether a NaN (bit 0) or an infinity (bit 1) was seen, gathered in LDS
-//                  first: one atomic per workgroup and element.
-//   k_rank_sort_tile / k_rank_sort_global
-//                  the key-only bitonic sort of every column (omc_rank_sort.h, shared with omc_rank.hip).
+//   k_hdi_gather   the gather tile of omc_rank_sort.h: the draws, read where they lie, as order-preserving keys in columns
+//                  keys [Kc CC][P], P the next power of two >= S.  A NaN draw takes the all-ones key, which is also the padding:
+//                  both sort behind every number.  It notes per column whether a NaN (bit 0) or an infinity (bit 1) was seen.
+//   rank_sort      the key-only bitonic sort of every column (omc_store_shared.hip, shared with omc_rank.hip).
 //   k_hdi_count    n = the keys of a sorted column below the all-ones key, by bisection: the draws that are not NaN.
 //   k_hdi_window   for every probability of the call m = min(floor(prob n), n - 1) and the minimum over i = 0 .. n - m - 1 of
 //                  (w, i), w = x[i + m] - x[i], in lexicographic order.  w >= 0 (or NaN in a column with an infinity, whose
@@ -29,10 +26,10 @@
 #include "omc_common.h"
 #include "omc_quantile.h"
 #include "omc_rank_sort.h"
+#include "omc_store_view.h"
 
 namespace {
 
-constexpr int H_TE = 16, H_TS = 64;       // k_hdi_gather: elements x draws of a workgroup's tile
 constexpr int HDI_PROBS = 8;              // probabilities of a call at most
 constexpr int64_t HDI_SMALL = 4096;       // columns up to this many draws: one wave
 constexpr int64_t HDI_SLICE = 16384;      // windows of a slice of a longer column
@@ -43,45 +40,9 @@ constexpr int64_t HDI_NONE = 0x7fffffffffffffffLL;  // the index of "no window"
 __global__ void __launch_bounds__(256) k_hdi_gather(const double* __restrict__ store, const int64_t* __restrict__ idx, int64_t k0, int64_t Kc,
                                                     int64_t size, int64_t rstride, int64_t S, int64_t P, int64_t n_st, int64_t n_et,
                                                     uint64_t* __restrict__ keys, int32_t* __restrict__ flags) {
-  __shared__ uint64_t tile[H_TE][H_TS + 1];
-  __shared__ int32_t seen[H_TE];
-  const int tid = threadIdx.x, e_l = tid & (H_TE - 1), d_l = tid / H_TE;
   const int64_t b = blockIdx.x, rest = b / n_st, c = rest / n_et;
-  const int64_t e0 = (rest % n_et) * H_TE, s0 = (b % n_st) * H_TS;
-  const int64_t e = e0 + e_l;
-  const bool live = e < Kc;
-  const int64_t col = live ? (idx ? idx[k0 + e] : k0 + e) : 0;
-  const double inf = __longlong_as_double(0x7ff0000000000000LL);
-  if (tid < H_TE) seen[tid] = 0;
-  __syncthreads();
-  int32_t bits = 0;
-  double v[H_TS / (256 / H_TE)];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int64_t s = s0 + d_l + 16 * u;
-    v[u] = (live && s < S) ? store[(s * rstride + c) * size + col] : 0.0;
-  }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int64_t s = s0 + d_l + 16 * u;
-    uint64_t key = ~0ull;
-    if (live && s < S) {
-      const double x = v[u];
-      if (x != x) bits |= 1;
-      else if (fabs(x) == inf) bits |= 2;
-      key = rank_key(x);
-    }
-    tile[e_l][d_l + 16 * u] = key;
-  }
-  if (bits) atomicOr(&seen[e_l], bits);
-  __syncthreads();
-  if (tid < H_TE && e0 + tid < Kc && seen[tid]) atomicOr(&flags[c * Kc + e0 + tid], seen[tid]);
-  const int s_l = tid & (H_TS - 1);
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int el = (tid >> 6) + 4 * u;
-    if (e0 + el < Kc && s0 + s_l < P) keys[(c * Kc + e0 + el) * P + s0 + s_l] = tile[el][s_l];
-  }
+  rank_gather_tile(store, idx, k0, Kc, size, S, P, (rest % n_et) * RANK_G_TE, (b % n_st) * RANK_G_TS, c * Kc,
+                   [=](int64_t s) { return s * rstride + c; }, [](double x) { return x; }, 0, keys, flags);
 }
 
 // n_valid [n_col]: the keys of each sorted column that are not the all-ones key
@@ -220,7 +181,7 @@ extern "C" omc_status omc_store_hdi(omc_ctx* ctx, int64_t n_iter, int64_t size, 
   const size_t per_col = (size_t)P * sizeof(uint64_t) + sizeof(int64_t) + (n_slices > 1 ? (size_t)n_slices * HDI_PROBS * 16 : 0) + sizeof(int32_t);
   const int64_t Kc = rank_chunk(ctx, per_col * (size_t)CC, n_idx);
   const int64_t n_col_max = Kc * CC;
-  const int64_t n_st = (P + H_TS - 1) / H_TS, n_et_max = (Kc + H_TE - 1) / H_TE;
+  const int64_t n_st = (P + RANK_G_TS - 1) / RANK_G_TS, n_et_max = (Kc + RANK_G_TE - 1) / RANK_G_TE;
   if (n_st * n_et_max * CC > 0x7fffffffLL || n_col_max * n_slices > 0x7fffffffLL) return OMC_INVALID_ARG;
   omc_status st = omc_ensure_bytes(ctx, &ctx->rank_ws, &ctx->rank_ws_bytes, RANK_HEAD + (size_t)n_col_max * per_col + 64);
   if (st != OMC_OK) return st;
@@ -229,7 +190,7 @@ extern "C" omc_status omc_store_hdi(omc_ctx* ctx, int64_t n_iter, int64_t size, 
   int64_t* n_valid = (int64_t*)(keys + (size_t)n_col_max * P);
   uint64_t* part = (uint64_t*)(n_valid + n_col_max);
   int32_t* flags = (int32_t*)(part + (n_slices > 1 ? (size_t)n_col_max * n_slices * HDI_PROBS * 2 : 0));
-  st = rank_check(ctx, idx, n_idx, size, (int32_t*)ws);
+  st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size);
   if (st != OMC_OK) return st;
   hipStream_t s = ctx->stream;
   HdiArgs a;
@@ -238,7 +199,7 @@ extern "C" omc_status omc_store_hdi(omc_ctx* ctx, int64_t n_iter, int64_t size, 
   a.n_probs = n_probs; a.omit_nan = omit_nan != 0;
   for (int p = 0; p < HDI_PROBS; ++p) a.probs[p] = p < n_probs ? probs[p] : 0.0;
   for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {
-    const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc, n_col = kc * CC, n_et = (kc + H_TE - 1) / H_TE;
+    const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc, n_col = kc * CC, n_et = (kc + RANK_G_TE - 1) / RANK_G_TE;
     OMC_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)n_col * sizeof(int32_t), s));
     hipLaunchKernelGGL(k_hdi_gather, dim3((unsigned)(n_st * n_et * CC)), dim3(256), 0, s, store, idx, k0, kc, size, per_chain ? C : (int64_t)1,
                        S, P, n_st, n_et, keys, flags);

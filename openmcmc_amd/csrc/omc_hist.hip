@@ -1,23 +1,22 @@
 // Marginal histograms, ranges and counts of the device store: one read of the store, integer results.
 //
 // What it replaces: np.histogram / np.nanmin / np.nanmax on MCMC.store[param] of the reference (host arrays there: mcmc.py:105-111);
-// here the store stays on the device and is read where it lies: store [n_iter][C][size], seen as rows of draws, as omc_cov.hip
-// sees it:
-//   pooled:    one set of rows, R = n_iter C, row r at r * size;
-//   per chain: C batches, chain c over its n_iter rows at (it * C + c) * size.
+// here the store stays on the device and is read where it lies: store [n_iter][C][size], seen as rows of draws through a
+// StoreView (omc_store_view.h): one set of R = n_iter C rows pooled, C batches of n_iter rows per chain.
 // k_hist_count: a workgroup owns a tile of TE consecutive selected elements (lanes along the elements: a wave reads 512
 //   contiguous bytes of a row when TE = 64; under an index the column offset is read once per thread) and walks slices of RB
-//   rows.  Every lane finds its value's bin by comparisons with the edges in LDS -- a bisection, or with evenly spaced edges an
-//   arithmetic guess put right by the same comparisons -- and adds one to a 32-bit LDS counter.  At the end the non-zero
+//   rows.  Every lane finds its value's bin by comparisons with the edges in LDS (hist_bin, omc_hist_layout.h) and adds one to a
+//   32-bit LDS counter.  At the end the non-zero
 //   counters go to the zeroed int64 output with 64-bit integer atomic adds from the vector lanes, consecutive bins on
 //   consecutive lanes.  Integer addition commutes: the result does not depend on the order of arrival, nor on the form.
 //   The LDS image and TE, RB come from hist_layout() (omc_hist_layout.h), on both sides.
 // k_hist_minmax_part / _join: the same tiling without counters: per-lane running minimum, maximum and count of the non-NaN
 //   draws, an LDS reduction over the row lanes, per-slice partials joined in slice order.
-// k_hist_check: index range, NaN or decreasing edges, and whether every row of edges is evenly spaced; two words the host
-//   reads back before anything is written.
+// k_hist_check: NaN or decreasing edges, and whether every row of edges is evenly spaced; two words the host reads back, with
+//   the verdict of the index check (omc_store_shared.hip) in the first, before anything is written.
 #include "omc_common.h"
 #include "omc_hist_layout.h"
+#include "omc_store_view.h"
 
 #define HIST_MM_RB 1024     // k_hist_minmax_part: rows of a slice
 #define HIST_MM_SLICES 1024  // ... and the most partials of a column
@@ -26,7 +25,7 @@
 namespace {
 
 struct HistArgs {
-  const double* data;
+  const double* data;   // the fields of the store's StoreView
   const int64_t* idx;   // [n_idx] or NULL
   const double* edges;  // [n_bins + 1] or [n_idx][n_bins + 1]
   int64_t* counts;      // [batches][n_idx][n_bins], zeroed
@@ -35,13 +34,11 @@ struct HistArgs {
   int n_bins;
 };
 
-// words[0] = 1: an index outside [0, size), a NaN edge or a decreasing pair; words[1] = 1: some row of edges is not evenly spaced
-// (each edge within a quarter of a bin of e0 + j (eN - e0) / n_bins, eN > e0 finite)
-__global__ void k_hist_check(const int64_t* __restrict__ idx, int64_t n_idx, int64_t size, const double* __restrict__ edges,
-                             int64_t edge_rows, int n_bins, int32_t* __restrict__ words) {
+// words[0] = 1: a NaN edge or a decreasing pair; words[1] = 1: some row of edges is not evenly spaced (each edge within a quarter
+// of a bin of e0 + j (eN - e0) / n_bins, eN > e0 finite)
+__global__ void k_hist_check(const double* __restrict__ edges, int64_t edge_rows, int n_bins, int32_t* __restrict__ words) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx && t < n_idx && (idx[t] < 0 || idx[t] >= size)) words[0] = 1;
-  if (!edges || t >= edge_rows * (n_bins + 1)) return;
+  if (t >= edge_rows * (n_bins + 1)) return;
   const int64_t row = t / (n_bins + 1);
   const int j = (int)(t - row * (n_bins + 1));
   const double* E = edges + row * (n_bins + 1);
@@ -88,22 +85,7 @@ __global__ void __launch_bounds__(HIST_THREADS) k_hist_count(HistArgs a) {
       if (v != v) { ++nans; return; }
       if (v < e0) { ++below; return; }
       if (v > eN) { ++above; return; }
-      // the last j in [0, nb) with edges[j] <= v: np.searchsorted(edges, v, 'right') - 1 with the last bin closed
-      int j;
-      if (UNIFORM) {
-        const double t = (v - e0) * scale;
-        j = t >= (double)nb ? nb - 1 : (int)t;
-        while (j > 0 && v < myE[j]) --j;
-        while (j < nb - 1 && v >= myE[j + 1]) ++j;
-      } else {
-        int lo = 0, hi = nb - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (myE[mid] <= v) lo = mid; else hi = mid - 1;
-        }
-        j = lo;
-      }
-      atomicAdd(&myC[j], 1u);
+      atomicAdd(&myC[hist_bin<UNIFORM>(myE, nb, e0, scale, v)], 1u);
     };
     for (int64_t slice = blockIdx.y; slice < a.slices; slice += gridDim.y) {
       const int64_t r0 = slice * L.RB;
@@ -140,11 +122,10 @@ __global__ void __launch_bounds__(HIST_THREADS) k_hist_count(HistArgs a) {
 
 // minimum, maximum and count of the non-NaN draws of the selected columns over slices of rows.  direct: one partial per column,
 // written to the outputs as they are defined (NaN, NaN, 0 without a draw); else part [3][gridDim.y][batches n_idx].
-__global__ void __launch_bounds__(HIST_THREADS) k_hist_minmax_part(const double* __restrict__ data, const int64_t* __restrict__ idx,
-                                                                   int64_t row_stride, int64_t batch_stride, int64_t R, int64_t n_idx,
-                                                                   int64_t tiles, int64_t slices, int direct, double* __restrict__ part,
-                                                                   double* __restrict__ min_out, double* __restrict__ max_out,
-                                                                   int64_t* __restrict__ count_out) {
+__global__ void __launch_bounds__(HIST_THREADS) k_hist_minmax_part(StoreView view, int64_t tiles, int64_t slices, int direct,
+                                                                   double* __restrict__ part, double* __restrict__ min_out,
+                                                                   double* __restrict__ max_out, int64_t* __restrict__ count_out) {
+  const int64_t row_stride = view.row_stride, R = view.R, n_idx = view.n;
   __shared__ double smn[HIST_MM_RL][HIST_TE_MAX], smx[HIST_MM_RL][HIST_TE_MAX];
   __shared__ int64_t scn[HIST_MM_RL][HIST_TE_MAX];
   const int tid = threadIdx.x, e = tid & (HIST_TE_MAX - 1), rl = tid / HIST_TE_MAX;
@@ -154,7 +135,7 @@ __global__ void __launch_bounds__(HIST_THREADS) k_hist_minmax_part(const double*
   double mn = inf, mx = -inf;
   int64_t cnt = 0;
   if (elem < n_idx) {
-    const double* p = data + batch * batch_stride + (idx ? idx[elem] : elem);
+    const double* p = view.column(batch, elem);
     for (int64_t slice = blockIdx.y; slice < slices; slice += gridDim.y) {
       const int64_t r0 = slice * HIST_MM_RB;
       const int64_t r1 = (r0 + HIST_MM_RB < R) ? r0 + HIST_MM_RB : R;
@@ -213,19 +194,17 @@ __global__ void k_hist_minmax_join(int64_t cols, int parts, const double* __rest
 
 }  // namespace
 
-// the two words of k_hist_check, read back: the launches behind it write nothing before the host has seen them (also omc_hist2d.hip)
+// the index check and k_hist_check on the same two words, read back once: the launches behind it write nothing before the host has
+// seen them (also omc_hist2d.hip)
 omc_status omc_hist_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64_t size, const double* edges, int64_t edge_rows, int n_bins,
                           int32_t got[2]) {
-  got[0] = got[1] = 0;
-  if (!idx && !edges) return OMC_OK;
   omc_status st = omc_ensure_bytes(ctx, &ctx->store_ws, &ctx->store_ws_bytes, 64);
   if (st != OMC_OK) return st;
   int32_t* words = (int32_t*)ctx->store_ws;
   OMC_HIP_CHECK(hipMemsetAsync(words, 0, 2 * sizeof(int32_t), ctx->stream));
-  int64_t n = edges ? edge_rows * (n_bins + 1) : 0;
-  if (idx && n_idx > n) n = n_idx;
-  hipLaunchKernelGGL(k_hist_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, idx, n_idx, size, edges, edge_rows,
-                     n_bins, words);
+  omc_store_check_index_launch(ctx, idx, n_idx, size, nullptr, 0, 0, words);
+  const int64_t n = edge_rows * (n_bins + 1);
+  hipLaunchKernelGGL(k_hist_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, edges, edge_rows, n_bins, words);
   OMC_HIP_CHECK(hipGetLastError());
   OMC_HIP_CHECK(hipMemcpyAsync(got, words, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -243,15 +222,13 @@ extern "C" omc_status omc_store_histogram_layout(int32_t n_bins, int32_t edges_p
 extern "C" omc_status omc_store_minmax(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                                        int32_t pooled, double* min_out, double* max_out, int64_t* count_out) {
   if (!ctx || n_iter < 1 || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size)) return OMC_INVALID_ARG;
-  const int64_t C = ctx->n_chains;
-  const int64_t R = pooled ? n_iter * C : n_iter, batches = pooled ? 1 : C;
+  const StoreView v = omc_store_view(ctx, n_iter, size, pooled != 0, store, idx, n_idx);
+  const int64_t R = v.R, batches = v.batches;
   const int64_t tiles = (n_idx + HIST_TE_MAX - 1) / HIST_TE_MAX;
   if (tiles * batches > 0x7fffffffLL) return OMC_INVALID_ARG;
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  int32_t got[2];
-  omc_status st = omc_hist_check(ctx, idx, n_idx, size, nullptr, 0, 0, got);
+  omc_status st = omc_store_check_index(ctx, nullptr, idx, n_idx, size);
   if (st != OMC_OK) return st;
-  if (got[0]) return OMC_INVALID_ARG;
   const int64_t slices = (R + HIST_MM_RB - 1) / HIST_MM_RB;
   // enough workgroups for the CUs, one partial per column where the tiles alone fill them (the per-chain form of a long store)
   int64_t parts = (8 * (int64_t)ctx->dev_cus + tiles * batches - 1) / (tiles * batches);
@@ -264,9 +241,8 @@ extern "C" omc_status omc_store_minmax(omc_ctx* ctx, int64_t n_iter, int64_t siz
     if (st != OMC_OK) return st;
     part = (double*)ctx->store_ws;
   }
-  hipLaunchKernelGGL(k_hist_minmax_part, dim3((unsigned)(tiles * batches), (unsigned)parts), dim3(HIST_THREADS), 0, ctx->stream, store, idx,
-                     pooled ? size : C * size, pooled ? (int64_t)0 : size, R, n_idx, tiles, slices, (int)(parts == 1), part, min_out, max_out,
-                     count_out);
+  hipLaunchKernelGGL(k_hist_minmax_part, dim3((unsigned)(tiles * batches), (unsigned)parts), dim3(HIST_THREADS), 0, ctx->stream, v, tiles, slices,
+                     (int)(parts == 1), part, min_out, max_out, count_out);
   if (parts > 1)
     hipLaunchKernelGGL(k_hist_minmax_join, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, ctx->stream, cols, (int)parts, part, min_out,
                        max_out, count_out);
@@ -280,8 +256,8 @@ extern "C" omc_status omc_store_histogram(omc_ctx* ctx, int64_t n_iter, int64_t 
   if (!ctx || n_iter < 1 || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size) || n_bins < 1 || n_bins > HIST_MAX_BINS || !edges ||
       !counts_out)
     return OMC_INVALID_ARG;
-  const int64_t C = ctx->n_chains;
-  const int64_t R = pooled ? n_iter * C : n_iter, batches = pooled ? 1 : C;
+  const StoreView v = omc_store_view(ctx, n_iter, size, pooled != 0, store, idx, n_idx);
+  const int64_t R = v.R, batches = v.batches;
   if (R >= (1LL << 32)) return OMC_UNSUPPORTED;  // a workgroup's 32-bit counters see at most R rows
   const bool per = edges_per_element != 0;
   const HistLayout L = hist_layout(n_bins, per);
@@ -297,9 +273,8 @@ extern "C" omc_status omc_store_histogram(omc_ctx* ctx, int64_t n_iter, int64_t 
   OMC_HIP_CHECK(hipMemsetAsync(counts_out, 0, (size_t)batches * n_idx * n_bins * sizeof(int64_t), s));
   if (outside_out) OMC_HIP_CHECK(hipMemsetAsync(outside_out, 0, (size_t)batches * n_idx * 3 * sizeof(int64_t), s));
   HistArgs a;
-  a.data = store; a.idx = idx; a.edges = edges; a.counts = counts_out; a.outside = outside_out;
-  a.row_stride = pooled ? size : C * size; a.batch_stride = pooled ? 0 : size;
-  a.R = R; a.n_idx = n_idx; a.tiles = tiles; a.slices = (R + L.RB - 1) / L.RB; a.n_bins = n_bins;
+  a.data = v.data; a.idx = v.idx; a.edges = edges; a.counts = counts_out; a.outside = outside_out;
+  a.row_stride = v.row_stride; a.batch_stride = v.batch_stride; a.R = R; a.n_idx = v.n; a.tiles = tiles; a.slices = (R + L.RB - 1) / L.RB; a.n_bins = n_bins;
   const bool uniform = got[1] == 0 && ctx->hist_algo != 1;
   const dim3 grid((unsigned)(tiles * batches), (unsigned)(a.slices < 65535 ? a.slices : 65535));
   const size_t lds = (size_t)L.end;

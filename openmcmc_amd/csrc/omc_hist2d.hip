@@ -12,26 +12,25 @@
 //   such passes in flight.  With occupancy every lane keeps the cells its (up to four) pairs fell into, keyed by (row of the
 //   pass, cell); the wave then takes the first remaining key with a ballot, its owner adds one to the cell's second counter, and
 //   every slot holding that key retires: a cell is counted once per row whatever the order.
-// Per axis the bin rule is that of k_hist_count: comparisons with the edges alone, a bisection or, with evenly spaced edges, an
-// arithmetic guess put right by the same comparisons.
+// Per axis the bin rule is k_hist_count's: hist_bin (omc_hist_layout.h).
 // Two forms of either kernel: 32-bit counters in LDS, the non-zero ones added to the zeroed int64 output at the end with 64-bit
 // integer atomic adds from the vector lanes (consecutive cells on consecutive lanes); or, for grids beyond the LDS budget and
 // for row counts a 32-bit counter could not hold, those atomic adds straight from the counting loop (DIRECT).  Integer addition
 // commutes: the result depends neither on the order of arrival nor on the form.  The LDS images and TE, RB come from
-// hist2d_layout_form() (omc_hist2d_layout.h), on both sides.  Validation is omc_hist.hip's k_hist_check, once per axis.
+// hist2d_layout_form() (omc_hist2d_layout.h), on both sides.  Validation is omc_hist.hip's omc_hist_check, once per axis.
 #include "omc_common.h"
 #include "omc_hist2d_layout.h"
+#include "omc_store_view.h"
 
 namespace {
 
 struct Hist2dArgs {
-  const double *x, *y;             // the two stores (may be the same)
-  const int64_t *idx_x, *idx_y;    // [n_pairs] or NULL
+  StoreView x, y;                  // the two stores (may be the same): the same R rows, n = n_pairs selected elements of each
   const double *ex, *ey;           // [nx + 1], [ny + 1] or [n_pairs][..]
   unsigned long long* counts;      // [batches][n_pairs][nx][ny] or [batches][nx][ny], zeroed
   unsigned long long* outside;     // [..][2], zeroed, or NULL
   unsigned long long* occupied;    // [batches][nx][ny], zeroed, or NULL
-  int64_t row_stride_x, batch_stride_x, row_stride_y, batch_stride_y, R, n_pairs, tiles, slices;
+  int64_t tiles, slices;
   int nx, ny;
   int pair_shift;   // k_hist2d_pool: a row takes 1 << pair_shift lanes of a wave (6: the whole wave)
   int chunk_shift;  // ... and 1 << chunk_shift of the four slots of a lane (rows of more than 64 pairs)
@@ -49,27 +48,10 @@ __device__ __forceinline__ Hist2dAxis hist2d_axis(const double* E, int nb) {
   a.scale = UNIFORM ? (double)nb / (a.eN - a.e0) : 0.0;
   return a;
 }
-// the last j in [0, nb) with E[j] <= v: np.searchsorted(E, v, 'right') - 1 with the last bin closed; -1 outside [E[0], E[nb]].
-// v is not NaN.
+// the axis' bin of v (not NaN), -1 outside [E[0], E[nb]]
 template <bool UNIFORM>
 __device__ __forceinline__ int hist2d_bin(const Hist2dAxis& a, double v) {
-  if (v < a.e0 || v > a.eN) return -1;
-  const int nb = a.nb;
-  int j;
-  if (UNIFORM) {
-    const double t = (v - a.e0) * a.scale;
-    j = t >= (double)nb ? nb - 1 : (int)t;
-    while (j > 0 && v < a.E[j]) --j;
-    while (j < nb - 1 && v >= a.E[j + 1]) ++j;
-  } else {
-    int lo = 0, hi = nb - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (a.E[mid] <= v) lo = mid; else hi = mid - 1;
-    }
-    j = lo;
-  }
-  return j;
+  return (v < a.e0 || v > a.eN) ? -1 : hist_bin<UNIFORM>(a.E, a.nb, a.e0, a.scale, v);
 }
 
 template <bool PER, bool UNIFORM, bool DIRECT>
@@ -84,7 +66,7 @@ __global__ void __launch_bounds__(HIST_THREADS) k_hist2d_pair(Hist2dArgs a) {
   const int tid = threadIdx.x, te = L.TE, e = tid & (te - 1), rl = tid / te, RL = HIST_THREADS / te;
   const int64_t batch = blockIdx.x / a.tiles, tile = blockIdx.x - batch * a.tiles;
   const int64_t j0 = tile * te, pair = j0 + e;
-  const int n_el = (a.n_pairs - j0 < te) ? (int)(a.n_pairs - j0) : te;  // pairs of this tile that exist
+  const int n_el = (a.x.n - j0 < te) ? (int)(a.x.n - j0) : te;  // pairs of this tile that exist
 
   if (PER) {
     const double* srcx = a.ex + j0 * (nx + 1);
@@ -110,20 +92,20 @@ __global__ void __launch_bounds__(HIST_THREADS) k_hist2d_pair(Hist2dArgs a) {
     const Hist2dAxis ax = hist2d_axis<UNIFORM>(PER ? sEx + e * L.EXS : sEx, nx);
     const Hist2dAxis ay = hist2d_axis<UNIFORM>(PER ? sEy + e * L.EYS : sEy, ny);
     uint32_t* myC = sC + e * L.CS;
-    unsigned long long* myG = a.counts + (batch * a.n_pairs + pair) * cells;
-    const double* px = a.x + batch * a.batch_stride_x + (a.idx_x ? a.idx_x[pair] : pair);
-    const double* py = a.y + batch * a.batch_stride_y + (a.idx_y ? a.idx_y[pair] : pair);
+    unsigned long long* myG = a.counts + (batch * a.x.n + pair) * cells;
+    const double* px = a.x.column(batch, pair);
+    const double* py = a.y.column(batch, pair);
     unsigned long long out_n = 0ull, nan_n = 0ull;
     for (int64_t slice = blockIdx.y; slice < a.slices; slice += gridDim.y) {
       const int64_t r0 = slice * L.RB;
-      const int64_t r1 = (r0 + L.RB < a.R) ? r0 + L.RB : a.R;
+      const int64_t r1 = (r0 + L.RB < a.x.R) ? r0 + L.RB : a.x.R;
       for (int64_t r = r0 + rl; r < r1; r += 4 * RL) {
         double vx[4], vy[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const bool in = r + k * RL < r1;
-          vx[k] = in ? px[(r + k * RL) * a.row_stride_x] : 0.0;
-          vy[k] = in ? py[(r + k * RL) * a.row_stride_y] : 0.0;
+          vx[k] = in ? px[(r + k * RL) * a.x.row_stride] : 0.0;
+          vy[k] = in ? py[(r + k * RL) * a.y.row_stride] : 0.0;
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -142,7 +124,7 @@ __global__ void __launch_bounds__(HIST_THREADS) k_hist2d_pair(Hist2dArgs a) {
   __syncthreads();
 
   if (!DIRECT) {
-    unsigned long long* out = a.counts + (batch * a.n_pairs + j0) * cells;
+    unsigned long long* out = a.counts + (batch * a.x.n + j0) * cells;
     for (int i = tid; i < n_el * cells; i += HIST_THREADS) {
       const int el = i / cells;
       const uint32_t c = sC[el * L.CS + (i - el * cells)];
@@ -150,7 +132,7 @@ __global__ void __launch_bounds__(HIST_THREADS) k_hist2d_pair(Hist2dArgs a) {
     }
   }
   if (a.outside) {
-    unsigned long long* oo = a.outside + (batch * a.n_pairs + j0) * 2;
+    unsigned long long* oo = a.outside + (batch * a.x.n + j0) * 2;
     for (int i = tid; i < n_el * 2; i += HIST_THREADS)
       if (sO[i]) atomicAdd(oo + i, sO[i]);
   }
@@ -188,35 +170,35 @@ __global__ void __launch_bounds__(HIST_THREADS) k_hist2d_pool(Hist2dArgs a) {
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int64_t p = 64 * (u & (cpr - 1)) + p0;
-    const bool in = p < a.n_pairs;
-    ox[u] = in ? (a.idx_x ? a.idx_x[p] : p) : 0;
-    oy[u] = in ? (a.idx_y ? a.idx_y[p] : p) : 0;
+    const bool in = p < a.x.n;
+    ox[u] = in ? (a.x.idx ? a.x.idx[p] : p) : 0;
+    oy[u] = in ? (a.y.idx ? a.y.idx[p] : p) : 0;
   }
-  const double* bx = a.x + batch * a.batch_stride_x;
-  const double* by = a.y + batch * a.batch_stride_y;
+  const double* bx = a.x.data + batch * a.x.batch_stride;
+  const double* by = a.y.data + batch * a.y.batch_stride;
   unsigned long long* G = a.counts + batch * cells;
   unsigned long long* GO = OCC ? a.occupied + batch * cells : nullptr;
   unsigned long long out_n = 0ull, nan_n = 0ull;
   const int rows_it = gpi * rpp;  // rows of a wave's iteration
   for (int64_t slice = blockIdx.y; slice < a.slices; slice += gridDim.y) {
     const int64_t r0 = slice * L.RB;
-    const int64_t r1 = (r0 + L.RB < a.R) ? r0 + L.RB : a.R;
+    const int64_t r1 = (r0 + L.RB < a.x.R) ? r0 + L.RB : a.x.R;
     for (int64_t rb = r0 + wave * rows_it; rb < r1; rb += 4 * rows_it) {
-      for (int64_t base = 0; base < a.n_pairs; base += 64 * 4) {  // (one trip unless a row has more than 256 pairs)
+      for (int64_t base = 0; base < a.x.n; base += 64 * 4) {  // (one trip unless a row has more than 256 pairs)
         double vx[4], vy[4];
         bool in[4];
         int key[4], cell[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int64_t r = rb + (u >> csh) * rpp + s, p = base + 64 * (u & (cpr - 1)) + p0;
-          in[u] = r < r1 && p < a.n_pairs;
+          in[u] = r < r1 && p < a.x.n;
           int64_t cx = ox[u], cy = oy[u];
           if (base && in[u]) {
-            cx = a.idx_x ? a.idx_x[p] : p;
-            cy = a.idx_y ? a.idx_y[p] : p;
+            cx = a.x.idx ? a.x.idx[p] : p;
+            cy = a.y.idx ? a.y.idx[p] : p;
           }
-          vx[u] = in[u] ? bx[r * a.row_stride_x + cx] : 0.0;
-          vy[u] = in[u] ? by[r * a.row_stride_y + cy] : 0.0;
+          vx[u] = in[u] ? bx[r * a.x.row_stride + cx] : 0.0;
+          vy[u] = in[u] ? by[r * a.y.row_stride + cy] : 0.0;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -302,8 +284,9 @@ extern "C" omc_status omc_store_histogram2d(omc_ctx* ctx, int64_t n_iter, int64_
       (edges_per_pair && pool_pairs) || (occupied_out && !pool_pairs))
     return OMC_INVALID_ARG;
   if (occupied_out && n_pairs > HIST2D_OCC_PAIRS) return OMC_UNSUPPORTED;  // a row's cells must stay in one wave
-  const int64_t C = ctx->n_chains;
-  const int64_t R = pooled ? n_iter * C : n_iter, batches = pooled ? 1 : C;
+  const StoreView vx = omc_store_view(ctx, n_iter, size_x, pooled != 0, store_x, idx_x, n_pairs);
+  const StoreView vy = omc_store_view(ctx, n_iter, size_y, pooled != 0, store_y, idx_y, n_pairs);
+  const int64_t R = vx.R, batches = vx.batches;
   const bool per = edges_per_pair != 0;
   const int shape = !pool_pairs ? HIST2D_PER_PAIR : (occupied_out ? HIST2D_POOLED_OCC : HIST2D_POOLED);
   Hist2dLayout L = hist2d_layout(nx, ny, per, shape);
@@ -330,11 +313,9 @@ extern "C" omc_status omc_store_histogram2d(omc_ctx* ctx, int64_t n_iter, int64_
   if (outside_out) OMC_HIP_CHECK(hipMemsetAsync(outside_out, 0, (size_t)grids * 2 * sizeof(int64_t), s));
   if (occupied_out) OMC_HIP_CHECK(hipMemsetAsync(occupied_out, 0, (size_t)batches * cells * sizeof(int64_t), s));
   Hist2dArgs a;
-  a.x = store_x; a.y = store_y; a.idx_x = idx_x; a.idx_y = idx_y; a.ex = edges_x; a.ey = edges_y;
+  a.x = vx; a.y = vy; a.ex = edges_x; a.ey = edges_y;
   a.counts = (unsigned long long*)counts_out; a.outside = (unsigned long long*)outside_out; a.occupied = (unsigned long long*)occupied_out;
-  a.row_stride_x = pooled ? size_x : C * size_x; a.batch_stride_x = pooled ? 0 : size_x;
-  a.row_stride_y = pooled ? size_y : C * size_y; a.batch_stride_y = pooled ? 0 : size_y;
-  a.R = R; a.n_pairs = n_pairs; a.tiles = tiles; a.slices = slices; a.nx = nx; a.ny = ny;
+  a.tiles = tiles; a.slices = slices; a.nx = nx; a.ny = ny;
   a.pair_shift = 6; a.chunk_shift = 0;
   if (n_pairs <= 32) {
     a.pair_shift = 0;

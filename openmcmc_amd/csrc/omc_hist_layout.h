@@ -56,3 +56,26 @@ OMC_HIST_HD constexpr HistLayout hist_layout(int n_bins, int per_element) {
 static_assert(hist_layout(HIST_MAX_BINS, 1).end <= HIST_LDS_BUDGET && hist_layout(HIST_MAX_BINS, 0).end <= HIST_LDS_BUDGET,
               "the one-element tile must fit");
 static_assert(HIST_LDS_BUDGET <= HIST_LDS_WORKGROUP, "a workgroup gets at most 64 KiB");
+
+#if defined(__HIPCC__)
+// The bin rule of the store histograms (omc_hist.hip, omc_hist2d.hip), the one that makes counts equal np.histogram's bit for bit:
+// the last j in [0, nb) with E[j] <= v, np.searchsorted(E, v, 'right') - 1 with the last bin closed, by comparisons with the
+// edges alone -- a bisection or, with evenly spaced edges (UNIFORM; scale = nb / (E[nb] - e0)), an arithmetic guess put right by
+// the same comparisons.  e0 = E[0] <= v <= E[nb], v not NaN: what lies outside or is NaN is the caller's to count.
+template <bool UNIFORM>
+__device__ __forceinline__ int hist_bin(const double* E, int nb, double e0, double scale, double v) {
+  if (UNIFORM) {
+    const double t = (v - e0) * scale;
+    int j = t >= (double)nb ? nb - 1 : (int)t;
+    while (j > 0 && v < E[j]) --j;
+    while (j < nb - 1 && v >= E[j + 1]) ++j;
+    return j;
+  }
+  int lo = 0, hi = nb - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (E[mid] <= v) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+#endif

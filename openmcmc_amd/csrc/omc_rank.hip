@@ -3,13 +3,11 @@
 // The contract is in include/omcmc_hip.h (omc_store_ranks, omc_store_rank_diagnostics, omc_store_rank_schedule).
 //
 // store is [N][C][size].  A chunk of Kc selected elements is worked on at a time:
-//   k_rank_gather  reads the draws of the chunk where they lie (16 adjacent elements of a row per 128 bytes), turns them into
-//                  order-preserving 64-bit keys (-0.0 first made +0.0) and writes them, transposed through LDS, into columns
-//                  keys [Kc][P], P the next power of two >= the S draws of a column, the rest of a column the all-ones key;
-//                  it notes per element whether a NaN (bit 0) or an infinity (bit 1) was seen.  With `fold` the value is
-//                  |x - med|, med the element's median from k_rank_stats.
-//   k_rank_sort_tile / k_rank_sort_global
-//                  the key-only bitonic sort of every column (omc_rank_sort.h, shared with omc_hdi.hip).
+//   k_rank_gather  the gather tile of omc_rank_sort.h: the draws of the chunk, read where they lie, as order-preserving 64-bit
+//                  keys (-0.0 first made +0.0) in columns keys [Kc][P], P the next power of two >= the S draws of a column, the
+//                  rest of a column the all-ones key; it notes per element whether a NaN (bit 0) or an infinity (bit 1) was
+//                  seen.  With `fold` the value is |x - med|, med the element's median from k_rank_stats.
+//   rank_sort      the key-only bitonic sort of every column (omc_store_shared.hip, shared with omc_hdi.hip).
 //   k_rank_emit    for every draw the number of smaller and of equal keys by bisection in its sorted column (ties are exact, no
 //                  payload is carried through the sort; the second bisection only where the next key is equal): the average rank, or z = ndtri((r - 3/8) / (S + 1/4)), and with the
 //                  same read of the store the tail indicators x <= q05, x <= q95.
@@ -26,60 +24,28 @@
 #include "omc_common.h"
 #include "omc_quantile.h"
 #include "omc_rank_sort.h"
+#include "omc_store_view.h"
 #include "omc_truncnorm.h"
 
 namespace {
 
-constexpr int G_TE = 16, G_TS = 64;  // k_rank_gather: elements x draws of a workgroup's tile
-
 // Draw s of a column (s < S) is row s of the store seen as [N C][size] when s < first, else row s + skip: the two halves of a
 // split store, with the middle row of an odd N (rows [mid_row0, mid_row0 + C), mid_row0 < 0: none) read for its NaN / inf only.
+// stats (or NULL): fold the draws, |x - stats[3 e]|.
 __global__ void __launch_bounds__(256) k_rank_gather(const double* __restrict__ store, const int64_t* __restrict__ idx, int64_t k0, int64_t Kc,
                                                      int64_t size, int64_t C, int64_t S, int64_t P, int64_t first, int64_t skip,
                                                      int64_t mid_row0, const double* __restrict__ stats, uint64_t* __restrict__ keys,
                                                      int32_t* __restrict__ flags) {
-  __shared__ uint64_t tile[G_TE][G_TS + 1];
-  const int tid = threadIdx.x, e_l = tid & (G_TE - 1), d_l = tid / G_TE;
-  const int64_t e0 = (int64_t)blockIdx.y * G_TE, s0 = (int64_t)blockIdx.x * G_TS;
-  const int64_t e = e0 + e_l;
-  const bool live = e < Kc;
-  const int64_t col = live ? (idx ? idx[k0 + e] : k0 + e) : 0;
+  const int64_t e0 = (int64_t)blockIdx.y * RANK_G_TE, e = e0 + (threadIdx.x & (RANK_G_TE - 1));
   const bool fold = stats != nullptr;
-  const double med = (fold && live) ? stats[3 * e] : 0.0;
-  const double inf = __longlong_as_double(0x7ff0000000000000LL);
+  const double med = (fold && e < Kc) ? stats[3 * e] : 0.0;
   int32_t bits = 0;
-  double v[G_TS / (256 / G_TE)];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int64_t s = s0 + d_l + 16 * u;
-    v[u] = (live && s < S) ? store[(s < first ? s : s + skip) * size + col] : 0.0;
+  if (mid_row0 >= 0 && blockIdx.x == 0 && e < Kc) {
+    const int64_t col = idx ? idx[k0 + e] : k0 + e;
+    for (int64_t c = threadIdx.x / RANK_G_TE; c < C; c += 256 / RANK_G_TE) bits |= rank_flag_bits(store[(mid_row0 + c) * size + col]);
   }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int64_t s = s0 + d_l + 16 * u;
-    uint64_t key = ~0ull;
-    if (live && s < S) {
-      const double x = fold ? fabs(v[u] - med) : v[u];
-      if (x != x) bits |= 1;
-      else if (fabs(x) == inf) bits |= 2;
-      key = rank_key(x);
-    }
-    tile[e_l][d_l + 16 * u] = key;
-  }
-  if (mid_row0 >= 0 && blockIdx.x == 0 && live)
-    for (int64_t c = d_l; c < C; c += 256 / G_TE) {
-      const double x = store[(mid_row0 + c) * size + col];
-      if (x != x) bits |= 1;
-      else if (fabs(x) == inf) bits |= 2;
-    }
-  if (flags && bits) atomicOr(&flags[e], bits);
-  __syncthreads();
-  const int s_l = tid & (G_TS - 1);
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int el = (tid >> 6) + 4 * u;
-    if (e0 + el < Kc && s0 + s_l < P) keys[(e0 + el) * P + s0 + s_l] = tile[el][s_l];
-  }
+  rank_gather_tile(store, idx, k0, Kc, size, S, P, e0, (int64_t)blockIdx.x * RANK_G_TS, 0,
+                   [=](int64_t s) { return s < first ? s : s + skip; }, [=](double x) { return fold ? fabs(x - med) : x; }, bits, keys, flags);
 }
 
 // stats [Kc][3] = median ((a + b) / 2 of the two middle order statistics: S is even), q05, q95 of the S sorted draws
@@ -177,7 +143,7 @@ RankGeom rank_geom(int64_t N, int64_t C, bool split) {
 
 omc_status rank_gather(omc_ctx* ctx, const double* store, const int64_t* idx, int64_t k0, int64_t kc, int64_t size, const RankGeom& g,
                        const double* stats, uint64_t* keys, int32_t* flags) {
-  const dim3 grid((unsigned)((g.P + G_TS - 1) / G_TS), (unsigned)((kc + G_TE - 1) / G_TE));
+  const dim3 grid((unsigned)((g.P + RANK_G_TS - 1) / RANK_G_TS), (unsigned)((kc + RANK_G_TE - 1) / RANK_G_TE));
   hipLaunchKernelGGL(k_rank_gather, grid, dim3(256), 0, ctx->stream, store, idx, k0, kc, size, ctx->n_chains, g.S, g.P, g.first, g.skip,
                      g.mid_row0, stats, keys, flags);
   OMC_HIP_CHECK(hipGetLastError());
@@ -212,7 +178,7 @@ extern "C" omc_status omc_store_ranks(omc_ctx* ctx, int64_t n_iter, int64_t size
   char* ws = (char*)ctx->rank_ws;
   uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
   int32_t* flags = (int32_t*)(ws + RANK_HEAD + (size_t)Kc * g.P * sizeof(uint64_t));
-  st = rank_check(ctx, idx, n_idx, size, (int32_t*)ws);
+  st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size);
   if (st != OMC_OK) return st;
   for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {
     const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc;
@@ -250,7 +216,7 @@ extern "C" omc_status omc_store_rank_diagnostics(omc_ctx* ctx, int64_t n_iter, i
   double* rh4 = stats + 3 * Kc;
   double* es4 = rh4 + 4 * Kc;
   int32_t* flags = (int32_t*)(es4 + 4 * Kc);
-  st = rank_check(ctx, idx, n_idx, size, (int32_t*)ws);
+  st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size);
   if (st != OMC_OK) return st;
   hipStream_t s = ctx->stream;
   for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {

@@ -27,6 +27,7 @@
 // every k -- and, in the long form without an index, on whether the row starts on a 16-byte boundary: on nothing that differs
 // between two calls with the same arguments.  No atomics of any kind, no scratch.
 #include "omc_common.h"
+#include "omc_store_view.h"
 
 namespace {
 
@@ -253,15 +254,15 @@ extern "C" omc_status omc_store_reduce(omc_ctx* ctx, int64_t n_iter, int64_t siz
   if (op < OMC_REDUCE_SUM || op > OMC_REDUCE_SUPNORM) return red_invalid("omc_store_reduce: unknown op");
   if (op == OMC_REDUCE_COUNT_ABOVE && !a) return red_invalid("omc_store_reduce: COUNT_ABOVE needs the thresholds a");
   if (op == OMC_REDUCE_SUPNORM && (!a || !b)) return red_invalid("omc_store_reduce: SUPNORM needs the centres a and the scales b");
-  const int64_t R = n_iter * ctx->n_chains;
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  int32_t got[2];
-  omc_status st = omc_hist_check(ctx, idx, n_idx, size, nullptr, 0, 0, got);
+  const omc_status st = omc_store_check_index(ctx, nullptr, idx, n_idx, size);
+  if (st == OMC_INVALID_ARG) return red_invalid("omc_store_reduce: an index outside [0, size)");  // (the helper's only use of that status)
   if (st != OMC_OK) return st;
-  if (got[0]) return red_invalid("omc_store_reduce: an index outside [0, size)");
+  const StoreView v = omc_store_view(ctx, n_iter, size, true, store, idx, n_idx);  // pooled: R rows of row_stride = size doubles
+  const int64_t R = v.R;
   RedArgs g;
-  g.store = store; g.idx = idx; g.a = a; g.b = b; g.out = out; g.count_out = count_out;
-  g.R = R; g.size = size; g.n_idx = n_idx; g.omit_nan = omit_nan != 0;
+  g.store = v.data; g.idx = v.idx; g.a = a; g.b = b; g.out = out; g.count_out = count_out;
+  g.R = R; g.size = v.row_stride; g.n_idx = v.n; g.omit_nan = omit_nan != 0;
   g.wpr = n_idx >= RED_SPLIT_MIN ? RED_THREADS / 64 : 1;
   // short form: G lanes per row, at most 16 selected elements each; the pitch is the first p >= size with p = G (mod 2 G), so
   // that the 32 / G rows of half a wave start on different multiples of G of the 32 eight-byte banks (from G = 32 on half a wave

@@ -2,6 +2,7 @@
 #include <math.h>
 
 #include "omc_common.h"
+#include "omc_store_view.h"
 
 // log Gamma(shape, rate) density at v (lnorm = shape log rate - lgamma(shape)), as scipy.stats.gamma.logpdf: at v = 0 the
 // density is +inf for shape < 1, rate for shape = 1 and 0 for shape > 1; -inf below 0
@@ -289,9 +290,7 @@ omc_status omc_store_moments(omc_ctx* ctx, int64_t n_iter, int64_t size, const d
                              double* mean_out, double* var_out) {
   if (!ctx || n_iter < 1 || size < 1 || !store || (!mean_out && !var_out)) return OMC_INVALID_ARG;
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  // both summaries are column moments of one row-major matrix (omc_store.hip): pooled [n_iter C][size], per chain [n_iter][C size]
-  const int64_t C = ctx->n_chains;
-  return omc_col_moments(ctx, store, pooled ? n_iter * C : n_iter, pooled ? size : C * size, mean_out, var_out);
+  return omc_col_moments(ctx, omc_store_view(ctx, n_iter, size, pooled != 0, store), mean_out, var_out);
 }
 
 omc_status omc_fill_normal(omc_ctx* ctx, int64_t n, uint64_t draw_index, double* out, int64_t ld) {

@@ -18,6 +18,7 @@
 
 #include "omc_common.h"
 #include "omc_quantile.h"
+#include "omc_store_view.h"
 
 namespace {
 
@@ -344,56 +345,6 @@ __global__ void __launch_bounds__(256) k_q_owned4(const double* __restrict__ dat
   }
 }
 
-// mean and unbiased variance of every column of [R][K]: row slices combined by Chan's pairwise update through a small
-// [slices][2][K] scratch (deterministic: fixed slice boundaries, fixed combination order)
-__global__ void __launch_bounds__(256) k_col_moments_part(const double* __restrict__ data, int64_t R, int64_t K, int64_t rows_per_block,
-                                                          double* __restrict__ part /*[slices][3][K]*/) {
-  __shared__ double sm[3][Q_ROWSTEP][Q_COLS];
-  const int tid = threadIdx.x, col = tid & (Q_COLS - 1), rr = tid >> 4;
-  const int64_t k = (int64_t)blockIdx.x * Q_COLS + col;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-  const int64_t r1 = (r0 + rows_per_block < R) ? r0 + rows_per_block : R;
-  double cnt = 0.0, mean = 0.0, m2 = 0.0;
-  if (k < K)
-    for (int64_t r = r0 + rr; r < r1; r += Q_ROWSTEP) {
-      const double v = data[r * K + k];
-      cnt += 1.0;
-      const double d = v - mean;
-      mean += d / cnt;
-      m2 = fma(d, v - mean, m2);
-    }
-  sm[0][rr][col] = cnt; sm[1][rr][col] = mean; sm[2][rr][col] = m2;
-  __syncthreads();
-  if (rr == 0 && k < K) {
-    for (int j = 1; j < Q_ROWSTEP; ++j) {
-      const double cb = sm[0][j][col], mb = sm[1][j][col], qb = sm[2][j][col];
-      if (cb == 0.0) continue;
-      const double tot = cnt + cb, d = mb - mean;
-      mean += d * (cb / tot);
-      m2 += qb + d * d * (cnt * cb / tot);
-      cnt = tot;
-    }
-    double* o = part + (int64_t)blockIdx.y * 3 * K;
-    o[k] = cnt; o[K + k] = mean; o[2 * K + k] = m2;
-  }
-}
-__global__ void k_col_moments_join(int64_t K, int slices, const double* __restrict__ part, double* __restrict__ mean_out, double* __restrict__ var_out) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= K) return;
-  double cnt = 0.0, mean = 0.0, m2 = 0.0;
-  for (int s = 0; s < slices; ++s) {
-    const double* o = part + (int64_t)s * 3 * K;
-    const double cb = o[k], mb = o[K + k], qb = o[2 * K + k];
-    if (cb == 0.0) continue;
-    const double tot = cnt + cb, d = mb - mean;
-    mean += d * (cb / tot);
-    m2 += qb + d * d * (cnt * cb / tot);
-    cnt = tot;
-  }
-  if (mean_out) mean_out[k] = mean;
-  if (var_out) var_out[k] = cnt > 1.0 ? m2 / (cnt - 1.0) : 0.0;
-}
-
 // every `every`-th stored iteration, packed: out[j] = store[first + j * every]  (rows of `row` doubles)
 __global__ void k_thin_rows(const double* __restrict__ src, int64_t row, int64_t first, int64_t every, int64_t n_out, double* __restrict__ dst) {
   const int64_t j = blockIdx.y;
@@ -412,8 +363,8 @@ omc_status omc_store_quantiles(omc_ctx* ctx, int64_t n_iter, int64_t size, const
   for (int j = 0; j < n_q; ++j)
     if (!(q[j] >= 0.0 && q[j] <= 1.0)) return OMC_INVALID_ARG;  // np.quantile: "Quantiles must be in the range [0, 1]"
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  const int64_t C = ctx->n_chains;
-  const int64_t R = pooled ? n_iter * C : n_iter, K = pooled ? size : C * size;
+  const StoreView v = omc_store_view(ctx, n_iter, size, pooled != 0);
+  const int64_t R = v.R, K = v.batches * v.n;  // every column takes part: the batches are adjacent columns of one matrix
   // workspace per column of a chunk: histograms 8 x 1 KB, prefixes and ranks 8 x 8 B each, fractions 4 x 8 B, NaN count
   const size_t per_col = (size_t)Q_TARGETS * 256 * 4 + (size_t)Q_TARGETS * 16 + (Q_TARGETS / 2) * 8 + 4;
   const size_t budget = (size_t)256 << 20;
@@ -493,20 +444,3 @@ omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const doub
 }
 
 }  // extern "C"
-
-// the column moments behind omc_store_moments (omc_scalar.hip keeps the entry point)
-omc_status omc_col_moments(omc_ctx* ctx, const double* data, int64_t R, int64_t K, double* mean_out, double* var_out) {
-  const unsigned tiles = (unsigned)((K + Q_COLS - 1) / Q_COLS);
-  int64_t slices = (2048 + tiles - 1) / tiles;
-  if (slices > (R + 255) / 256) slices = (R + 255) / 256;
-  if (slices < 1) slices = 1;
-  if (slices > 1024) slices = 1024;
-  const int64_t rpb = (R + slices - 1) / slices;
-  omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->store_ws, &ctx->store_ws_bytes, (size_t)slices * 3 * K * sizeof(double));
-  if (st != OMC_OK) return st;
-  double* part = (double*)ctx->store_ws;
-  hipLaunchKernelGGL(k_col_moments_part, dim3(tiles, (unsigned)slices), dim3(256), 0, ctx->stream, data, R, K, rpb, part);
-  hipLaunchKernelGGL(k_col_moments_join, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, ctx->stream, K, (int)slices, part, mean_out, var_out);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
-}

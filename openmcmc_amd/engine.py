@@ -25,6 +25,11 @@ def _torch():
     return _TORCH
 
 
+def _ptr(t):
+    """Device pointer of a tensor of any dtype (None passes through as NULL)."""
+    return None if t is None else t.data_ptr()
+
+
 class Engine:
     """Owns an omc_ctx bound to torch's current stream on `device`."""
 
@@ -1157,11 +1162,15 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ posterior summaries
-    def store_moments(self, store, pooled=False):
-        """(mean, var) of a device store (n_iter, C, size): per chain (C, size) or pooled (size,)."""
+    def _store_shape(self, store):
+        """(n_iter, size) of a device store (n_iter, C, size)"""
         if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
             raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
-        n_iter, _, size = store.shape
+        return store.shape[0], store.shape[2]
+
+    def store_moments(self, store, pooled=False):
+        """(mean, var) of a device store (n_iter, C, size): per chain (C, size) or pooled (size,)."""
+        n_iter, size = self._store_shape(store)
         shape = (size,) if pooled else (self.n_chains, size)
         mean, var = self.empty(*shape), self.empty(*shape)
         check(lib.omc_store_moments(self._ctx, n_iter, size, self._p(store), int(pooled), self._p(mean), self._p(var)))
@@ -1170,14 +1179,12 @@ class Engine:
     def store_quantiles(self, store, q, pooled=False, omit_nan=True):
         """np.quantile (omit_nan=False) / np.nanquantile (True) of a device store (n_iter, C, size) along the iterations,
         default "linear" method: (len(q), C, size) per chain or (len(q), size) pooled over chains; computed on the device."""
-        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
-            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        n_iter, size = self._store_shape(store)
         qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
         if qs.ndim != 1 or qs.size < 1:
             raise ValueError("q must be a scalar or a one-dimensional sequence")
         if not np.all((qs >= 0) & (qs <= 1)):
             raise ValueError("Quantiles must be in the range [0, 1]")  # np.quantile's own message
-        n_iter, _, size = store.shape
         out = self.empty(*((qs.size, size) if pooled else (qs.size, self.n_chains, size)))
         check(lib.omc_store_quantiles(self._ctx, n_iter, size, self._p(store), int(pooled), qs.size,
                                       qs.ctypes.data_as(C.POINTER(C.c_double)), int(bool(omit_nan)), self._p(out)))
@@ -1187,9 +1194,7 @@ class Engine:
         """Split R-hat and effective sample size of every element of a device store (n_iter, C, size), computed on the
         device (omc_store_rhat_ess): (rhat, ess, lags) as device tensors of shape (size,), lags int32 = the lags the
         element's Geyer sequence used.  n_iter >= 4."""
-        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
-            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
-        n_iter, _, size = store.shape
+        n_iter, size = self._store_shape(store)
         if n_iter < 4:
             raise ValueError("split R-hat and ESS need at least 4 stored iterations")
         rhat, ess = self.empty(size), self.empty(size)
@@ -1222,22 +1227,17 @@ class Engine:
         torch integers) select elements, in that order, repeats allowed; without store_b the matrix is that of a with
         itself and exactly symmetric (index_b is then not accepted).  NaN draws propagate as in np.cov."""
         torch = _torch()
-        for t in (store_a,) if store_b is None else (store_a, store_b):
-            if t.dim() != 3 or t.shape[1] != self.n_chains or not t.is_contiguous():
-                raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        n_iter, size_a = self._store_shape(store_a)
+        n_iter_b, size_b = (n_iter, size_a) if store_b is None else self._store_shape(store_b)
         if store_b is None and index_b is not None:
             raise ValueError("index_b needs store_b")
-        if store_b is not None and store_b.shape[0] != store_a.shape[0]:
+        if n_iter_b != n_iter:
             raise ValueError("store_a and store_b must hold the same number of iterations")
-        n_iter, _, size_a = store_a.shape
         idx_a, n_a = self._store_index(index_a, size_a)
-        size_b, idx_b, n_b = size_a, None, n_a
-        if store_b is not None:
-            size_b = store_b.shape[2]
-            idx_b, n_b = self._store_index(index_b, size_b)
+        idx_b, n_b = (None, n_a) if store_b is None else self._store_index(index_b, size_b)
         out = self.empty(*((n_a, n_b) if pooled else (self.n_chains, n_a, n_b)))
-        check(lib.omc_store_cov(self._ctx, n_iter, size_a, self._p(store_a), None if idx_a is None else idx_a.data_ptr(), n_a,
-                                size_b, self._p(store_b), None if idx_b is None else idx_b.data_ptr(), n_b,
+        check(lib.omc_store_cov(self._ctx, n_iter, size_a, self._p(store_a), _ptr(idx_a), n_a,
+                                size_b, self._p(store_b), _ptr(idx_b), n_b,
                                 int(bool(pooled)), int(bool(correlation)), self._p(out)))
         return out
 
@@ -1260,14 +1260,12 @@ class Engine:
         (omc_store_minmax): np.nanmin, np.nanmax and the number of non-NaN draws, shape (n_idx,) pooled over chains and
         iterations, else (C, n_idx); count is int64; an element without a non-NaN draw gives NaN, NaN, 0."""
         torch = _torch()
-        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
-            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
-        n_iter, _, size = store.shape
+        n_iter, size = self._store_shape(store)
         idx, n = self._store_index(index, size)
         shape = (n,) if pooled else (self.n_chains, n)
         mn, mx = self.empty(*shape), self.empty(*shape)
         cnt = torch.empty(shape, dtype=torch.int64, device=self.device)
-        check(lib.omc_store_minmax(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n,
+        check(lib.omc_store_minmax(self._ctx, n_iter, size, self._p(store), _ptr(idx), n,
                                    int(bool(pooled)), self._p(mn), self._p(mx), cnt.data_ptr()))
         return mn, mx, cnt
 
@@ -1277,9 +1275,7 @@ class Engine:
         (.., 3) = draws below edges[0], above edges[-1], NaN.  edges: 1-D (n_bins + 1,) shared by all elements or 2-D
         (n_idx, n_bins + 1) per element, a host array (uploaded synchronously) or a device tensor; non-decreasing, no NaN."""
         torch = _torch()
-        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
-            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
-        n_iter, _, size = store.shape
+        n_iter, size = self._store_shape(store)
         idx, n = self._store_index(index, size)
         e = self._store_edges(edges)
         if e.dim() not in (1, 2) or (e.dim() == 2 and e.shape[0] != n):
@@ -1290,7 +1286,7 @@ class Engine:
         lead = (n,) if pooled else (self.n_chains, n)
         counts = torch.empty(lead + (n_bins,), dtype=torch.int64, device=self.device)
         outside = torch.empty(lead + (3,), dtype=torch.int64, device=self.device)
-        check(lib.omc_store_histogram(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n,
+        check(lib.omc_store_histogram(self._ctx, n_iter, size, self._p(store), _ptr(idx), n,
                                       int(bool(pooled)), n_bins, e.data_ptr(), int(e.dim() == 2), counts.data_ptr(), outside.data_ptr()))
         return counts, outside
 
@@ -1331,13 +1327,10 @@ class Engine:
         (n_pairs, ny + 1) per pair (both or neither; not with pool_pairs); host arrays (uploaded synchronously) or device
         tensors; non-decreasing, no NaN."""
         torch = _torch()
-        for t in (store_x, store_y):
-            if t.dim() != 3 or t.shape[1] != self.n_chains or not t.is_contiguous():
-                raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
-        if store_y.shape[0] != store_x.shape[0]:
+        n_iter, size_x = self._store_shape(store_x)
+        n_iter_y, size_y = self._store_shape(store_y)
+        if n_iter_y != n_iter:
             raise ValueError("store_x and store_y must hold the same number of iterations")
-        n_iter, _, size_x = store_x.shape
-        size_y = store_y.shape[2]
         idx_x, n = self._store_index(index_x, size_x)
         idx_y, n_y = self._store_index(index_y, size_y)
         if n != n_y:
@@ -1356,10 +1349,10 @@ class Engine:
         counts = torch.empty(lead + (nx, ny), dtype=torch.int64, device=self.device)
         outside = torch.empty(lead + (2,), dtype=torch.int64, device=self.device)
         occupied = torch.empty(lead + (nx, ny), dtype=torch.int64, device=self.device) if occupancy else None
-        check(lib.omc_store_histogram2d(self._ctx, n_iter, size_x, self._p(store_x), None if idx_x is None else idx_x.data_ptr(),
-                                        size_y, self._p(store_y), None if idx_y is None else idx_y.data_ptr(), n, int(bool(pooled)),
+        check(lib.omc_store_histogram2d(self._ctx, n_iter, size_x, self._p(store_x), _ptr(idx_x),
+                                        size_y, self._p(store_y), _ptr(idx_y), n, int(bool(pooled)),
                                         int(bool(pool_pairs)), nx, ex.data_ptr(), ny, ey.data_ptr(), int(ex.dim() == 2),
-                                        counts.data_ptr(), outside.data_ptr(), None if occupied is None else occupied.data_ptr()))
+                                        counts.data_ptr(), outside.data_ptr(), _ptr(occupied)))
         return (counts, outside, occupied) if occupancy else (counts, outside)
 
     @staticmethod
@@ -1377,14 +1370,12 @@ class Engine:
         (omc_store_ranks): a device tensor (n_iter, C, n_idx), scipy.stats.rankdata(method="average") of the element's
         n_iter * C draws, bit for bit.  split=True: ranks among the split draws (first and last n_iter // 2 iterations of
         every chain, n_iter >= 4), NaN in the dropped middle row of an odd n_iter.  An element with a NaN draw gives NaN."""
-        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
-            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
-        n_iter, _, size = store.shape
+        n_iter, size = self._store_shape(store)
         if n_iter < (4 if split else 1):
             raise ValueError("split ranks need at least 4 stored iterations")
         idx, n = self._store_index(index, size)
         out = self.empty(n_iter, self.n_chains, n)
-        check(lib.omc_store_ranks(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n,
+        check(lib.omc_store_ranks(self._ctx, n_iter, size, self._p(store), _ptr(idx), n,
                                   int(bool(split)), self._p(out)))
         return out
 
@@ -1392,14 +1383,12 @@ class Engine:
         """Rank-normalised split R-hat, bulk-ESS and tail-ESS (Vehtari et al. 2021) of every selected element of a device
         store (n_iter, C, size), on the device (omc_store_rank_diagnostics): (rhat, ess_bulk, ess_tail) as device tensors
         of shape (n_idx,).  n_iter >= 4; an element with a NaN or infinite draw gives NaN."""
-        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
-            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
-        n_iter, _, size = store.shape
+        n_iter, size = self._store_shape(store)
         if n_iter < 4:
             raise ValueError("rank-normalised R-hat and ESS need at least 4 stored iterations")
         idx, n = self._store_index(index, size)
         rhat, bulk, tail = self.empty(n), self.empty(n), self.empty(n)
-        check(lib.omc_store_rank_diagnostics(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n,
+        check(lib.omc_store_rank_diagnostics(self._ctx, n_iter, size, self._p(store), _ptr(idx), n,
                                              self._p(rhat), self._p(bulk), self._p(tail)))
         return rhat, bulk, tail
 
@@ -1412,9 +1401,7 @@ class Engine:
         each inside (0, 1); a scalar is one probability (n_prob = 1).  omit_nan leaves NaN draws out; without it a column
         with a NaN gives NaN.  A column with an infinite draw or without a valid draw gives NaN."""
         torch = _torch()
-        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
-            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
-        n_iter, _, size = store.shape
+        n_iter, size = self._store_shape(store)
         probs = np.atleast_1d(np.asarray(prob, dtype=np.float64))
         if probs.ndim != 1 or not 1 <= probs.size <= 8:
             raise ValueError("prob must be a number or a sequence of 1 to 8 numbers")
@@ -1425,7 +1412,7 @@ class Engine:
         out = self.empty(*lead, n, 2)
         cnt = torch.empty(lead[1:] + (n,), dtype=torch.int64, device=self.device)
         host = (C.c_double * probs.size)(*probs.tolist())
-        check(lib.omc_store_hdi(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n, host, probs.size,
+        check(lib.omc_store_hdi(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, host, probs.size,
                                 int(not pooled), int(bool(omit_nan)), self._p(out), cnt.data_ptr()))
         return out, cnt
 
@@ -1456,17 +1443,15 @@ class Engine:
         "argmin" / "argmax" the position of the first NaN.  a, b: host arrays or device tensors with one value per SELECTED
         element, scalars are broadcast.  "sum" is within n_idx 2^-53 sum|terms| of the exact sum, everything else is exact."""
         torch = _torch()
-        if store.dim() != 3 or store.shape[1] != self.n_chains or not store.is_contiguous():
-            raise ValueError("store must be a contiguous (n_iter, C, size) tensor")
+        n_iter, size = self._store_shape(store)
         code = self.REDUCE_OPS.get(op)
         if code is None:
             raise ValueError(f"unknown reduction {op!r}: one of {', '.join(self.REDUCE_OPS)}")
-        n_iter, _, size = store.shape
         idx, n = self._store_index(index, size)
         av, bv = self._reduce_vector(a, n, "a"), self._reduce_vector(b, n, "b")
         out = self.empty(n_iter, self.n_chains)
         cnt = torch.empty((n_iter, self.n_chains), dtype=torch.int64, device=self.device)
-        st = lib.omc_store_reduce(self._ctx, n_iter, size, self._p(store), None if idx is None else idx.data_ptr(), n, code,
+        st = lib.omc_store_reduce(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, code,
                                   int(bool(omit_nan)), self._p(av), self._p(bv), self._p(out), cnt.data_ptr())
         if st == _abi.INVALID_ARG:  # the library says which argument
             raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())

@@ -2,35 +2,15 @@
 keeps its lag accumulators and its ring of lagged operands in registers -- no scratch, no spilled VGPRs."""
 
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_usage import HIPCC, compile_usage, not_in_registers
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 
 
 def test_diag_kernels_need_no_scratch(tmp_path):
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", f"-I{ROOT}/include",
-           "-mllvm", "-instcombine-max-copied-from-constant-users=100000",  # as openmcmc_amd/csrc/Makefile
-           "-c", f"{ROOT}/openmcmc_amd/csrc/omc_diag.hip", "-o", str(tmp_path / "omc_diag.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    usage, name = {}, None
-    for line in (out.stderr + out.stdout).splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-        m = re.search(r"(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
+    usage = compile_usage("omc_diag.hip", tmp_path)
     kernels = {k: v for k, v in usage.items() if "k_diag_" in k}
     assert len(kernels) >= 4, sorted(usage)  # means, lag blocks, short-series form, Geyer step
-    bad = {k: v for k, v in kernels.items() if v.get("ScratchSize [bytes/lane]") != 0 or v.get("VGPRs Spill") != 0}
-    assert not bad, bad
+    assert not not_in_registers(kernels)

@@ -3,36 +3,16 @@ four prefetched draws, its edge pointers and its three outside counters stay in 
 all four instantiations, and so does every other kernel of the file."""
 
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_usage import HIPCC, compile_usage, not_in_registers
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 
 
 def test_hist_kernels_need_no_scratch(tmp_path):
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", f"-I{ROOT}/include",
-           "-mllvm", "-instcombine-max-copied-from-constant-users=100000",  # as openmcmc_amd/csrc/Makefile
-           "-c", f"{ROOT}/openmcmc_amd/csrc/omc_hist.hip", "-o", str(tmp_path / "omc_hist.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    usage, name = {}, None
-    for line in (out.stderr + out.stdout).splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-        m = re.search(r"(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
+    usage = compile_usage("omc_hist.hip", tmp_path)
     kernels = {k: v for k, v in usage.items() if "k_hist_" in k}
     assert sum("k_hist_count" in k for k in kernels) == 4, sorted(usage)  # shared / per-element edges x guess / bisection
     assert any("k_hist_minmax_part" in k for k in kernels) and any("k_hist_check" in k for k in kernels), sorted(usage)
-    bad = {k: v for k, v in kernels.items() if v.get("ScratchSize [bytes/lane]") != 0 or v.get("VGPRs Spill") != 0}
-    assert not bad, bad
+    assert not not_in_registers(kernels)
