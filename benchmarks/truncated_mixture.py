@@ -1,4 +1,4 @@
-"""Cost of truncated mixture priors (omc_truncmix.hip).  Prints one JSON line with
+"""Cost of truncated mixture priors (omc_truncmix.hip, omc_trunc_dense.h).  Prints one JSON line with
   * cfg5 (reversible jump over Gaussian-kernel knots next to a GMRF, n = 5000, n_max = 20, 512 chains) in ms per sweep,
     with and without beta >= 0 on the coefficients' mixture prior;
   * omc_small_gibbs_truncated next to omc_small_sample_canonical at C = 512, kmax = 20 (in-kernel streams, live counts

@@ -139,6 +139,32 @@ extern "C" omc_status omc_gram_mfma_launch(omc_ctx* ctx, int64_t n, int64_t p, c
 
 #define OMC_NO_BAD_CHAIN 0x7fffffffffffffffLL
 
+// blocks of `block` that cover n
+inline unsigned omc_grid1(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
+
+// An entry point's one launch on the context's device and stream, and its status.  Grid, block and dynamic LDS stay at the call site.
+template <class... P, class... A>
+omc_status omc_launch(omc_ctx* ctx, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, A... args) {
+  OMC_HIP_CHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args...);
+  OMC_HIP_CHECK(hipGetLastError());
+  return OMC_OK;
+}
+
+// sum over the wave, butterfly order: lanes l and l^sh add the same two values, so every lane ends with the same bits
+__device__ __forceinline__ double omc_wave_sum(double v) {
+#pragma unroll
+  for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh, 64);
+  return v;
+}
+// v of lane i (i wave-uniform) in every lane, through two scalar reads
+__device__ __forceinline__ double omc_readlane_d(double v, int i) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, i);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), i);
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
 // Workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains the vector-memory counter, which
 // would expose the latency of prefetched global loads (and of stores) at every step of a loop whose threads communicate through
 // LDS alone.
@@ -167,7 +193,8 @@ __device__ __forceinline__ void omc_lds_barrier() { asm volatile("s_waitcnt lgkm
 //                               omc_tridiag.hip makes the same numbers: its sweep draw plus the block's position)
 //                   bit  40     prior draw of the start value: (1 << 40) + position (mcmc.py)
 //                   bits 44-47  `sub`, several draws of one purpose under one draw index (Gamma.rvs, Normal columns)
-//   block         ctr0: position within the draw.  A Gamma(a) draw reads blocks 0 .. OMC_GAMMA_BLOCKS - 1; mixture
+//   block         ctr0: position within the draw.  Element e of a vector lives in half e & 1 of block sub + (e >> 1)
+//                 (omc_elem_uniform, omc_elem_normal).  A Gamma(a) draw reads blocks 0 .. OMC_GAMMA_BLOCKS - 1; mixture
 //                 component k of k_mixture_normal_gamma adds (k + 1) << OMC_COMPONENT_SHIFT (k < 255), so its
 //                 blocks lie above those of every plain gamma draw of the same draw index.
 enum : uint32_t { OMC_RNG_NORMAL = 0, OMC_RNG_GAMMA = 1, OMC_RNG_UNIFORM = 2, OMC_RNG_RAW = 3 };
@@ -245,6 +272,14 @@ __device__ __forceinline__ double omc_chain_uniform(const double* u_in, int64_t 
   if (u_in) return u_in[idx];
   const uint4 w = omc_rng_block(key, global_chain, block);
   return omc_u53(w.x, w.y);
+}
+// Element e of a chain's vector of uniforms: the injected u_in[idx], or half e & 1 of block sub + (e >> 1) of its stream
+// (omc_elem_normal, behind omc_normal_pair, is the same for normals)
+__device__ __forceinline__ double omc_elem_uniform(const double* u_in, int64_t idx, const omc_rng_key& key, int64_t global_chain,
+                                                   int64_t e, uint32_t sub = 0u) {
+  if (u_in) return u_in[idx];
+  const uint4 w = omc_rng_block(key, global_chain, sub + (uint32_t)(e >> 1));
+  return (e & 1) ? omc_u53(w.z, w.w) : omc_u53(w.x, w.y);
 }
 
 // ---- lean fp64 elementary functions for the Box-Muller transform -------------------------------
@@ -451,6 +486,14 @@ __host__ __device__ inline void omc_normal_pair(uint4 w, double& n0, double& n1)
   const bool swap = (int32_t)(w.w << 21) < 0;                          // random swap (bit 10)
   n0 = (swap ? cs : sn) * r;
   n1 = (swap ? sn : cs) * r;
+}
+// Element e of a chain's vector of normals: the injected z_in[idx], or half e & 1 of block sub + (e >> 1) of its stream
+__device__ __forceinline__ double omc_elem_normal(const double* z_in, int64_t idx, const omc_rng_key& key, int64_t global_chain,
+                                                  int64_t e, uint32_t sub = 0u) {
+  if (z_in) return z_in[idx];
+  double n0, n1;
+  omc_normal_pair(omc_rng_block(key, global_chain, sub + (uint32_t)(e >> 1)), n0, n1);
+  return (e & 1) ? n1 : n0;
 }
 
 // Marsaglia & Tsang (2000) Gamma(a,1), a > 0, from the chain's Philox stream.

@@ -20,8 +20,6 @@
 #include "omc_common.h"
 #include "omc_truncnorm.h"
 
-omc_status omc_ensure_bytes(omc_ctx* ctx, void** buf, size_t* have, size_t need);  // omc_dense.hip
-
 #define KN_THREADS 1024
 
 __device__ __forceinline__ double kn_block_sum(double v, double* red, int tid) {
@@ -57,6 +55,9 @@ __global__ void __launch_bounds__(64) k_knot_propose(int64_t C, int64_t chain_of
   const int64_t c = e / kmax, j = e - c * kmax;
   if (!((double)j < count[c])) return;
   const double mu = theta[e];
+  // Whole blocks, words 0-1 of each (not the two halves of one block as omc_elem_uniform lays a vector out): the host route
+  // makes knot j's proposal with omc_rw_propose (p = 1, sub = 2 j) and its decision with omc_mh_accept (sub = 2 j + 1), and this
+  // kernel must read the same words
   double d, u;
   if (inj_z) {
     d = inj_z[j * C + c];

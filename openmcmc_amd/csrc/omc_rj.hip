@@ -10,10 +10,6 @@
 #include "omc_common.h"
 #include "omc_truncnorm.h"
 
-omc_status omc_ensure_bytes(omc_ctx* ctx, void** buf, size_t* have, size_t need);  // omc_dense.hip
-
-static inline unsigned grid1(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
 // a*b + c with the product rounded first (no FMA contraction): what numpy's `mu + z * step` computes
 __device__ __forceinline__ double mul_add_2r(double a, double b, double c) {
 #pragma clang fp contract(off)
@@ -36,6 +32,8 @@ __global__ void k_rw_propose(int64_t C, int64_t chain_offset, int64_t p, const d
     double out = mu;
     if (active) {
       const double s = step[e * ses];
+      // element e of the stream as omc_elem_uniform / omc_elem_normal read it, written out: one Philox block serves either kind
+      // (through the two helpers the ten rounds are compiled twice: 529 -> 609 instructions)
       double d;
       if (inject) {
         d = inject[c * p + e];
@@ -87,15 +85,7 @@ __global__ void k_mala_diag(int64_t C, int64_t chain_offset, int64_t kmax, const
     const double m = x[t] + 0.5 * (grad[t] / prec);
     double xo;
     if (propose) {
-      double z;
-      if (z_in) {
-        z = z_in[t];
-      } else {
-        double n0, n1;
-        omc_normal_pair(omc_rng_block(key, chain_offset + c, sub + (uint32_t)(j >> 1)), n0, n1);
-        z = (j & 1) ? n1 : n0;
-      }
-      xo = m + z / L;
+      xo = m + omc_elem_normal(z_in, t, key, chain_offset + c, j, sub) / L;
       x_other[t] = xo;
     } else {
       xo = x_other[t];
@@ -180,59 +170,45 @@ __global__ void k_ragged_resize(int64_t C, int64_t rows, int64_t kmax, const dou
 }
 
 // ------------------------------------------------------------------------------------------------
-// per-chain design matrices B_c (n x kmax, column j contiguous: B[c*kmax*n + j*n + i])
+// per-chain design matrices B_c (n x kmax, column j contiguous: B[c*kmax*n + j*n + i]).  W nodes per thread: W = 2 (16-byte accesses)
+// wants n even and every vector 16-byte aligned.
+template <int W>
 __global__ void k_design_predict_batched(int64_t C, int64_t n, int64_t kmax, const double* B, const double* coef,
                                          const double* add_chain, const double* add_shared, double alpha,
                                          const double* chain_scale, double* out) {
-  const int64_t c = blockIdx.y;
-  const double* Bc = B + c * kmax * n;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    double s = 0.0;
+  typedef double vec __attribute__((ext_vector_type(W)));
+  const int64_t c = blockIdx.y, nv = n / W;
+  const vec* Bc = reinterpret_cast<const vec*>(B + c * kmax * n);
+  const vec* ac = add_chain ? reinterpret_cast<const vec*>(add_chain + c * n) : nullptr;
+  const vec* as = add_shared ? reinterpret_cast<const vec*>(add_shared) : nullptr;
+  vec* oc = reinterpret_cast<vec*>(out + c * n);
+  const double cs = chain_scale ? chain_scale[c] : 1.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+    double s[W] = {};
     // eight columns at a time: the coefficients first (wave-uniform), then the loads of the live columns issued
     // together, then the sums in column order (a test-and-load per column serialises the memory latencies)
     for (int64_t j0 = 0; j0 < kmax; j0 += 8) {
-      double cf[8], bv[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) cf[u] = (j0 + u < kmax) ? coef[c * kmax + j0 + u] : 0.0;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) bv[u] = (cf[u] != 0.0) ? Bc[(j0 + u) * n + i] : 0.0;
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (cf[u] != 0.0) s = fma(bv[u], cf[u], s);
-    }
-    double v = alpha * s + (add_chain ? add_chain[c * n + i] : 0.0) + (add_shared ? add_shared[i] : 0.0);
-    if (chain_scale) v *= chain_scale[c];
-    out[c * n + i] = v;
-  }
-}
-
-// the same with two nodes per thread (16-byte accesses): n even, every vector 16-byte aligned
-__global__ void k_design_predict_batched2(int64_t C, int64_t n, int64_t kmax, const double* B, const double* coef,
-                                          const double* add_chain, const double* add_shared, double alpha,
-                                          const double* chain_scale, double* out) {
-  const int64_t c = blockIdx.y, n2 = n / 2;
-  const double2* Bc = reinterpret_cast<const double2*>(B + c * kmax * n);
-  const double2* ac = add_chain ? reinterpret_cast<const double2*>(add_chain + c * n) : nullptr;
-  const double2* as = add_shared ? reinterpret_cast<const double2*>(add_shared) : nullptr;
-  double2* oc = reinterpret_cast<double2*>(out + c * n);
-  const double cs = chain_scale ? chain_scale[c] : 1.0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
-    double s0 = 0.0, s1 = 0.0;
-    for (int64_t j0 = 0; j0 < kmax; j0 += 8) {
       double cf[8];
-      double2 bv[8];
+      vec bv[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) cf[u] = (j0 + u < kmax) ? coef[c * kmax + j0 + u] : 0.0;
 #pragma unroll
-      for (int u = 0; u < 8; ++u) bv[u] = (cf[u] != 0.0) ? Bc[(j0 + u) * n2 + i] : make_double2(0.0, 0.0);
+      for (int u = 0; u < 8; ++u) bv[u] = (cf[u] != 0.0) ? Bc[(j0 + u) * nv + i] : vec(0.0);
 #pragma unroll
       for (int u = 0; u < 8; ++u)
-        if (cf[u] != 0.0) { s0 = fma(bv[u].x, cf[u], s0); s1 = fma(bv[u].y, cf[u], s1); }
+        if (cf[u] != 0.0) {
+#pragma unroll
+          for (int w = 0; w < W; ++w) s[w] = fma(bv[u][w], cf[u], s[w]);
+        }
     }
-    const double2 a = ac ? ac[i] : make_double2(0.0, 0.0), b = as ? as[i] : make_double2(0.0, 0.0);
-    double v0 = alpha * s0 + a.x + b.x, v1 = alpha * s1 + a.y + b.y;
-    if (chain_scale) { v0 *= cs; v1 *= cs; }
-    oc[i] = make_double2(v0, v1);
+    const vec a = ac ? ac[i] : vec(0.0), b = as ? as[i] : vec(0.0);
+    vec v;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      v[w] = alpha * s[w] + a[w] + b[w];
+      if (chain_scale) v[w] *= cs;
+    }
+    oc[i] = v;
   }
 }
 
@@ -436,6 +412,33 @@ __global__ void k_gram_reduce(int64_t C, int64_t len, int parts, const double* i
 //   Q = diag(prior_prec) + lik_scale * G,  rhs = prior_prec * prior_mean + lik_scale * g,  on the live k x k block
 // one wave per chain, lane = row, matrix in LDS.
 #define SMALL_KMAX 64
+// Right-looking Cholesky of the k x k matrix in LDS (row stride ld), column by column in natural order (as np.linalg.cholesky /
+// SuperLU without permutation): one wave, lane = row, vec = k doubles of LDS.  Returns true at the first pivot that is not
+// positive; adds sum log d_j of the pivots to logdet.  FACTOR: L is left in the lower triangle, the diagonal included (without
+// it only the trailing updates are made: the log-determinant is all the caller wants).
+template <bool FACTOR>
+__device__ __forceinline__ bool small_cholesky(double* L, int ld, int k, int lane, double* vec, double& logdet) {
+  bool fail = false;
+  for (int j = 0; j < k; ++j) {
+    const double d = L[j * ld + j];
+    if (!(d > 0.0)) { fail = true; break; }
+    const double sd = sqrt(d);
+    logdet += log(d);
+    double lij = 0.0;
+    if (lane > j && lane < k) lij = L[lane * ld + j] / sd;
+    __syncthreads();
+    if (FACTOR && lane == j) L[j * ld + j] = sd;
+    if (lane > j && lane < k) {
+      if (FACTOR) L[lane * ld + j] = lij;
+      vec[lane] = lij;
+    }
+    __syncthreads();
+    if (lane > j && lane < k)
+      for (int t = j + 1; t <= lane; ++t) L[lane * ld + t] -= lij * vec[t];
+    __syncthreads();
+  }
+  return fail;
+}
 __global__ void __launch_bounds__(64) k_small_sample_canonical(int64_t C, int64_t chain_offset, int kmax, const double* gram,
                                                                const double* gram_rhs, const double* lik_scale,
                                                                const double* prior_prec, const double* prior_mean,
@@ -457,26 +460,8 @@ __global__ void __launch_bounds__(64) k_small_sample_canonical(int64_t C, int64_
     }
   }
   __syncthreads();
-  // right-looking Cholesky, column by column (natural order, as np.linalg.cholesky / SuperLU without permutation)
-  bool fail = false;
-  for (int j = 0; j < k; ++j) {
-    const double d = L[j * ld + j];
-    if (!(d > 0.0)) { fail = true; break; }
-    const double sd = sqrt(d);
-    double lij = 0.0;
-    if (lane > j && lane < k) lij = L[lane * ld + j] / sd;
-    __syncthreads();
-    if (lane == j) L[j * ld + j] = sd;
-    if (lane > j && lane < k) {
-      L[lane * ld + j] = lij;
-      vec[lane] = lij;
-    }
-    __syncthreads();
-    if (lane > j && lane < k)
-      for (int t = j + 1; t <= lane; ++t) L[lane * ld + t] -= lij * vec[t];
-    __syncthreads();
-  }
-  if (fail) {
+  double logdet = 0.0;  // (not wanted here)
+  if (small_cholesky<true>(L, ld, k, lane, vec, logdet)) {
     if (lane == 0) atomicMin((unsigned long long*)bad, (unsigned long long)c);
     if (lane < kmax) x_out[c * kmax + lane] = NAN;
     return;
@@ -485,13 +470,7 @@ __global__ void __launch_bounds__(64) k_small_sample_canonical(int64_t C, int64_
   double rhs = 0.0, zz = 0.0;
   if (lane < k) {
     rhs = tau * gram_rhs[c * kmax + lane] + prior_prec[c * kmax + lane] * (prior_mean ? prior_mean[c * kmax + lane] : 0.0);
-    if (z_in) {
-      zz = z_in[c * kmax + lane];
-    } else {
-      double n0, n1;
-      omc_normal_pair(omc_rng_block(key, chain_offset + c, (uint32_t)(lane >> 1)), n0, n1);
-      zz = (lane & 1) ? n1 : n0;
-    }
+    zz = omc_elem_normal(z_in, c * kmax + lane, key, chain_offset + c, lane);
   }
   for (int j = 0; j < k; ++j) {
     if (lane == j) { rhs /= L[j * ld + j]; vec[0] = rhs; }
@@ -562,6 +541,9 @@ __device__ double lu_solve_wave(double* A, int ld, int m, int nrhs, int* iscratc
   return det;
 }
 
+// log N(t scale; 0, scale^2) as gmrf.multivariate_normal_pdf computes it with Q = 1 / scale^2 (reversible_jump.py:255-257)
+__device__ __forceinline__ double gauss1_logpdf(double t, double scale) { return 0.5 * (-2.0 * log(scale) - OMC_LOG_2PI - t * t); }
+
 // ReversibleJump.matched_birth_transition / matched_death_transition (reversible_jump.py:195-308)
 __global__ void __launch_bounds__(64) k_rj_matched(int64_t C, int64_t chain_offset, int kmax, const double* gram_cur,
                                                    const double* gram_prop, const double* count, const int* birth,
@@ -621,10 +603,9 @@ __global__ void __launch_bounds__(64) k_rj_matched(int64_t C, int64_t chain_offs
       if (has_limits) {
         last = omc_truncated_normal_rv(mu, scale, lim_lo, lim_hi, d);
         la_f = omc_truncated_normal_log_pdf(last, mu, scale, lim_lo, lim_hi);
-      } else {  // gmrf.sample_normal / multivariate_normal_pdf with Q = 1/scale^2 (reversible_jump.py:255-257)
+      } else {  // gmrf.sample_normal, then its density
         last = mul_add_2r(d, scale, mu);
-        const double t = (last - mu) / scale;
-        la_f = 0.5 * (-2.0 * log(scale) - 1.8378770664093453 - t * t);
+        la_f = gauss1_logpdf((last - mu) / scale, scale);
       }
       lq_fwd[c] += la_f;
       lq_rev[c] += log(det);
@@ -648,8 +629,7 @@ __global__ void __launch_bounds__(64) k_rj_matched(int64_t C, int64_t chain_offs
       if (has_limits) {
         la_r = omc_truncated_normal_log_pdf(del_val, 0.0, scale, lim_lo, lim_hi);
       } else {
-        const double t = del_val / scale;
-        la_r = 0.5 * (-2.0 * log(scale) - 1.8378770664093453 - t * t);
+        la_r = gauss1_logpdf(del_val / scale, scale);
       }
       lq_fwd[c] += log(det);
       lq_rev[c] += la_r;
@@ -688,28 +668,14 @@ __global__ void __launch_bounds__(64) k_small_spd_ops(int64_t C, int k, const do
     if (Av_out && lane < k) Av_out[c * k + lane] = av;
     if (quad_out) {
       double q = (lane < k) ? av * vec[lane] : 0.0;
-      for (int s = 32; s >= 1; s >>= 1) q += __shfl_xor(q, s, 64);
+      q = omc_wave_sum(q);
       if (lane == 0) quad_out[c] = q;
     }
   }
   if (!logdet_out) return;
   __syncthreads();
-  bool fail = false;
   double acc = 0.0;
-  for (int j = 0; j < k; ++j) {
-    const double d = L[j * ld + j];
-    if (!(d > 0.0)) { fail = true; break; }
-    const double sd = sqrt(d);
-    acc += log(d);
-    double lij = 0.0;
-    if (lane > j && lane < k) lij = L[lane * ld + j] / sd;
-    __syncthreads();
-    if (lane > j && lane < k) vec[lane] = lij;
-    __syncthreads();
-    if (lane > j && lane < k)
-      for (int t = j + 1; t <= lane; ++t) L[lane * ld + t] -= lij * vec[t];
-    __syncthreads();
-  }
+  const bool fail = small_cholesky<false>(L, ld, k, lane, vec, acc);
   if (lane == 0) {
     logdet_out[c] = fail ? NAN : acc;
     if (fail) atomicMin((unsigned long long*)bad, (unsigned long long)c);
@@ -725,25 +691,19 @@ omc_status omc_rw_propose(omc_ctx* ctx, int64_t p, const double* x, int64_t x_ch
                           double* lq_rev) {
   if (!ctx || p < 1 || !x || !step || !z || !lq_fwd || !lq_rev || ((lower == nullptr) != (upper == nullptr)))
     return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_rw_propose, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, p, x, x_chain_stride, x_elem_stride, step, step_elem_stride, lower, upper, count,
-                     index, draw_inject, omc_make_key(ctx->seed, draw_index, lower ? OMC_RNG_UNIFORM : OMC_RNG_NORMAL), sub,
-                     z, z_chain_stride, z_elem_stride, lq_fwd, lq_rev);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_rw_propose, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, ctx->chain_offset, p, x,
+                    x_chain_stride, x_elem_stride, step, step_elem_stride, lower, upper, count, index, draw_inject,
+                    omc_make_key(ctx->seed, draw_index, lower ? OMC_RNG_UNIFORM : OMC_RNG_NORMAL), sub, z, z_chain_stride,
+                    z_elem_stride, lq_fwd, lq_rev);
 }
 
 omc_status omc_mala_diag(omc_ctx* ctx, int64_t kmax, const double* x, const double* grad, const double* hdiag,
                          const double* count, double step, int32_t propose, const double* z_inject, uint64_t draw_index,
                          uint32_t sub, double* x_other, double* lq) {
   if (!ctx || kmax < 1 || !x || !grad || !hdiag || !(step > 0.0) || !x_other || !lq) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_mala_diag, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains, ctx->chain_offset,
-                     kmax, x, grad, hdiag, count, step, (int)propose, z_inject,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL), sub, x_other, lq, ctx->d_bad_chain);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_mala_diag, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, ctx->chain_offset, kmax, x, grad,
+                    hdiag, count, step, (int)propose, z_inject, omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL), sub, x_other,
+                    lq, ctx->d_bad_chain);
 }
 
 omc_status omc_mh_accept(omc_ctx* ctx, const double* lp_cur, const double* lp_prop, const double* lq_fwd,
@@ -751,24 +711,17 @@ omc_status omc_mh_accept(omc_ctx* ctx, const double* lp_cur, const double* lp_pr
                          uint64_t draw_index, uint32_t sub, int32_t* accept, double* log_alpha, int64_t* accept_count,
                          int64_t* proposal_count) {
   if (!ctx || !lp_cur || !lp_prop || !accept) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_mh_accept, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, lp_cur, lp_prop, lq_fwd, lq_rev, count, index, u_inject,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), sub, (int*)accept, log_alpha,
-                     (long long*)accept_count, (long long*)proposal_count);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_mh_accept, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, ctx->chain_offset, lp_cur, lp_prop,
+                    lq_fwd, lq_rev, count, index, u_inject, omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), sub,
+                    (int*)accept, log_alpha, (long long*)accept_count, (long long*)proposal_count);
 }
 
 omc_status omc_chain_select(omc_ctx* ctx, const int32_t* accept, int64_t width, const double* src, double* dst) {
   if (!ctx || !accept || width < 1 || !src || !dst) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  unsigned gx = grid1(width, 256);
+  unsigned gx = omc_grid1(width, 256);
   if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(k_chain_select, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, ctx->n_chains, width,
-                     (const int*)accept, src, dst);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_chain_select, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->n_chains, width, (const int*)accept,
+                    src, dst);
 }
 
 omc_status omc_chain_select_multi(omc_ctx* ctx, const int32_t* accept, int32_t n_items, const int64_t* widths,
@@ -785,14 +738,11 @@ omc_status omc_chain_select_multi(omc_ctx* ctx, const int32_t* accept, int32_t n
     it.dst[e] = on ? dsts[e] : nullptr;
     if (on && widths[e] > wmax) wmax = widths[e];
   }
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
   // few workgroups per (chain, entry): most chains reject and their workgroups only cost their dispatch
-  unsigned gx = grid1(wmax, 256 * 16);
+  unsigned gx = omc_grid1(wmax, 256 * 16);
   if (gx > 16) gx = 16;
-  hipLaunchKernelGGL(k_chain_select_multi, dim3(gx, (unsigned)ctx->n_chains, (unsigned)n_items), dim3(256), 0, ctx->stream,
-                     ctx->n_chains, (const int*)accept, it);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_chain_select_multi, dim3(gx, (unsigned)ctx->n_chains, (unsigned)n_items), dim3(256), 0, ctx->n_chains,
+                    (const int*)accept, it);
 }
 
 omc_status omc_ragged_resize(omc_ctx* ctx, int64_t rows, int64_t kmax, const double* count, const int32_t* birth,
@@ -800,14 +750,10 @@ omc_status omc_ragged_resize(omc_ctx* ctx, int64_t rows, int64_t kmax, const dou
                              int64_t chain_stride, int64_t row_stride, int64_t col_stride) {
   if (!ctx || rows < 1 || kmax < 1 || !count || !birth || !del_index || !src || !dst || src == dst)
     return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  unsigned gx = grid1(rows * kmax, 256);
+  unsigned gx = omc_grid1(rows * kmax, 256);
   if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(k_ragged_resize, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, ctx->n_chains, rows,
-                     kmax, count, (const int*)birth, (const long long*)del_index, new_vals, src, dst, chain_stride,
-                     row_stride, col_stride);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_ragged_resize, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->n_chains, rows, kmax, count,
+                    (const int*)birth, (const long long*)del_index, new_vals, src, dst, chain_stride, row_stride, col_stride);
 }
 
 omc_status omc_gaussian_basis(omc_ctx* ctx, int64_t n, int64_t kmax, const double* X, const double* knots,
@@ -816,34 +762,22 @@ omc_status omc_gaussian_basis(omc_ctx* ctx, int64_t n, int64_t kmax, const doubl
   if (!ctx || n < 1 || kmax < 1 || !X || !knots || !B || column >= kmax || (!scales && !(scale0 > 0.0)) ||
       (prev_count && !count))
     return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  unsigned gx = grid1(n, 256);
+  unsigned gx = omc_grid1(n, 256);
   if (gx > 32) gx = 32;
-  hipLaunchKernelGGL(k_gaussian_basis, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, ctx->n_chains, n, kmax,
-                     X, knots, scales, scale0, count, prev_count, column, B);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_gaussian_basis, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->n_chains, n, kmax, X, knots, scales,
+                    scale0, count, prev_count, column, B);
 }
 
 omc_status omc_design_predict_batched(omc_ctx* ctx, int64_t n, int64_t kmax, const double* B, const double* coef,
                                       const double* add_chain, const double* add_shared, double alpha,
                                       const double* chain_scale, double* out) {
   if (!ctx || n < 1 || kmax < 1 || !B || !coef || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const uintptr_t align = (uintptr_t)B | (uintptr_t)out | (uintptr_t)add_chain | (uintptr_t)add_shared;
-  if (n % 2 == 0 && (align & 15u) == 0) {
-    unsigned gx = grid1(n / 2, 256);
-    if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(k_design_predict_batched2, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream,
-                       ctx->n_chains, n, kmax, B, coef, add_chain, add_shared, alpha, chain_scale, out);
-  } else {
-    unsigned gx = grid1(n, 256);
-    if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(k_design_predict_batched, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream,
-                       ctx->n_chains, n, kmax, B, coef, add_chain, add_shared, alpha, chain_scale, out);
-  }
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  const bool wide = n % 2 == 0 && (align & 15u) == 0;  // two nodes per thread
+  unsigned gx = omc_grid1(wide ? n / 2 : n, 256);
+  if (gx > 64) gx = 64;
+  return omc_launch(ctx, wide ? k_design_predict_batched<2> : k_design_predict_batched<1>, dim3(gx, (unsigned)ctx->n_chains), dim3(256),
+                    0, ctx->n_chains, n, kmax, B, coef, add_chain, add_shared, alpha, chain_scale, out);
 }
 
 omc_status omc_design_resid_sq_batched(omc_ctx* ctx, int64_t n, int64_t kmax, const double* B, const double* coef,
@@ -920,13 +854,10 @@ omc_status omc_small_sample_canonical(omc_ctx* ctx, int64_t kmax, const double* 
                                       const double* count, const double* z_inject, uint64_t draw_index, double* x,
                                       double* mu) {
   if (!ctx || kmax < 1 || kmax > SMALL_KMAX || !gram || !gram_rhs || !prior_prec || !x) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const size_t lds = (size_t)(kmax * (kmax + 1) + kmax + 2) * sizeof(double);
-  hipLaunchKernelGGL(k_small_sample_canonical, dim3((unsigned)ctx->n_chains), dim3(64), lds, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, (int)kmax, gram, gram_rhs, lik_scale, prior_prec, prior_mean, count, z_inject,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL), x, mu, ctx->d_bad_chain);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_small_sample_canonical, dim3((unsigned)ctx->n_chains), dim3(64), lds, ctx->n_chains, ctx->chain_offset,
+                    (int)kmax, gram, gram_rhs, lik_scale, prior_prec, prior_mean, count, z_inject,
+                    omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL), x, mu, ctx->d_bad_chain);
 }
 
 omc_status omc_rj_matched_transition(omc_ctx* ctx, int64_t kmax, const double* gram_cur, const double* gram_prop,
@@ -937,26 +868,20 @@ omc_status omc_rj_matched_transition(omc_ctx* ctx, int64_t kmax, const double* g
   if (!ctx || kmax < 1 || kmax > SMALL_KMAX || !gram_cur || !gram_prop || !count || !birth || !del_index || !coef_cur ||
       !(scale > 0.0) || !coef_prop || !lq_fwd || !lq_rev)
     return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const size_t lds = (size_t)(kmax * (2 * kmax + 1) + kmax * (kmax + 2)) * sizeof(double);
-  hipLaunchKernelGGL(k_rj_matched, dim3((unsigned)ctx->n_chains), dim3(64), lds, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, (int)kmax, gram_cur, gram_prop, count, (const int*)birth,
-                     (const long long*)del_index, coef_cur, scale, (int)has_limits, lim_lo, lim_hi, draw_inject,
-                     omc_make_key(ctx->seed, draw_index, has_limits ? OMC_RNG_UNIFORM : OMC_RNG_NORMAL), sub, coef_prop,
-                     lq_fwd, lq_rev);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_rj_matched, dim3((unsigned)ctx->n_chains), dim3(64), lds, ctx->n_chains, ctx->chain_offset, (int)kmax,
+                    gram_cur, gram_prop, count, (const int*)birth, (const long long*)del_index, coef_cur, scale, (int)has_limits,
+                    lim_lo, lim_hi, draw_inject,
+                    omc_make_key(ctx->seed, draw_index, has_limits ? OMC_RNG_UNIFORM : OMC_RNG_NORMAL), sub, coef_prop, lq_fwd,
+                    lq_rev);
 }
 
 omc_status omc_small_spd_ops(omc_ctx* ctx, int64_t k, const double* A, const double* v, double* Av_out, double* quad_out,
                              double* logdet_out) {
   if (!ctx || k < 1 || k > SMALL_KMAX || !A || ((Av_out || quad_out) && !v)) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const size_t lds = (size_t)(k * (k + 1) + k) * sizeof(double);
-  hipLaunchKernelGGL(k_small_spd_ops, dim3((unsigned)ctx->n_chains), dim3(64), lds, ctx->stream, ctx->n_chains, (int)k, A, v, Av_out,
-                     quad_out, logdet_out, ctx->d_bad_chain);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_small_spd_ops, dim3((unsigned)ctx->n_chains), dim3(64), lds, ctx->n_chains, (int)k, A, v, Av_out,
+                    quad_out, logdet_out, ctx->d_bad_chain);
 }
 
 }  // extern "C"

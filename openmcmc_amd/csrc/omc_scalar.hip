@@ -3,6 +3,7 @@
 
 #include "omc_common.h"
 #include "omc_store_view.h"
+#include "omc_truncnorm.h"
 
 // log Gamma(shape, rate) density at v (lnorm = shape log rate - lgamma(shape)), as scipy.stats.gamma.logpdf: at v = 0 the
 // density is +inf for shape < 1, rate for shape = 1 and 0 for shape > 1; -inf below 0
@@ -31,7 +32,7 @@ __global__ void k_scaled_gauss_logpdf(int64_t C, double n, const double* scale, 
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const double s = scale ? scale[c] : 1.0;
-  const double lp = 0.5 * (n * log(s) + logdet_unscaled[0] - n * 1.8378770664093453 - s * quad[c]);
+  const double lp = 0.5 * (n * log(s) + logdet_unscaled[0] - n * OMC_LOG_2PI - s * quad[c]);
   out[c] = accumulate ? out[c] + lp : lp;
 }
 
@@ -53,7 +54,7 @@ __global__ void k_log_post_sum(int64_t C, LogpArgs P, double host_const, double*
     if (q.kind == 0) {
       const double s = q.scale ? q.scale[c] : 1.0;
       const double ld = (q.logdet_mult == 1.0) ? q.logdet[0] : q.logdet[0] * q.logdet_mult;
-      lp = 0.5 * (q.n * log(s) + ld - q.n * 1.8378770664093453 - s * q.quad[c]);
+      lp = 0.5 * (q.n * log(s) + ld - q.n * OMC_LOG_2PI - s * q.quad[c]);
     } else {
       lp = gamma_logpdf_at(q.x[c], q.shape, q.rate, P.lnorm[i]);
     }
@@ -172,32 +173,22 @@ __global__ void k_rj_move(int64_t C, int64_t chain_offset, long long n_max, doub
   }
 }
 
-// mean / variance over stored iterations (and chains when pooled): one lane per output element,
-// coalesced across the element index, Welford accumulation
-static inline unsigned grid1(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
 extern "C" {
 
 omc_status omc_normal_gamma_update(omc_ctx* ctx, double a0, double b0, int64_t n_pos, const double* quad,
                                    const double* g_inject, uint64_t draw_index, double* out) {
   if (!ctx || !quad || !out || n_pos < 0) return OMC_INVALID_ARG;
   if (!(a0 + 0.5 * (double)n_pos > 0.0)) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_normal_gamma, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, a0, b0, 0.5 * (double)n_pos, quad, g_inject,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_GAMMA), out, ctx->d_bad_chain);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_normal_gamma, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, ctx->chain_offset, a0, b0,
+                    0.5 * (double)n_pos, quad, g_inject, omc_make_key(ctx->seed, draw_index, OMC_RNG_GAMMA), out,
+                    ctx->d_bad_chain);
 }
 
 omc_status omc_scaled_gauss_logpdf(omc_ctx* ctx, int64_t n, const double* scale, const double* logdet_unscaled,
                                    const double* quad, double* out, int32_t accumulate) {
   if (!ctx || n < 1 || !logdet_unscaled || !quad || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_scaled_gauss_logpdf, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream,
-                     ctx->n_chains, (double)n, scale, logdet_unscaled, quad, out, (int)accumulate);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_scaled_gauss_logpdf, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, (double)n, scale,
+                    logdet_unscaled, quad, out, (int)accumulate);
 }
 
 omc_status omc_log_post_sum(omc_ctx* ctx, int32_t n_pieces, const omc_logp_piece* pieces, double host_const, double* out) {
@@ -216,21 +207,15 @@ omc_status omc_log_post_sum(omc_ctx* ctx, int32_t n_pieces, const omc_logp_piece
       return OMC_INVALID_ARG;
     }
   }
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_log_post_sum, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains, P, host_const, out);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_log_post_sum, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, P, host_const, out);
 }
 
 omc_status omc_gamma_logpdf(omc_ctx* ctx, const double* x, double shape, double rate, double* out,
                             int32_t accumulate) {
   if (!ctx || !x || !out || !(shape > 0.0) || !(rate > 0.0)) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const double lnorm = shape * log(rate) - lgamma(shape);
-  hipLaunchKernelGGL(k_gamma_logpdf, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains, x,
-                     shape, rate, lnorm, out, (int)accumulate);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_gamma_logpdf, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, x, shape, rate, lnorm, out,
+                    (int)accumulate);
 }
 
 omc_status omc_rj_move(omc_ctx* ctx, int64_t n_max, double birth_probability, const int64_t* n, const double* u_inject,
@@ -239,13 +224,10 @@ omc_status omc_rj_move(omc_ctx* ctx, int64_t n_max, double birth_probability, co
   if (!ctx || n_max < 1 || n_max > 0x7fffffffLL || !(birth_probability >= 0.0 && birth_probability <= 1.0) || !n ||
       !birth_out || !p_birth_out || !p_death_out || !del_index_out)
     return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_rj_move, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains, ctx->chain_offset,
-                     (long long)n_max, birth_probability, (const long long*)n, u_inject, (const long long*)idx_inject,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), birth_out, p_birth_out, p_death_out,
-                     (long long*)del_index_out, ctx->d_bad_chain, nullptr, nullptr, 0.0, nullptr, nullptr, nullptr);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_rj_move, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, ctx->chain_offset,
+                    (long long)n_max, birth_probability, (const long long*)n, u_inject, (const long long*)idx_inject,
+                    omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), birth_out, p_birth_out, p_death_out,
+                    (long long*)del_index_out, ctx->d_bad_chain, nullptr, nullptr, 0.0, nullptr, nullptr, nullptr);
 }
 
 omc_status omc_rj_move_densities(omc_ctx* ctx, int64_t n_max, double birth_probability, const double* count,
@@ -255,14 +237,11 @@ omc_status omc_rj_move_densities(omc_ctx* ctx, int64_t n_max, double birth_proba
   if (!ctx || n_max < 1 || n_max > 0x7fffffffLL || !(birth_probability >= 0.0 && birth_probability <= 1.0) || !count ||
       !birth_out || !del_index_out || !count_prop_out || !lq_fwd_out || !lq_rev_out)
     return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_rj_move, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains, ctx->chain_offset,
-                     (long long)n_max, birth_probability, (const long long*)nullptr, u_inject, (const long long*)idx_inject,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), birth_out, (double*)nullptr, (double*)nullptr,
-                     (long long*)del_index_out, ctx->d_bad_chain, count, density_chain, density_const, count_prop_out,
-                     lq_fwd_out, lq_rev_out);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_rj_move, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, ctx->chain_offset,
+                    (long long)n_max, birth_probability, (const long long*)nullptr, u_inject, (const long long*)idx_inject,
+                    omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), birth_out, (double*)nullptr, (double*)nullptr,
+                    (long long*)del_index_out, ctx->d_bad_chain, count, density_chain, density_const, count_prop_out, lq_fwd_out,
+                    lq_rev_out);
 }
 
 // dst[c][j] = src[c][j] for j < count[c], NaN beyond: one draw of a variable-size parameter into its store slab
@@ -279,11 +258,8 @@ omc_status omc_store_ragged(omc_ctx* ctx, int64_t width, const double* src, int6
                             double* dst, int64_t dst_chain_stride) {
   if (!ctx || width < 1 || !src || !count || !dst || src_chain_stride < width || dst_chain_stride < width)
     return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_store_ragged, dim3(grid1(ctx->n_chains * width, 256)), dim3(256), 0, ctx->stream, ctx->n_chains, width,
-                     src, src_chain_stride, count, dst, dst_chain_stride);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_store_ragged, dim3(omc_grid1(ctx->n_chains * width, 256)), dim3(256), 0, ctx->n_chains, width, src,
+                    src_chain_stride, count, dst, dst_chain_stride);
 }
 
 omc_status omc_store_moments(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int32_t pooled,
@@ -295,54 +271,46 @@ omc_status omc_store_moments(omc_ctx* ctx, int64_t n_iter, int64_t size, const d
 
 omc_status omc_fill_normal(omc_ctx* ctx, int64_t n, uint64_t draw_index, double* out, int64_t ld) {
   if (!ctx || n < 1 || !out || ld < n) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  unsigned gx = grid1((n + 1) / 2, 256);
+  unsigned gx = omc_grid1((n + 1) / 2, 256);
   if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(k_fill_normal, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, n, omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL), out, ld);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_fill_normal, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->n_chains, ctx->chain_offset, n,
+                    omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL), out, ld);
 }
 
 omc_status omc_fill_philox_u32(omc_ctx* ctx, int64_t n_words, uint64_t draw_index, uint32_t* out, int64_t ld) {
   if (!ctx || n_words < 1 || !out || ld < n_words) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  unsigned gx = grid1((n_words + 3) / 4, 256);
+  unsigned gx = omc_grid1((n_words + 3) / 4, 256);
   if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(k_fill_u32, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, n_words, omc_make_key(ctx->seed, draw_index, OMC_RNG_RAW), out, ld);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_fill_u32, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->n_chains, ctx->chain_offset, n_words,
+                    omc_make_key(ctx->seed, draw_index, OMC_RNG_RAW), out, ld);
 }
 
 }  // extern "C"
 
 // ---- log-density pieces for ragged parameters ---------------------
-// sum over a wave in a fixed order (butterfly): every lane ends with the total
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh, 64);
-  return v;
-}
-
 // one WAVE per chain (blockDim 256 = 4 chains): the lanes stride over the chain's elements, coalesced; with one thread per
-// chain a p = 500 coefficient vector cost 180 us of serial, strided loads and logs
+// chain a p = 500 coefficient vector cost 180 us of serial, strided loads and logs.  LIMITS: -inf for a chain with a live
+// x_j < lower or x_j > upper (entries at and beyond count[c] are not looked at); the sums are the same in the same order.
+template <bool LIMITS>
 __global__ void __launch_bounds__(256) k_diag_gauss_logpdf(int64_t C, int64_t kmax, const double* x, const double* mean, const double* prec,
-                                                           const double* count, double* out, int accumulate) {
+                                                           const double* count, double lower, double upper, double* out, int accumulate) {
   const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (c >= C) return;
   const int64_t k = count ? (int64_t)count[c] : kmax;
   double ld = 0.0, q = 0.0;
+  bool outside = false;
   for (int64_t j = lane; j < k; j += 64) {
     const double d = prec[c * kmax + j];
-    const double r = x[c * kmax + j] - (mean ? mean[c * kmax + j] : 0.0);
+    const double xv = x[c * kmax + j];
+    const double r = xv - (mean ? mean[c * kmax + j] : 0.0);
     ld += log(d);
     q = fma(d * r, r, q);
+    if (LIMITS) outside = outside || xv < lower || xv > upper;
   }
-  ld = wave_sum_d(ld);
-  q = wave_sum_d(q);
-  const double lp = 0.5 * (ld - (double)k * 1.8378770664093453 - q);
+  ld = omc_wave_sum(ld);
+  q = omc_wave_sum(q);
+  const double lp = (LIMITS && __ballot(outside) != 0) ? -INFINITY : 0.5 * (ld - (double)k * OMC_LOG_2PI - q);
   if (lane == 0) out[c] = accumulate ? out[c] + lp : lp;
 }
 
@@ -419,7 +387,7 @@ __global__ void __launch_bounds__(256) k_centered_rowdot(int64_t n, const double
   double acc = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 256)
     acc = fma(a[c * ld_a + i] - (ca ? ca[i] : 0.0), b[c * ld_b + i] - (cb ? cb[i] : 0.0), acc);
-  for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 64);
+  acc = omc_wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) out[c] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -440,13 +408,7 @@ __global__ void k_mixture_allocation(int64_t C, int64_t chain_offset, int64_t p,
     const double z = (yi - mean[c * mstride + k]) / sd;
     total += pr[k] * (exp(-(z * z) / 2.0) / 2.5066282746310002 / sd);
   }
-  double u;
-  if (u_in) {
-    u = u_in[t];
-  } else {
-    const uint4 w = omc_rng_block(key, chain_offset + c, (uint32_t)(i >> 1));
-    u = (i & 1) ? omc_u53(w.z, w.w) : omc_u53(w.x, w.y);
-  }
+  const double u = omc_elem_uniform(u_in, t, key, chain_offset + c, i);
   double cum = 0.0;
   int64_t pick = 0;
   for (int64_t k = 0; k < K; ++k) {  // np.sum(U > np.cumsum(prob / total))
@@ -472,7 +434,7 @@ __global__ void __launch_bounds__(256) k_categorical_logpmf(int64_t C, int64_t p
     }
     lp += log(prob[(prob_rows > 1 ? i * K : 0) + a]);
   }
-  lp = wave_sum_d(lp);
+  lp = omc_wave_sum(lp);
   if (lane == 0) out[c] = accumulate ? out[c] + lp : lp;
 }
 
@@ -492,8 +454,8 @@ __global__ void __launch_bounds__(256) k_mixture_normal_gamma(int64_t C, int64_t
       ss = fma(r, r, ss);
     }
   }
-  cnt = wave_sum_d(cnt);
-  ss = wave_sum_d(ss);
+  cnt = omc_wave_sum(cnt);
+  ss = omc_wave_sum(ss);
   if (lane != 0) return;
   const double a = a0[k] + 0.5 * cnt, b = b0[k] + 0.5 * ss;
   const double scale = (b == 0.0) ? INFINITY : 1.0 / b;
@@ -531,7 +493,7 @@ __global__ void __launch_bounds__(256) k_log_transform(int64_t n, const double* 
     out[c * ld_o + i] = v;
     acc += v;
   }
-  for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 64);
+  acc = omc_wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0 && sumlog) sumlog[c] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -543,13 +505,7 @@ __global__ void k_uniform_draw(int64_t C, int64_t chain_offset, int64_t p, const
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= C * p) return;
   const int64_t c = t / p, e = t % p;
-  double u;
-  if (u_in) {
-    u = u_in[t];
-  } else {
-    const uint4 w = omc_rng_block(key, chain_offset + c, sub + (uint32_t)(e >> 1));
-    u = (e & 1) ? omc_u53(w.z, w.w) : omc_u53(w.x, w.y);
-  }
+  const double u = omc_elem_uniform(u_in, t, key, chain_offset + c, e, sub);
   {
 #pragma clang fp contract(off)
     const double prod = range[e] * u;
@@ -572,7 +528,7 @@ __device__ __forceinline__ double poisson_loggam(double x) {
   const double x2 = (1.0 / x0) * (1.0 / x0);
   double gl0 = a[9];
   for (int k = 8; k >= 0; --k) gl0 = gl0 * x2 + a[k];
-  double gl = gl0 / x0 + 0.5 * 1.8378770664093453 + (x0 - 0.5) * log(x0) - x0;
+  double gl = gl0 / x0 + 0.5 * OMC_LOG_2PI + (x0 - 0.5) * log(x0) - x0;
   for (int k = 0; k < n; ++k) {
     gl -= log(x0 - 1.0);
     x0 -= 1.0;
@@ -594,7 +550,7 @@ __global__ void k_poisson_draw(int64_t C, int64_t chain_offset, const double* ra
     if (u_in) {
       u = ((int64_t)used < ld_u) ? u_in[c * ld_u + used] : __builtin_nan("");
       if (!(u == u)) { exhausted = true; u = 0.0; }  // off the tape: 0 ends both loops
-    } else {
+    } else {  // element `used` as omc_elem_uniform lays it out, the block kept for its second half (the helper would make it twice)
       if ((used & 1u) == 0u) w = omc_rng_block(key, chain_offset + c, used >> 1);
       u = (used & 1u) ? omc_u53(w.z, w.w) : omc_u53(w.x, w.y);
     }
@@ -641,22 +597,15 @@ extern "C" {
 omc_status omc_poisson_draw(omc_ctx* ctx, const double* rate, int64_t rate_stride, const double* u_inject, int64_t ld_u,
                             uint64_t draw_index, double* out) {
   if (!ctx || !rate || !out || rate_stride < 0 || (u_inject && ld_u < 1)) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_poisson_draw, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains, ctx->chain_offset, rate,
-                     rate_stride, u_inject, ld_u, omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), out, ctx->d_bad_chain);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_poisson_draw, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, ctx->chain_offset, rate,
+                    rate_stride, u_inject, ld_u, omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), out, ctx->d_bad_chain);
 }
 
 omc_status omc_uniform_draw(omc_ctx* ctx, int64_t p, const double* lower, const double* range, const double* u_inject,
                             uint64_t draw_index, uint32_t sub, double* out) {
   if (!ctx || p < 1 || !lower || !range || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_uniform_draw, dim3(grid1(ctx->n_chains * p, 256)), dim3(256), 0, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, p, lower, range, u_inject, omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), sub,
-                     out);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_uniform_draw, dim3(omc_grid1(ctx->n_chains * p, 256)), dim3(256), 0, ctx->n_chains, ctx->chain_offset, p,
+                    lower, range, u_inject, omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), sub, out);
 }
 
 omc_status omc_mixture_allocation(omc_ctx* ctx, int64_t p, int64_t K, const double* y, const double* prior,
@@ -664,133 +613,102 @@ omc_status omc_mixture_allocation(omc_ctx* ctx, int64_t p, int64_t K, const doub
                                   int64_t prec_stride, const double* u_inject, uint64_t draw_index, double* alloc) {
   if (!ctx || p < 1 || K < 1 || !y || !prior || (prior_rows != 1 && prior_rows != p) || !mean || !prec || !alloc)
     return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_mixture_allocation, dim3(grid1(ctx->n_chains * p, 256)), dim3(256), 0, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, p, K, y, prior, prior_rows, mean, mean_stride, prec, prec_stride, u_inject,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), alloc);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_mixture_allocation, dim3(omc_grid1(ctx->n_chains * p, 256)), dim3(256), 0, ctx->n_chains, ctx->chain_offset,
+                    p, K, y, prior, prior_rows, mean, mean_stride, prec, prec_stride, u_inject,
+                    omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), alloc);
 }
 
 omc_status omc_categorical_logpmf(omc_ctx* ctx, int64_t p, int64_t K, const double* alloc, const double* prob,
                                   int64_t prob_rows, double* out, int32_t accumulate) {
   if (!ctx || p < 1 || K < 1 || !alloc || !prob || (prob_rows != 1 && prob_rows != p) || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_categorical_logpmf, dim3(grid1(ctx->n_chains, 4)), dim3(256), 0, ctx->stream, ctx->n_chains, p, K,
-                     alloc, prob, prob_rows, out, (int)accumulate, ctx->d_bad_chain);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_categorical_logpmf, dim3(omc_grid1(ctx->n_chains, 4)), dim3(256), 0, ctx->n_chains, p, K, alloc, prob,
+                    prob_rows, out, (int)accumulate, ctx->d_bad_chain);
 }
 
 omc_status omc_mixture_normal_gamma(omc_ctx* ctx, int64_t p, int64_t K, const double* resid, const double* alloc,
                                     const double* a0, const double* b0, const double* g_inject, uint64_t draw_index,
                                     double* out) {
   if (!ctx || p < 1 || K < 1 || K > 255 || !resid || !alloc || !a0 || !b0 || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_mixture_normal_gamma, dim3(grid1(ctx->n_chains * K, 4)), dim3(256), 0, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, p, K, resid, alloc, a0, b0, g_inject,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_GAMMA), out, ctx->d_bad_chain);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_mixture_normal_gamma, dim3(omc_grid1(ctx->n_chains * K, 4)), dim3(256), 0, ctx->n_chains, ctx->chain_offset,
+                    p, K, resid, alloc, a0, b0, g_inject, omc_make_key(ctx->seed, draw_index, OMC_RNG_GAMMA), out,
+                    ctx->d_bad_chain);
 }
 
 omc_status omc_gamma_logpdf_vec(omc_ctx* ctx, int64_t K, const double* x, const double* shape, const double* rate,
                                 double* out, int32_t accumulate) {
   if (!ctx || K < 1 || !x || !shape || !rate || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_gamma_logpdf_vec, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains, K, x, shape,
-                     rate, out, (int)accumulate);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_gamma_logpdf_vec, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, K, x, shape, rate, out,
+                    (int)accumulate);
 }
 
 omc_status omc_log_transform(omc_ctx* ctx, int64_t n, const double* x, int64_t ld_x, double* out, int64_t ld_o,
                              double* sumlog) {
   if (!ctx || n < 1 || !x || !out || ld_x < n || ld_o < n) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_log_transform, dim3((unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, n, x, ld_x, out, ld_o, sumlog);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_log_transform, dim3((unsigned)ctx->n_chains), dim3(256), 0, n, x, ld_x, out, ld_o, sumlog);
 }
 
 omc_status omc_centered_rowdot(omc_ctx* ctx, int64_t n, const double* a, int64_t ld_a, const double* center_a,
                                const double* b, int64_t ld_b, const double* center_b, double* out) {
   if (!ctx || n < 1 || !a || !b || ld_a < n || ld_b < n || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_centered_rowdot, dim3((unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, n, a, ld_a, center_a, b, ld_b,
-                     center_b, out);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_centered_rowdot, dim3((unsigned)ctx->n_chains), dim3(256), 0, n, a, ld_a, center_a, b, ld_b, center_b,
+                    out);
 }
 
 omc_status omc_gamma_logpdf_ragged(omc_ctx* ctx, int64_t kmax, const double* x, const double* count, double shape,
                                    double rate, int32_t last_only, double* out, int32_t accumulate) {
   if (!ctx || kmax < 1 || !x || !out || !(shape > 0.0) || !(rate > 0.0)) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const double lnorm = shape * log(rate) - lgamma(shape);
-  hipLaunchKernelGGL(k_gamma_logpdf_ragged, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains, kmax, x,
-                     count, shape, rate, lnorm, (int)last_only, out, (int)accumulate);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_gamma_logpdf_ragged, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, kmax, x, count, shape,
+                    rate, lnorm, (int)last_only, out, (int)accumulate);
 }
 
 omc_status omc_diag_gauss_grad(omc_ctx* ctx, int64_t kmax, const double* x, const double* mean, const double* prec,
                                const double* count, double* grad) {
   if (!ctx || kmax < 1 || !x || !prec || !grad) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_diag_gauss_grad, dim3(grid1(ctx->n_chains * kmax, 256)), dim3(256), 0, ctx->stream, ctx->n_chains,
-                     kmax, x, mean, prec, count, grad);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_diag_gauss_grad, dim3(omc_grid1(ctx->n_chains * kmax, 256)), dim3(256), 0, ctx->n_chains, kmax, x, mean,
+                    prec, count, grad);
 }
 
 omc_status omc_diag_gauss_logpdf(omc_ctx* ctx, int64_t kmax, const double* x, const double* mean, const double* prec,
                                  const double* count, double* out, int32_t accumulate) {
   if (!ctx || kmax < 1 || !x || !prec || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_diag_gauss_logpdf, dim3(grid1(ctx->n_chains, 4)), dim3(256), 0, ctx->stream, ctx->n_chains, kmax,
-                     x, mean, prec, count, out, (int)accumulate);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_diag_gauss_logpdf<false>, dim3(omc_grid1(ctx->n_chains, 4)), dim3(256), 0, ctx->n_chains, kmax, x, mean, prec,
+                    count, 0.0, 0.0, out, (int)accumulate);
+}
+
+// the same with -inf for a chain that has a live element outside the scalar limits (location_scale.py:162-188)
+omc_status omc_diag_gauss_logpdf_limits(omc_ctx* ctx, int64_t kmax, const double* x, const double* mean, const double* prec,
+                                        const double* count, double lower, double upper, double* out, int32_t accumulate) {
+  if (!ctx || kmax < 1 || !x || !prec || !out) return OMC_INVALID_ARG;
+  return omc_launch(ctx, k_diag_gauss_logpdf<true>, dim3(omc_grid1(ctx->n_chains, 4)), dim3(256), 0, ctx->n_chains, kmax, x, mean, prec,
+                    count, lower, upper, out, (int)accumulate);
 }
 
 omc_status omc_poisson_logpmf(omc_ctx* ctx, const double* x, double rate, double* out, int32_t accumulate) {
   if (!ctx || !x || !out || !(rate > 0.0)) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_poisson_logpmf, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains, x, rate,
-                     out, (int)accumulate);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_poisson_logpmf, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, x, rate, out,
+                    (int)accumulate);
 }
 
 omc_status omc_count_logpdf(omc_ctx* ctx, const double* count, double per_element, double* out, int32_t accumulate) {
   if (!ctx || !count || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_count_logpdf, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains, count,
-                     per_element, out, (int)accumulate);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_count_logpdf, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, count, per_element, out,
+                    (int)accumulate);
 }
 
 omc_status omc_mixture_gather(omc_ctx* ctx, int64_t kmax, int64_t m, const double* param, int64_t param_stride,
                               const double* alloc, const double* count, double fill, double* out) {
   if (!ctx || kmax < 1 || m < 1 || !param || !alloc || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_mixture_gather, dim3(grid1(ctx->n_chains * kmax, 256)), dim3(256), 0, ctx->stream, ctx->n_chains,
-                     kmax, m, param, param_stride, alloc, count, fill, out, ctx->d_bad_chain, nullptr, 0, 0.0, nullptr);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_mixture_gather, dim3(omc_grid1(ctx->n_chains * kmax, 256)), dim3(256), 0, ctx->n_chains, kmax, m, param,
+                    param_stride, alloc, count, fill, out, ctx->d_bad_chain, nullptr, 0, 0.0, nullptr);
 }
 
 omc_status omc_mixture_gather2(omc_ctx* ctx, int64_t kmax, int64_t m, const double* alloc, const double* count,
                                const double* param_a, int64_t stride_a, double fill_a, double* out_a, const double* param_b,
                                int64_t stride_b, double fill_b, double* out_b) {
   if (!ctx || kmax < 1 || m < 1 || !alloc || !param_a || !out_a || !param_b || !out_b) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_mixture_gather, dim3(grid1(ctx->n_chains * kmax, 256)), dim3(256), 0, ctx->stream, ctx->n_chains,
-                     kmax, m, param_a, stride_a, alloc, count, fill_a, out_a, ctx->d_bad_chain, param_b, stride_b, fill_b, out_b);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_mixture_gather, dim3(omc_grid1(ctx->n_chains * kmax, 256)), dim3(256), 0, ctx->n_chains, kmax, m, param_a,
+                    stride_a, alloc, count, fill_a, out_a, ctx->d_bad_chain, param_b, stride_b, fill_b, out_b);
 }
 
 }  // extern "C"

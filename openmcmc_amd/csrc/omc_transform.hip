@@ -8,8 +8,6 @@
 
 #include "omc_common.h"
 
-static inline unsigned tf_grid(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
 // ------------------------------------------------------------------------------------------------
 // out[c][i] = alpha cs[c] sum_j X[i][j] exp(x[c][j]) + add_chain[c][i] + add_shared[i].  One thread per output row, the
 // transformed vector staged in LDS a chunk at a time (it never goes to memory), the sum in index order.
@@ -65,15 +63,6 @@ __global__ void __launch_bounds__(256) k_transform_grad_hess(int64_t p, const do
 // store in between (so the loads run ahead of the multiply-adds), then every lane writes its entry of the column; the next
 // column reads row j + 1 across lanes, hence a tf_wave_sync() per column.  The order of the subtractions per entry is that of the
 // right-looking form of k_small_spd_ops / k_small_sample_canonical.
-__device__ __forceinline__ double tf_bcast(double v, int src) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double tf_wave_sum(double v) {
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
 // LDS accesses of one wave complete in issue order; this keeps the compiler from moving them across the point where lanes start
 // reading what other lanes wrote.
 __device__ __forceinline__ void tf_wave_sync() {
@@ -100,7 +89,7 @@ __device__ __forceinline__ TfPoint tf_point(int p, int ld, int lane, const doubl
   const double d = on ? xv - m0v : 0.0;
   double Gt_i = 0.0, Pd = 0.0;
   for (int j = 0; j < p; ++j) {
-    const double tj = tf_bcast(t, j), dj = tf_bcast(d, j);
+    const double tj = omc_readlane_d(t, j), dj = omc_readlane_d(d, j);
     const double gij = Gt[j * p + row], pij = Pt[j * p + row];
     Gt_i = fma(gij, tj, Gt_i);
     Pd = fma(pij, dj, Pd);
@@ -108,7 +97,7 @@ __device__ __forceinline__ TfPoint tf_point(int p, int ld, int lane, const doubl
   }
   TfPoint r;
   const double g = tau * (t * (cv - Gt_i)) - lam * Pd;
-  r.target = tau * tf_wave_sum(t * cv - 0.5 * (t * Gt_i)) - 0.5 * lam * tf_wave_sum(d * Pd);
+  r.target = tau * omc_wave_sum(t * cv - 0.5 * (t * Gt_i)) - 0.5 * lam * omc_wave_sum(d * Pd);
   r.ok = true;
   r.sumlog = 0.0;
   r.mu = xv;
@@ -118,7 +107,7 @@ __device__ __forceinline__ TfPoint tf_point(int p, int ld, int lane, const doubl
     const double* rj = tile + j * ld;
     double acc = own[j];
     for (int k = 0; k < j; ++k) acc = fma(-own[k], rj[k], acc);
-    const double dj = tf_bcast(acc, j);
+    const double dj = omc_readlane_d(acc, j);
     if (!(dj > 0.0)) { r.ok = false; break; }
     const double sd = sqrt(dj);
     r.sumlog += log(sd);
@@ -131,13 +120,13 @@ __device__ __forceinline__ TfPoint tf_point(int p, int ld, int lane, const doubl
   for (int j = 0; j < p; ++j) {
     const double lj = own[j];
     if (lane == j) w /= lj;
-    const double wj = tf_bcast(w, j);
+    const double wj = omc_readlane_d(w, j);
     if (on && lane > j) w = fma(-lj, wj, w);
   }
   for (int j = p - 1; j >= 0; --j) {
     const double lj = tile[j * ld + row];
     if (lane == j) w /= lj;
-    const double vj = tf_bcast(w, j);
+    const double vj = omc_readlane_d(w, j);
     if (lane < j) w = fma(-lj, vj, w);
   }
   r.mu = on ? xv + 0.5 * w : 0.0;
@@ -149,10 +138,10 @@ __device__ __forceinline__ double tf_quad(int p, int ld, int lane, const double*
   const int row = lane < p ? lane : 0;
   double w = 0.0;
   for (int i = 0; i < p; ++i) {
-    const double ri = tf_bcast(r, i), li = tile[i * ld + row];
+    const double ri = omc_readlane_d(r, i), li = tile[i * ld + row];
     if (lane <= i && lane < p) w = fma(li, ri, w);
   }
-  return tf_wave_sum(w * w);
+  return omc_wave_sum(w * w);
 }
 
 #define TF_WAVES_MAX 4
@@ -182,6 +171,9 @@ __global__ void __launch_bounds__(64 * TF_WAVES_MAX) k_mala_transform_step(
       z = (lane & 1) ? n1 : n0;
     }
   }
+  // the accept uniform: block (p + 1) / 2 + 1 of the uniform stream, beyond the (p + 1) / 2 blocks a vector of p elements takes --
+  // the block the host route's decision reads (metropolis_hastings.py: sub = (p + 1) // 2 + 1), so both routes accept alike.
+  // Written out, not omc_chain_uniform: that changed this kernel's code (profiles/r08_mh_refactor_same_code.txt)
   double u;
   if (u_in) {
     u = u_in[c];
@@ -198,7 +190,7 @@ __global__ void __launch_bounds__(64 * TF_WAVES_MAX) k_mala_transform_step(
     for (int j = p - 1; j >= 0; --j) {
       const double lj = tile[j * ld + (on ? lane : 0)];
       if (lane == j) v /= lj;
-      const double vj = tf_bcast(v, j);
+      const double vj = omc_readlane_d(v, j);
       if (lane < j) v = fma(-lj, vj, v);
     }
     xp = on ? cur.mu + v : 0.0;
@@ -231,24 +223,18 @@ omc_status omc_transform_predict(omc_ctx* ctx, int64_t n, int64_t p, const doubl
   if (!ctx || n < 1 || p < 1 || !X || ld_X < p || !x || ld_x < p || (add_chain && ld_add < n) || !out || ld_out < n)
     return OMC_INVALID_ARG;
   if (ctx->n_chains > 65535) return OMC_UNSUPPORTED;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_transform_predict, dim3(tf_grid(n, 256), (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, n, p, X, ld_X,
-                     x, ld_x, add_chain, ld_add, add_shared, alpha, chain_scale, out, ld_out);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_transform_predict, dim3(omc_grid1(n, 256), (unsigned)ctx->n_chains), dim3(256), 0, n, p, X, ld_X, x, ld_x,
+                    add_chain, ld_add, add_shared, alpha, chain_scale, out, ld_out);
 }
 
 omc_status omc_transform_grad_hess(omc_ctx* ctx, int64_t p, const double* x, int64_t ld_x, const double* u, int64_t ld_u,
                                    const double* G, const double* scale, double* grad, double* H) {
   if (!ctx || p < 1 || !x || ld_x < p || (grad && (!u || ld_u < p)) || (H && !G) || (!grad && !H)) return OMC_INVALID_ARG;
   if (ctx->n_chains > 65535) return OMC_UNSUPPORTED;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  unsigned gx = tf_grid(p * p, 256);
+  unsigned gx = omc_grid1(p * p, 256);
   if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(k_transform_grad_hess, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, p, x, ld_x, u, ld_u, G,
-                     scale, grad, H);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_transform_grad_hess, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, p, x, ld_x, u, ld_u, G, scale, grad,
+                    H);
 }
 
 omc_status omc_mala_transform_step(omc_ctx* ctx, int64_t p, const double* G, const double* cvec, const double* P, const double* m0,
@@ -266,7 +252,7 @@ omc_status omc_mala_transform_step(omc_ctx* ctx, int64_t p, const double* G, con
     OMC_HIP_CHECK(hipFuncSetAttribute((const void*)k_mala_transform_step, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (ctx->device >= 0 && ctx->device < 64) lds_raised[ctx->device] = true;
   }
-  hipLaunchKernelGGL(k_mala_transform_step, dim3(tf_grid(ctx->n_chains, waves)), dim3(64 * waves), lds, ctx->stream, ctx->n_chains,
+  hipLaunchKernelGGL(k_mala_transform_step, dim3(omc_grid1(ctx->n_chains, waves)), dim3(64 * waves), lds, ctx->stream, ctx->n_chains,
                      ctx->chain_offset, (int)p, G, cvec, P, m0, tau, lam, 1.0 / (step * step), x, ld_x, z_inject, u_inject,
                      omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL), omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM),
                      (long long*)accept_count, (long long*)proposal_count, prop_out, lq_fwd_out, lq_rev_out, logp_out,

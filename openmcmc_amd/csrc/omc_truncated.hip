@@ -11,8 +11,7 @@
 
 #include "omc_common.h"
 #include "omc_truncnorm.h"
-
-static inline unsigned grid1(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
+#include "omc_trunc_dense.h"
 
 struct TruncTerms {
   int n_terms;
@@ -21,13 +20,6 @@ struct TruncTerms {
   const double* rhs[OMC_MAX_TERMS];
   const double* scale[OMC_MAX_TERMS];
 };
-
-__device__ __forceinline__ double trunc_uniform(const double* u_in, int64_t ld, int64_t c, int64_t i, const omc_rng_key& key,
-                                                int64_t gc) {
-  if (u_in) return u_in[c * ld + i];
-  const uint4 w = omc_rng_block(key, gc, (uint32_t)(i >> 1));
-  return (i & 1) ? omc_u53(w.z, w.w) : omc_u53(w.x, w.y);
-}
 
 // One wave = 64 chains, one lane each, 64 sites at a time:
 //   * the block's x (and the per-chain right-hand side, if any) comes in as 64 coalesced rows through an LDS transpose
@@ -276,73 +268,10 @@ __global__ void k_band_gibbs_truncated(int64_t C, int64_t chain_offset, int64_t 
     if (!(a > 0.0)) fail = true;
     const double lo = lower ? lower[i] : -INFINITY, hi = upper ? upper[i] : INFINITY;
     double mean, sd;
-    if (n == 1) {
-      mean = b / a;
-      sd = 1.0 / sqrt(a);
-    } else {
-      const double v = 1.0 / a;
-      sd = sqrt(v);
-      mean = v * ((b - row) + a * xi_old);
-    }
-    xc[i] = omc_truncated_normal_rv(mean, sd, lo, hi, trunc_uniform(u_in, ld_u, c, i, key, chain_offset + c));
+    omc_trunc_site(a, b, row, xi_old, n == 1, mean, sd);
+    xc[i] = omc_truncated_normal_rv(mean, sd, lo, hi, omc_elem_uniform(u_in, c * ld_u + i, key, chain_offset + c, i));
   }
   if (fail) atomicMin((unsigned long long*)bad, (unsigned long long)c);
-}
-
-// dense precision, one wave per chain: Q_c = sum_k s_k[c] M_k assembled row by row on the fly
-__global__ void __launch_bounds__(64) k_dense_gibbs_truncated(int64_t C, int64_t chain_offset, int64_t p, int n_terms,
-                                                              const double* m0, const double* m1, const double* m2,
-                                                              const double* m3, const double* s0, const double* s1,
-                                                              const double* s2, const double* s3, const double* r0,
-                                                              const double* r1, const double* r2, const double* r3,
-                                                              const double* rhs_chain, int64_t ld_rhs, const double* lower,
-                                                              const double* upper, const double* u_in, int64_t ld_u,
-                                                              omc_rng_key key, double* x, int64_t ld_x, long long* bad) {
-  extern __shared__ double xs[];  // the chain's vector
-  const int64_t c = blockIdx.x;
-  const int lane = threadIdx.x;
-  const double* M[4] = {m0, m1, m2, m3};
-  const double* R[4] = {r0, r1, r2, r3};
-  double s[4] = {s0 ? s0[c] : 1.0, s1 ? s1[c] : 1.0, s2 ? s2[c] : 1.0, s3 ? s3[c] : 1.0};
-  for (int64_t j = lane; j < p; j += 64) xs[j] = x[c * ld_x + j];
-  __syncthreads();
-  bool fail = false;
-  for (int64_t i = 0; i < p; ++i) {
-    double dot = 0.0;
-    for (int64_t j = lane; j < p; j += 64) {
-      double q = 0.0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (k < n_terms) q = fma(s[k], M[k] ? M[k][i * p + j] : (i == j ? 1.0 : 0.0), q);
-      dot = fma(q, xs[j], dot);
-    }
-#pragma unroll
-    for (int sh = 32; sh > 0; sh >>= 1) dot += __shfl_xor(dot, sh, 64);
-    if (lane == 0) {
-      double a = 0.0, b = rhs_chain ? rhs_chain[c * ld_rhs + i] : 0.0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (k < n_terms) {
-          a = fma(s[k], M[k] ? M[k][i * p + i] : 1.0, a);
-          if (R[k]) b = fma(s[k], R[k][i], b);
-        }
-      if (!(a > 0.0)) fail = true;
-      const double lo = lower ? lower[i] : -INFINITY, hi = upper ? upper[i] : INFINITY;
-      double mean, sd;
-      if (p == 1) {
-        mean = b / a;
-        sd = 1.0 / sqrt(a);
-      } else {
-        const double v = 1.0 / a;
-        sd = sqrt(v);
-        mean = v * ((b - dot) + a * xs[i]);
-      }
-      xs[i] = omc_truncated_normal_rv(mean, sd, lo, hi, trunc_uniform(u_in, ld_u, c, i, key, chain_offset + c));
-    }
-    __syncthreads();
-  }
-  for (int64_t j = lane; j < p; j += 64) x[c * ld_x + j] = xs[j];
-  if (fail && lane == 0) atomicMin((unsigned long long*)bad, (unsigned long long)c);
 }
 
 // Normal.check_domain_response + log_p = -inf outside the domain (location_scale.py:162-188)
@@ -393,7 +322,7 @@ omc_status omc_tridiag_gibbs_truncated(omc_ctx* ctx, int64_t n, const omc_tridia
     if (lds > 48 * 1024)                                                                                                        \
       OMC_HIP_CHECK(hipFuncSetAttribute((const void*)(k_tridiag_gibbs_truncated<INJv, NTv>),                                    \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
-    hipLaunchKernelGGL((k_tridiag_gibbs_truncated<INJv, NTv>), dim3(grid1(ctx->n_chains, 64)), dim3(64 * TG_NW), lds, ctx->stream,      \
+    hipLaunchKernelGGL((k_tridiag_gibbs_truncated<INJv, NTv>), dim3(omc_grid1(ctx->n_chains, 64)), dim3(64 * TG_NW), lds, ctx->stream,      \
                        ctx->n_chains, ctx->chain_offset, n, T, rhs_chain, ld_rhs, lower, upper, u_inject, ld_u,                 \
                        omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), x, ld_x, ctx->d_bad_chain);                        \
   } while (0)
@@ -417,7 +346,6 @@ omc_status omc_band_gibbs_truncated(omc_ctx* ctx, int64_t n, int64_t w, const om
   if (!ctx || n < 1 || w < 0 || w > 128 || !terms || terms->n_terms < 1 || terms->n_terms > OMC_MAX_TERMS || !x || ld_x < n ||
       (rhs_chain && ld_rhs < n) || (u_inject && ld_u < n))
     return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
   TruncBand T{};
   T.n_terms = terms->n_terms;
   for (int k = 0; k < OMC_MAX_TERMS; ++k) {
@@ -428,11 +356,9 @@ omc_status omc_band_gibbs_truncated(omc_ctx* ctx, int64_t n, int64_t w, const om
     T.scale[k] = on ? terms->scale[k] : nullptr;
     if (on && (T.bw[k] < 0 || T.bw[k] > w)) return OMC_INVALID_ARG;
   }
-  hipLaunchKernelGGL(k_band_gibbs_truncated, dim3(grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->stream, ctx->n_chains,
-                     ctx->chain_offset, n, (int)w, T, rhs_chain, ld_rhs, lower, upper, u_inject, ld_u,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), x, ld_x, ctx->d_bad_chain);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_band_gibbs_truncated, dim3(omc_grid1(ctx->n_chains, 64)), dim3(64), 0, ctx->n_chains, ctx->chain_offset, n,
+                    (int)w, T, rhs_chain, ld_rhs, lower, upper, u_inject, ld_u, omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM),
+                    x, ld_x, ctx->d_bad_chain);
 }
 
 omc_status omc_dense_gibbs_truncated(omc_ctx* ctx, int64_t p, const omc_dense_terms* terms, const double* rhs_chain,
@@ -441,28 +367,16 @@ omc_status omc_dense_gibbs_truncated(omc_ctx* ctx, int64_t p, const omc_dense_te
   if (!ctx || p < 1 || p > 8192 || !terms || terms->n_terms < 1 || terms->n_terms > OMC_MAX_TERMS || !x || ld_x < p ||
       (rhs_chain && ld_rhs < p) || (u_inject && ld_u < p))
     return OMC_INVALID_ARG;
-  if (terms->diag_chain)  // per-chain diagonal (a mixture prior): omc_truncmix.hip
+  if (terms->diag_chain)  // per-chain diagonal (a mixture prior): the instantiation of omc_truncmix.hip
     return omc_dense_gibbs_truncated_diag_launch(ctx, p, terms, rhs_chain, ld_rhs, lower, upper, u_inject, ld_u, draw_index, x, ld_x);
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  const double *m[4] = {0, 0, 0, 0}, *s[4] = {0, 0, 0, 0}, *r[4] = {0, 0, 0, 0};
-  for (int k = 0; k < terms->n_terms; ++k) { m[k] = terms->mat[k]; s[k] = terms->scale[k]; r[k] = terms->rhs[k]; }
-  hipLaunchKernelGGL(k_dense_gibbs_truncated, dim3((unsigned)ctx->n_chains), dim3(64), (size_t)p * sizeof(double),
-                     ctx->stream, ctx->n_chains, ctx->chain_offset, p, (int)terms->n_terms, m[0], m[1], m[2], m[3], s[0], s[1],
-                     s[2], s[3], r[0], r[1], r[2], r[3], rhs_chain, ld_rhs, lower, upper, u_inject, ld_u,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), x, ld_x, ctx->d_bad_chain);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_trunc_dense_launch<false>(ctx, p, terms, rhs_chain, ld_rhs, lower, upper, u_inject, ld_u, draw_index, x, ld_x);
 }
 
 omc_status omc_domain_penalty(omc_ctx* ctx, int64_t n, const double* x, int64_t ld, const double* lower,
                               const double* upper, double* out) {
   if (!ctx || n < 1 || !x || ld < n || !out) return OMC_INVALID_ARG;
   if (!lower && !upper) return OMC_OK;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_domain_penalty, dim3((unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, ctx->n_chains, n, x, ld,
-                     lower, upper, out);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
+  return omc_launch(ctx, k_domain_penalty, dim3((unsigned)ctx->n_chains), dim3(256), 0, ctx->n_chains, n, x, ld, lower, upper, out);
 }
 
 }  // extern "C"

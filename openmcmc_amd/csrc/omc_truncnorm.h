@@ -18,6 +18,7 @@
 
 #define OMC_RSQRT2 0.70710678118654752440
 #define OMC_LOG_SQRT_2PI 0.91893853320467274178
+#define OMC_LOG_2PI 1.8378770664093453
 
 __device__ inline double omc_log_ndtr(double t) {  // log Phi(t), any t including +-inf
   if (t > 0.0) return log1p(-0.5 * erfc(t * OMC_RSQRT2));
@@ -41,7 +42,7 @@ __device__ inline double omc_ndtri_exp_lower(double y) {
     x = normcdfinv(exp(y));
     iters = 1;  // normcdfinv is already good to a few ulp; one Newton step removes the rounding of exp(y) for large |y|
   } else {  // Phi(x) ~ phi(x)/|x|:  x^2 = -2y - log(2 pi) - log(x^2)
-    const double r = -2.0 * y - 1.8378770664093453;
+    const double r = -2.0 * y - OMC_LOG_2PI;
     x = -sqrt(r - log(r));
     iters = 4;
   }
@@ -263,6 +264,18 @@ __device__ inline double omc_log_gauss_mass(double a, double b) {
 __device__ inline double omc_truncated_normal_rv(double mean, double scale, double lower, double upper, double u) {
   const double a = (lower - mean) / scale, b = (upper - mean) / scale;
   return omc_truncnorm_ppf(u, a, b) * scale + mean;
+}
+// Mean and sd of one site's full conditional in a scan of single-site updates (gmrf.py:255-262): a = Q_ii, b = b_i,
+// row = Q_i. x with the current x, x_old = x_i.  single: the vector has one site, mean = b / Q (gmrf.py:244-247).
+__device__ __forceinline__ void omc_trunc_site(double a, double b, double row, double x_old, bool single, double& mean, double& sd) {
+  if (single) {
+    mean = b / a;
+    sd = 1.0 / sqrt(a);
+  } else {
+    const double v = 1.0 / a;
+    sd = sqrt(v);
+    mean = v * ((b - row) + a * x_old);
+  }
 }
 // the same with 1/scale supplied (no division on the caller's serial path); an infinite limit stays infinite
 __device__ inline double omc_truncated_normal_rv_inv(double mean, double scale, double inv_scale, double lower, double upper, double u) {

@@ -139,6 +139,37 @@ def test_dense_gibbs_truncated_diag_chain_matches_restatement(p):
     eng.close()
 
 
+@pytest.mark.parametrize("p", [1, 7, 65])
+def test_dense_gibbs_truncated_zero_diag_chain_is_the_plain_scan(p):
+    """The two instantiations of k_dense_gibbs_truncated are one source: a per-chain diagonal of zeros adds 0 to positive
+    diagonal entries (no signed zero arises) and the scan is the one without diag_chain, bit for bit.  The inputs of
+    test_dense_gibbs_truncated_diag_chain_matches_restatement; p = 65 makes the lanes stride."""
+    from openmcmc_amd.engine import Engine
+
+    rng = np.random.default_rng(100 + p)
+    C = 3
+    eng = Engine(C, seed=4)
+    A = rng.standard_normal((p + 5, p))
+    M = A.T @ A / p
+    r = rng.standard_normal(p)
+    s = 0.5 + rng.random(C)
+    rng.random((C, p))  # (the diagonal d of that test: its draws keep the streams of the inputs below in step)
+    rc = rng.standard_normal((C, p)) * 3
+    lower = np.where(rng.random(p) < 0.5, 0.0, -np.inf)
+    x0 = np.abs(rng.standard_normal((C, p)))
+    u = rng.random((C, p))
+    t = eng.to_device
+    terms = [{"mat": t(M), "rhs": t(r), "scale": t(s)}]
+    x_plain, x_zero = t(x0), t(x0)
+    eng.dense_gibbs_truncated(p, terms, x_plain, lower=t(lower), u=t(u), rhs_chain=t(rc))
+    eng.dense_gibbs_truncated(p, terms, x_zero, lower=t(lower), u=t(u), rhs_chain=t(rc), diag_chain=t(np.zeros((C, p))))
+    eng.check_status()
+    plain, zero = x_plain.cpu().numpy(), x_zero.cpu().numpy()
+    assert np.all(np.isfinite(plain)) and not np.array_equal(plain, x0)
+    assert np.array_equal(plain, zero), (p, np.max(np.abs(plain - zero)))
+    eng.close()
+
+
 def test_small_gibbs_truncated_in_kernel_uniforms():
     """Same draw_index: bit-equal; identical chains differ; count == 1 draws follow scipy's truncnorm (KS)."""
     from openmcmc_amd.engine import Engine

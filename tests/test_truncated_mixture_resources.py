@@ -1,39 +1,25 @@
-"""Compile-time guard for the truncated mixture kernels (omc_truncmix.hip; no GPU needed: hipcc cross-compiles): the
-ragged scan inlines the near-limit truncated-normal quantile, which under a spike component is the common path -- no
-kernel of the file uses scratch or spills VGPRs."""
+"""Compile-time guard for the truncated mixture kernels (no GPU needed: hipcc cross-compiles): the ragged scan and the dense scan
+with a per-chain diagonal (omc_truncmix.hip) inline the near-limit truncated-normal quantile, which under a spike component is
+the common path, and the log-density with limits (omc_scalar.hip) is a few sums -- none of them uses scratch or spills VGPRs."""
 
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_usage import HIPCC, compile_usage, not_in_registers
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 
 
 def test_truncated_mixture_kernels_need_no_scratch(tmp_path):
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", f"-I{ROOT}/include",
-           "-mllvm", "-instcombine-max-copied-from-constant-users=100000",  # as openmcmc_amd/csrc/Makefile
-           "-c", f"{ROOT}/openmcmc_amd/csrc/omc_truncmix.hip", "-o", str(tmp_path / "omc_truncmix.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    usage, name = {}, None
-    for line in (out.stderr + out.stdout).splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-        m = re.search(r"(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
-    kernels = {k: v for k, v in usage.items() if "k_" in k}
-    names = " ".join(kernels)
-    for want in ("k_small_gibbs_truncated", "k_dense_gibbs_truncated_diag", "k_diag_gauss_logpdf_limits"):
-        assert want in names, sorted(usage)
-    bad = {k: v for k, v in kernels.items() if v.get("ScratchSize [bytes/lane]") != 0 or v.get("VGPRs Spill") != 0}
-    assert not bad, bad
+    usage = {**compile_usage("omc_truncmix.hip", tmp_path), **compile_usage("omc_scalar.hip", tmp_path)}
+    # by substring of the (mangled) name; the dense scan and the log-density are template instantiations now, and every
+    # instantiation that the two files hold is checked
+    wanted = ("k_small_gibbs_truncated", "k_dense_gibbs_truncated", "k_diag_gauss_logpdf")
+    kernels = {k: v for k, v in usage.items() if any(w in k for w in wanted)}
+    for want in wanted:
+        assert any(want in k for k in kernels), sorted(usage)
+    # the per-chain-diagonal instantiation <true> of the dense scan and the instantiation <true> (limits) of the log-density
+    assert any("k_dense_gibbs_truncatedILb1E" in k for k in kernels), sorted(kernels)
+    assert any("k_diag_gauss_logpdfILb1E" in k for k in kernels), sorted(kernels)
+    assert not not_in_registers(kernels), not_in_registers(kernels)
