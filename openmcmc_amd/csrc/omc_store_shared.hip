@@ -50,6 +50,12 @@ __global__ void __launch_bounds__(256) k_store_moments_part(StoreView v, int64_t
     } else {
       for (int64_t r = r0 + rr; r < r1; r += M_ROWS) omc_welford(cnt, mean, m2, v.data[r * v.row_stride + j]);
     }
+    if (mean != mean) {  // a non-finite value among the lane's: the mean of their plain sum, +-inf or NaN (omc_moments.h)
+      const double* p = v.data + (IDX ? batch * v.batch_stride + v.idx[j] : j);
+      double sum = 0.0;
+      for (int64_t r = r0 + rr; r < r1; r += M_ROWS) sum += p[r * v.row_stride];
+      mean = sum / cnt;
+    }
   }
   sm[0][rr][col] = cnt; sm[1][rr][col] = mean; sm[2][rr][col] = m2;
   __syncthreads();
