@@ -106,7 +106,8 @@ omc_status omc_ctx_synchronize(omc_ctx* ctx);
  * "hist2d_algo" (0 auto; bit 0: omc_store_histogram2d always takes the direct form, atomic adds to the output without counters in
  * LDS; bit 1: it always finds the bins by bisection; same counts either way),
  * "rank_tile" (0 = 8192, or a power of two 64 .. 8192: keys of an LDS tile of the sort behind omc_store_ranks; same results bit for
- * bit), "rank_chunk" (0 auto, else the elements omc_store_ranks / omc_store_rank_diagnostics / omc_store_hdi work on at a time),
+ * bit), "rank_chunk" (0 auto, else the elements omc_store_ranks / omc_store_rank_diagnostics / omc_store_hdi / omc_store_autocorr work on at a time),
+ * "autocorr_slice" (0 = 2048, else the rows of a time slice of omc_store_autocorr, at least 1: same results to rounding),
  * "band_algo" (0 auto; 1 narrow bands one lane per chain in ONE piece; 2 one workgroup per chain, a column per step; 3 one
  * workgroup per chain in blocks of 16 columns, the next block factorised ahead, the window update on the matrix cores -- auto
  * takes it from w = 9, and from w = 4 on up to 3072 chains, where a lane per chain leaves the SIMDs to lone waves), "band_seg_overlap"
@@ -1007,6 +1008,53 @@ enum { OMC_REDUCE_SUM = 0, OMC_REDUCE_MIN = 1, OMC_REDUCE_MAX = 2, OMC_REDUCE_AR
        OMC_REDUCE_COUNT_ABOVE = 5, OMC_REDUCE_SUPNORM = 6 };
 omc_status omc_store_reduce(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                             int32_t op, int32_t omit_nan, const double* a, const double* b, double* out, int64_t* count_out);
+/* Autocovariance, autocorrelation and integrated autocorrelation time of the same store: the plot next to the trace, and the
+ * one principled way to choose a thinning.  store, idx, n_idx and the NULL convention as omc_store_reduce (order kept, repeats
+ * allowed, n_idx may exceed size); an index outside [0, size) is OMC_INVALID_ARG, found on the device before any output is written.
+ * With N = n_iter, L = max_lag, u = 2^-53, for chain c and selection position k with draws x[0 .. N):
+ *   m      = the column's mean as omc_col_moments gives it on the per-chain view of the selection (Welford's and Chan's updates:
+ *            exact for equal draws); written to mean_out [C][n_idx] (may be NULL)
+ *   d_i    = x_i - m                                           (one IEEE subtraction)
+ *   s_c(t) = sum_{i = 0}^{N - 1 - t} d_i d_{i + t},  t = 0 .. L   (products rounded or fused)
+ *   per_chain != 0: acf_out [C][n_idx][L + 1] = g(t) = s_c(t) / N                        (one division)
+ *   per_chain == 0: acf_out [n_idx][L + 1]    = g(t) = S(t) / (N C),  S(t) = sum_c s_c(t), the chains added in ascending c: the
+ *                   chains' autocovariances around their OWN means, averaged
+ *   normalize != 0: g(t) / g(0) instead, one more IEEE division of the two rounded values (bit-equal to dividing the
+ *                   normalize == 0 result by its lag-0 entry)
+ *   tau_out [C][n_idx] or [n_idx] (may be NULL): the integrated autocorrelation time by Geyer's initial positive sequence on
+ *                   rho(t) = g(t) / g(0): tau = -1, then for k = 0, 1, ... while 2 k + 1 <= L and G = rho(2 k) + rho(2 k + 1) > 0:
+ *                   tau += 2 G (sequential fp64 additions in that order)
+ *   window_out, int32, shaped like tau_out (may be NULL): the lags used, 2 * (pairs taken).  window >= L (L odd) or >= L - 1
+ *                   (L even): the sequence ran into max_lag, tau is a lower bound -- raise max_lag.
+ * Edge rules.  A column whose mean is not finite -- a NaN draw, or an infinite one, which is not special-cased: its deviation is
+ * inf - inf -- gives NaN in every lag; per chain that column only, pooled that element only.  A column whose draws all equal its
+ * first draw (compared as values) has s(t) = 0 exactly, whatever the mean rounds to; pooled it adds 0 to S.  Where rho(0) = g(0) / g(0)
+ * is NaN (g(0) NaN, zero -- every contributing draw equal -- or infinite) the normalised lags are NaN by that division, tau is
+ * NaN and window is 0.
+ * OMC_INVALID_ARG, with a text in omc_last_error and the outputs untouched: n_iter < 2, size < 1, max_lag < 0,
+ * max_lag > n_iter - 1, n_idx < 1 (or no index and n_idx != size), store or acf_out NULL, an index outside [0, size), more than
+ * 65535 time slices or blocks of 32 lags.
+ * Accuracy: |s(t) - exact sum of d_i d_{i+t}| <= (terms + 1) u sum |d_i d_{i+t}|, terms = N - t per chain and C (N - t) pooled:
+ * the bound of any order of additions of rounded or fused products (as omc_store_reduce's SUM).  The order of additions depends
+ * on N, L, C and option "autocorr_slice" only -- not on size, n_idx or the index --; no floating-point atomics; repeated calls
+ * are bit-equal and so are the rows of repeated index entries.
+ * How: a chunk of selected elements at a time (C columns per element).  The means; a pre-pass that flags, per column, a draw that
+ * differs from the first and a mean that is not finite (integer OR) and, with an index, gathers the centred draws into a
+ * compact [N][C chunk] workspace (without an index the store is read where it lies and centred on load); the lag kernel, one
+ * lane per column, consecutive lanes on consecutive columns, grid = column tiles x blocks of 32 lags x time slices, each block of
+ * lags 32 accumulators and a 32-slot register ring (two loads per 32 FMAs), four adjacent blocks of lags to a workgroup; a slice owns the products
+ * whose left factor lies in its rows and reads up to L rows past its end; partials [slice][lag][column] are added slices first,
+ * then chains, both ascending, divided, normalised, and walked by the Geyer loop.  Slices are 2048 rows (option "autocorr_slice":
+ * 0 = that, else rows per slice, at least 1; results for different settings agree within the bound, not bit for bit), so a few
+ * long columns still fill the device.  Workspace (rank_ws): per column 256 (L / 32 + 1) bytes per slice, 8 (L + 1) bytes, 8 N bytes
+ * with an index, one word; the chunk is what fits 1 GiB, at least one element (option "rank_chunk" forces it), so the workspace stays bounded by
+ * 1 GiB, or by one element's C columns where those alone need more, however large the store is.  Store bytes read: the means' and
+ * the pre-pass's one read each of the selected columns; without an index the lag kernel's 2 (L / 32 + 1) loads of every row,
+ * which the waves of a workgroup share through the caches.  Runs on the
+ * context's stream; with an index the host reads one word back (the validation).                                              */
+omc_status omc_store_autocorr(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                              int64_t max_lag, int32_t per_chain, int32_t normalize, double* acf_out, double* tau_out,
+                              int32_t* window_out, double* mean_out);
 /* Thinned copy of the store for a thinned gather: out[j] = store[first + j * every] (slabs of C * size doubles),
  * j = 0 .. ceil((n_iter - first) / every) - 1 (that count is left in *n_out when n_out is not NULL, host).           */
 omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int64_t first, int64_t every,

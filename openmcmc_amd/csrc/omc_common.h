@@ -36,7 +36,7 @@ struct omc_ctx {
   // omc_store_cov), radix histograms (omc_store.hip), partial minima / maxima (omc_hist.hip), lag sums and Geyer state (omc_diag.hip)
   void* store_ws; size_t store_ws_bytes;
   double* cov_ws; size_t cov_ws_bytes;  // omc_cov.hip: means, variances and partial tiles of omc_store_cov
-  void* rank_ws; size_t rank_ws_bytes;  // omc_rank.hip, omc_hdi.hip: keys, series and per-element words of a chunk (its own: it calls omc_store_rhat_ess, which uses store_ws)
+  void* rank_ws; size_t rank_ws_bytes;  // omc_rank.hip, omc_hdi.hip: keys, series and per-element words of a chunk (its own: it calls omc_store_rhat_ess, which uses store_ws); omc_autocorr.hip: partial lag sums and centred draws of a chunk (omc_col_moments uses store_ws)
   // dense path (omc_dense.hip): rocBLAS handle and workspaces, created on first use
   void* blas;
   // blocked dense factorisation: second half of the chains on a side stream (forked from / joined into `stream` by events),
@@ -91,6 +91,7 @@ struct omc_ctx {
   int hist2d_algo;  // omc_store_histogram2d: bit 0 always the direct form (atomic adds to the output, no LDS counters), bit 1 always the bisection
   int rank_tile;  // omc_rank.hip: keys of an LDS tile of the sort, a power of two 64 .. 8192 (0: 8192)
   int64_t rank_chunk;  // omc_rank.hip: elements per chunk (0: what fits the workspace budget)
+  int64_t autocorr_slice;  // omc_autocorr.hip: rows per time slice (0: 2048)
   int band_seg_overlap;  // segmented lane kernel: columns of warm-up before a segment (default 192)
   int band_seg_count;    // segmented lane kernel: number of segments (0 = chosen for the SIMDs; tuning and tests)
   int band_blocked_threads;  // blocked band kernel: 0 = form chosen by what fits a CU; 512, 4, 8, 16 force one (A/B, tests; band_blocked_choose)

@@ -74,6 +74,7 @@ omc_status omc_ctx_create(int32_t device, int64_t n_chains, uint64_t seed, int64
   c->hist2d_algo = 0;
   c->reduce_algo = 0;
   c->rank_tile = 0; c->rank_chunk = 0;
+  c->autocorr_slice = 0;
   c->band_algo = 0; c->band_seg_overlap = 192; c->band_seg_count = 0; c->band_blocked_threads = 0;
   if (c->own_stream) {
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -298,6 +299,11 @@ omc_status omc_ctx_set_option(omc_ctx* ctx, const char* name, int64_t value) {
   if (!strcmp(name, "rank_chunk")) {
     if (value < 0) return OMC_INVALID_ARG;
     ctx->rank_chunk = value;
+    return OMC_OK;
+  }
+  if (!strcmp(name, "autocorr_slice")) {
+    if (value < 0) return OMC_INVALID_ARG;
+    ctx->autocorr_slice = value;
     return OMC_OK;
   }
   if (!strcmp(name, "band_seg_overlap")) {

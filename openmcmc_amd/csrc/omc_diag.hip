@@ -16,14 +16,15 @@
 // block of L lags costs L FMAs per draw.  The loop is unrolled by L: every ring index is a compile-time constant.
 //   short form (M <= 64): a workgroup stages one chain's two halves for 64 elements in LDS (one read of the store) and
 //     computes means and every lag from there -- eight waves, each one half and 16 of the 64 lags;
-//   long form: a means pass, then blocks of L = 32 lags (32 accumulators and a 32-slot ring: 256 VGPRs, no scratch); block 0 reads the store once (x[i] is its own lagged operand),
-//     every later block twice (x[i] and x[i - t0]).  Blocks stop when every element's Geyer sequence has ended.
+//   long form: a means pass, then blocks of L = 32 lags (32 accumulators and a 32-slot ring: 256 VGPRs, no scratch); block 0 reads the store once (x[i] is its own lagged operand:
+//     the second load of the address is served by the cache), every later block twice (x[i] and x[i - t0]).  Blocks stop when every element's Geyer sequence has ended.
 // A workgroup covers 64 elements and a fixed group of series; it writes one partial per (group, lag, element), and
 // k_diag_step adds the groups' partials in a fixed order and advances each element's Geyer state by the block.  The number
 // of groups depends on C and size only: repeated calls are bit-equal.  No floating-point atomics anywhere.
 #include <math.h>
 
 #include "omc_common.h"
+#include "omc_lag_block.h"
 #include "omc_moments.h"
 
 namespace {
@@ -33,28 +34,8 @@ constexpr int D_L = 32;       // lags per block
 constexpr int D_SHORT = 64;   // longest half-series of the short form (every lag in one pass)
 constexpr int D_STATE = 8;    // per-element Geyer state, [D_STATE][size]
 
-// acc[l] += sum_{i = t0 + l}^{M-1} y(i) y(i - t0 - l), l < L: the lane's contribution to S(t0 + l).  Ring slot u holds
-// y(i - t0) of the step i = i0 + u; slots not yet written in this call are zero, which drops the terms with i - t0 - l < 0.
-template <int L, typename F>
-__device__ __forceinline__ void d_lag_block(int64_t t0, int64_t M, F y, double (&acc)[L]) {
-  double ring[L];
-#pragma unroll
-  for (int l = 0; l < L; ++l) ring[l] = 0.0;
-  for (int64_t i0 = t0; i0 < M; i0 += L) {
-#pragma unroll
-    for (int u = 0; u < L; ++u) {
-      const int64_t i = i0 + u;
-      double a = 0.0, b = 0.0;
-      if (i < M) {
-        a = y(i);
-        b = t0 == 0 ? a : y(i - t0);
-      }
-      ring[u] = b;
-#pragma unroll
-      for (int l = 0; l < L; ++l) acc[l] = fma(a, ring[(u - l + L) % L], acc[l]);
-    }
-  }
-}
+// d_lag_block<L>(t0, M, y, post, acc) (omc_lag_block.h): with z(i) = post(y(i)), acc[l] += sum_{i = t0 + l}^{M-1} z(i) z(i - t0 - l),
+// l < L, the lane's contribution to S(t0 + l)
 
 // Long form, pass 1: the two split means of every (chain, element); the middle draw of an odd N only for its NaN.
 // means [J][size], series j = 2 c + h
@@ -109,7 +90,7 @@ __global__ void __launch_bounds__(256) k_diag_lags(const double* __restrict__ st
   for (int64_t s = (int64_t)g * spg + wave; s < s1; s += 4) {
     const double m = means[s * size + kc];
     const double* q = store + (s >> 1) * size + kc + ((s & 1) ? N - M : 0) * row;
-    d_lag_block<L>(t0, M, [&](int64_t i) { return q[i * row] - m; }, acc);
+    d_lag_block<L>(t0, M, [&](int64_t i) { return q[i * row]; }, [&](double x) { return x - m; }, acc);
     if (t0 == 0) omc_welford(bn, bm, bq, m);
   }
   // the four waves' sums in a fixed order: ((w3 + w2) + w1) + w0
@@ -168,7 +149,7 @@ __global__ void __launch_bounds__(512) k_diag_short(const double* __restrict__ s
     for (int64_t i = 0; i < M; ++i) s += xh[i * D_TILE] - x0;
     double m = x0 + s / (double)M;
     if (mid[lane] != mid[lane]) m = mid[lane];
-    d_lag_block<S_L>(S_L * blk, M, [&](int64_t i) { return xh[i * D_TILE] - m; }, acc);
+    d_lag_block<S_L>(S_L * blk, M, [&](int64_t i) { return xh[i * D_TILE]; }, [&](double x) { return x - m; }, acc);
     if (blk == 0) omc_welford(bn, bm, bq, m);
     __syncthreads();
   }

@@ -1458,6 +1458,35 @@ class Engine:
         check(st)
         return out, cnt
 
+    def store_autocorr(self, store, max_lag, index=None, pooled=True, normalize=True):
+        """Autocorrelation of every selected element of a device store (n_iter, C, size), on the device (omc_store_autocorr):
+        (acf, tau, window, mean) as device tensors.  acf is fp64 (n_idx, max_lag + 1) pooled -- the chains' autocovariances
+        around their own means, averaged -- else (C, n_idx, max_lag + 1) per chain: g(t) = sum_i d_i d_{i+t} / n_iter of the
+        centred draws, divided by g(0) with normalize.  tau, fp64 (n_idx,) or (C, n_idx), is the integrated autocorrelation
+        time by Geyer's initial positive sequence, window (int32, same shape) the lags it used: a window that reaches
+        max_lag means tau is a lower bound.  mean is fp64 (C, n_idx), the per-chain means the draws were centred on.
+        0 <= max_lag <= n_iter - 1, n_iter >= 2.  A column with a NaN or infinite draw gives NaN; a column that never moved
+        an autocovariance of 0, NaN once normalised, tau NaN and window 0."""
+        torch = _torch()
+        n_iter, size = self._store_shape(store)
+        if n_iter < 2:
+            raise ValueError("the autocorrelation needs at least 2 stored iterations")
+        max_lag = int(max_lag)
+        if not 0 <= max_lag <= n_iter - 1:
+            raise ValueError(f"max_lag must lie in [0, n_iter - 1] = [0, {n_iter - 1}]")
+        idx, n = self._store_index(index, size)
+        lead = () if pooled else (self.n_chains,)
+        acf = self.empty(*lead, n, max_lag + 1)
+        tau = self.empty(*lead, n)
+        window = torch.empty(lead + (n,), dtype=torch.int32, device=self.device)
+        mean = self.empty(self.n_chains, n)
+        st = lib.omc_store_autocorr(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, max_lag, int(not pooled),
+                                    int(bool(normalize)), self._p(acf), self._p(tau), window.data_ptr(), self._p(mean))
+        if st == _abi.INVALID_ARG:  # the library says which argument
+            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
+        check(st)
+        return acf, tau, window, mean
+
     def store_thin(self, store, every, first=0):
         """store[first::every] of a device store (n_iter, C, ...) as a packed device tensor (one launch)."""
         if store.dim() < 2 or store.shape[1] != self.n_chains or not store.is_contiguous():

@@ -511,6 +511,25 @@ class MCMC:
         critical = float(self.engine.store_quantiles(m.unsqueeze(-1).contiguous(), float(prob), pooled=True, omit_nan=True).cpu().numpy()[0, 0])
         return {"lower": mean - critical * sd, "upper": mean + critical * sd, "mean": mean, "sd": sd, "critical": critical}
 
+    def autocorrelation(self, key, max_lag=None, index=None, pooled=True, normalize=True):
+        """Autocorrelation function and integrated autocorrelation time of store[key], computed on the device (no gather of the
+        store): a dict of host arrays "acf" (n_idx, max_lag + 1), "tau" (n_idx,) and "window" (n_idx,), or per chain
+        (pooled=False) (C, n_idx, max_lag + 1), (C, n_idx), (C, n_idx).  The estimator: g(t) = sum_i (x_i - m)(x_{i+t} - m) / n_iter
+        around each chain's own mean m, averaged over the chains when pooled, "acf" = g(t) / g(0) (normalize=False: g(t), the
+        autocovariance), and tau = -1 + 2 sum of the pairs rho(2k) + rho(2k+1) while they are positive (Geyer's initial positive
+        sequence).  ceil(tau) is the thinning at which stored draws are roughly independent: the way to choose n_thin.
+        "window" is the number of lags the sum used; a window that reaches max_lag (max_lag - 1 for an even max_lag) means
+        the sequence was cut off and tau is a lower bound: raise max_lag.  max_lag defaults to min(100, n_iter - 1).  index
+        selects elements (in that order, repeats allowed); a 2-D entry ("log_post") counts as one element, and an entry made
+        by derive(name=...) is a key like any other.  An element with a NaN or infinite draw gives NaN; one that never moved
+        gives tau NaN and window 0.  Under a sharded multi-GPU run this summarises this rank's chains only."""
+        self._whole_store_on_device("autocorrelation")
+        t = self._store_3d(key)
+        if max_lag is None:
+            max_lag = min(100, t.shape[0] - 1)
+        acf, tau, window, _ = self.engine.store_autocorr(t, max_lag, index=index, pooled=pooled, normalize=normalize)
+        return {"acf": acf.cpu().numpy(), "tau": tau.cpu().numpy(), "window": window.cpu().numpy()}
+
     def _store_3d(self, key):
         t = self.store[key]
         return (t.unsqueeze(-1) if t.dim() == 2 else t.reshape(t.shape[0], t.shape[1], -1)).contiguous()
