@@ -43,7 +43,7 @@ def main():
         dt = (time.perf_counter() - t0) / 15
         M.engine.check_status()
         lam = M.store["lambda"].mean().item()
-        print(f"n={n} C={C}: {1e3 * dt:.2f} ms per sweep = {C / dt:.0f} chain-updates/s; plan {samplers[0].plan(M.state)['kind']}; lambda mean {lam:.1f}; "
+        print(f"n={n} C={C}: {1e3 * dt:.2f} ms per sweep = {C / dt:.0f} chain-updates/s; plan {samplers[0].plan(M.state).kind}; lambda mean {lam:.1f}; "
               f"band joins retried {M.engine.counter('band_join_retries')}, in one piece {M.engine.counter('band_join_fallbacks')}")
         del M
 

@@ -49,7 +49,7 @@ def main():
     M.engine.check_status()
     out = M.collect()
     print(f"n={n} p={p} C={C}: {1e3 * dt:.2f} ms per sweep = {C / dt:.0f} chain-updates/s; kinds "
-          f"{samplers[0].plan(M.state)['kind']}/{samplers[1].plan(M.state)['kind']}; "
+          f"{samplers[0].plan(M.state).kind}/{samplers[1].plan(M.state).kind}; "
           f"all finite: {bool(np.isfinite(out['b']).all() and np.isfinite(out['tau']).all())}; lambda / tau at the end {out['lambda'][:, 0, -1].mean() / out['tau'][:, 0, -1].mean():.3g}; "
           f"band joins retried {M.engine.counter('band_join_retries')}, in one piece {M.engine.counter('band_join_fallbacks')} (groups of 64 chains x draws)")
 

@@ -50,7 +50,7 @@ def main():
     eb = np.abs(out["beta"].mean(axis=(0, 2)) - beta).max()
     eg = np.abs(out["gamma"].mean(axis=(0, 2)) - gamma).max()
     print(f"n={n} p={p} q={q} C={C}: {1e3 * dt:.2f} ms per sweep = {C / dt:.0f} chain-updates/s; kinds "
-          f"{samplers[0].plan(M.state)['kind']}/{samplers[1].plan(M.state)['kind']}; posterior mean error beta {eb:.2e}, gamma {eg:.2e}; "
+          f"{samplers[0].plan(M.state).kind}/{samplers[1].plan(M.state).kind}; posterior mean error beta {eb:.2e}, gamma {eg:.2e}; "
           f"tau mean {out['tau'].mean():.1f} (truth 100)")
 
 

@@ -52,6 +52,8 @@ class Engine:
         # library writes into caller tensors that torch's version counter does not see (see note_write)
         self._write_serial = 0
         self._written = {}
+        # per-model constants and the quadratic forms a draw left behind, filled on demand
+        self._quad_cache, self._logdet_cache, self._shared_cache, self._band_cache, self._model_cache = {}, {}, {}, {}, {}
 
     # ------------------------------------------------------------------ memory helpers
     def empty(self, *shape):
@@ -120,12 +122,10 @@ class Engine:
         """The fused quadratic form of a draw IS the residual statistic r'Mr of `dist` for the state the draw leaves
         (sampler.py:276,284; gmrf.py:343-344).  Kept with what it was computed from -- the device tensors of the state
         entries the residual reads -- and handed out by `quad_cache_get` while none of them has been replaced or written."""
-        if not hasattr(self, "_quad_cache"):
-            self._quad_cache = {}
         self._quad_cache[id(dist)] = (dist, quad, [(t, t.data_ptr(), t._version) for t in inputs], self._write_serial)
 
     def quad_cache_get(self, dist, inputs):
-        hit = getattr(self, "_quad_cache", {}).get(id(dist))
+        hit = self._quad_cache.get(id(dist))
         if hit is None or hit[0] is not dist or len(hit[2]) != len(inputs):
             return None
         for (t0, ptr, ver), t in zip(hit[2], inputs):
@@ -510,8 +510,6 @@ class Engine:
     # ------------------------------------------------------------------ per-model constants
     def matrix_logdet(self, st):
         """Device scalar log det M of a Normal's unscaled precision (tridiagonal bands), cached."""
-        if not hasattr(self, "_logdet_cache"):
-            self._logdet_cache = {}
         hit = self._logdet_cache.get(id(st.matrix))
         if hit is not None and hit[0] is st.matrix:
             return hit[1]
@@ -536,8 +534,6 @@ class Engine:
         """Device copy of a shared host array (dense or scipy.sparse -> dense), cached by identity."""
         from scipy import sparse
 
-        if not hasattr(self, "_shared_cache"):
-            self._shared_cache = {}
         hit = self._shared_cache.get(id(array))
         if hit is not None and hit[0] is array:
             return hit[1]
@@ -549,8 +545,6 @@ class Engine:
     def band_cache(self, dist, st, center):
         """Device copies of a banded Normal's shared pieces: band rows of M, the vector m its residual is taken around
         and M m (host product, once per model)."""
-        if not hasattr(self, "_band_cache"):
-            self._band_cache = {}
         key = (id(dist), id(st.matrix))
         c_host = np.ascontiguousarray(center, dtype=np.float64).reshape(-1)
         hit = self._band_cache.get(key)
@@ -566,8 +560,6 @@ class Engine:
     def model_cache(self, dist, state, st, center):
         """Device copies of one Normal's shared pieces (bands of M, the vector m its residual is taken
         around, M m, log det M), built once per (distribution, matrix, vector) and reused every sweep."""
-        if not hasattr(self, "_model_cache"):
-            self._model_cache = {}
         key = (id(dist), id(st.matrix))
         hit = self._model_cache.get(key)
         c_host = np.ascontiguousarray(center, dtype=np.float64).reshape(-1)

@@ -24,8 +24,8 @@ from scipy import sparse
 
 from openmcmc_amd.chains import ChainArray, host_2d, is_chain
 from openmcmc_amd.model import Model
-from openmcmc_amd.parameter import ScaledMatrix
-from openmcmc_amd.sampler.sampler import MCMCSampler, NormalGamma, NormalNormal
+from openmcmc_amd.parameter import LinearCombination, ScaledMatrix
+from openmcmc_amd.sampler.sampler import MCMCSampler, MixtureAllocation, NormalGamma, NormalNormal
 
 
 @dataclass
@@ -114,47 +114,49 @@ class MCMC:
             plan = nn.plan(self.state)
         except NotImplementedError:
             return None
-        if plan["kind"] != "tridiag" or plan.get("offsets") or plan.get("chain_rhs") or plan.get("center_chain") or plan.get("replicated") \
-                or plan.get("limits") is not None:
+        if plan.kind != "tridiag" or plan.chain_terms or plan.center_chain or plan.replicated or plan.limits is not None:
             return None
         term_of = {}
-        for k, key in enumerate(plan["keys"]):
+        for k, key in enumerate(plan.keys):
             prec = nn.model[key].precision
             if isinstance(prec, ScaledMatrix):
                 term_of[prec.scalar] = k
-        blocks = [None] * len(plan["keys"])
+        blocks = [None] * len(plan.keys)
         for pos, g in enumerate(gammas, start=1):
             k = term_of.get(g.param)
-            if k is None or g.normal_param != plan["keys"][k] or blocks[k] is not None:
+            if k is None or g.normal_param != plan.keys[k] or blocks[k] is not None:
                 return None
             blocks[k] = (pos, g)
-        expected = set(plan["keys"]) | {g.param for g in gammas}
+        expected = set(plan.keys) | {g.param for g in gammas}
         full_model = set(self.model.keys()) == expected
         return {"nn": nn, "plan": plan, "blocks": blocks, "log_post": full_model}
+
+    def _gamma_specs(self, draw_index0, rows):
+        """One spec per term of the fused plan for the library's Gamma blocks: the block of sampler `pos` draws from index
+        draw_index0 + pos and writes into the rows `rows` of its store (None: nowhere)."""
+        f = self._fused
+        nn, plan = f["nn"], f["plan"]
+        specs = []
+        for k, key in enumerate(plan.keys):
+            spec = {"enabled": False, "logdet": plan.logdets[k]}
+            if f["blocks"][k] is not None:
+                pos, g = f["blocks"][k]
+                a0, b0 = g.prior_shape_rate(self.state)
+                spec.update(enabled=True, a0=a0, b0=b0, n_pos=nn.model[key].structure(self.state).n_pos, draw_index=draw_index0 + pos,
+                            g=g.inject(g, g._sweep) if g.inject is not None else None,
+                            store=None if rows is None else self.store[g.param][rows, :, 0])
+            specs.append(spec)
+        return specs
 
     def _fused_sweep(self, store_it):
         eng, f = self.engine, self._fused
         nn, plan = f["nn"], f["plan"]
-        ns, t = len(self.samplers), nn._sweep
-        n = plan["n"]
-        specs = []
-        for k, key in enumerate(plan["keys"]):
-            dist = nn.model[key]
-            st = dist.structure(self.state)
-            x_or_y, m = (None, None)
-            cache = eng._model_cache[(id(dist), id(st.matrix))]
-            spec = {"enabled": False, "logdet": cache["logdet"]}
-            if f["blocks"][k] is not None:
-                pos, g = f["blocks"][k]
-                a0, b0 = g.prior_shape_rate(self.state)
-                spec.update(enabled=True, a0=a0, b0=b0, n_pos=st.n_pos, draw_index=t * ns + pos,
-                            g=g.inject(g, g._sweep) if g.inject is not None else None,
-                            store=self.store[g.param][store_it, :, 0] if store_it is not None else None)
-            specs.append(spec)
+        ns, t, n = len(self.samplers), nn._sweep, plan.n
+        specs = self._gamma_specs(t * ns, store_it)
         x_out = self.store[nn.param][store_it] if store_it is not None else self._scratch(n)
         lp = self.store["log_post"][store_it] if (store_it is not None and f["log_post"]) else None
         z = nn.inject(nn, nn._sweep) if getattr(nn, "inject", None) is not None else None  # (test hook set after construction)
-        eng.gmrf_sweep(n, plan["terms"], specs, x_out, z=z, draw_index=t * ns, log_post_out=lp)
+        eng.gmrf_sweep(n, plan.terms, specs, x_out, z=z, draw_index=t * ns, log_post_out=lp)
         self.state[nn.param] = ChainArray(x_out)
         for s in self.samplers:
             s._sweep += 1
@@ -182,18 +184,8 @@ class MCMC:
         """The whole loop as one omc_gmrf_run call: possible when no draws are injected."""
         eng, f = self.engine, self._fused
         nn, plan = f["nn"], f["plan"]
-        ns, n = len(self.samplers), plan["n"]
-        specs = []
-        for k, key in enumerate(plan["keys"]):
-            dist = nn.model[key]
-            st = dist.structure(self.state)
-            spec = {"enabled": False, "logdet": eng._model_cache[(id(dist), id(st.matrix))]["logdet"]}
-            if f["blocks"][k] is not None:
-                pos, g = f["blocks"][k]
-                a0, b0 = g.prior_shape_rate(self.state)
-                spec.update(enabled=True, a0=a0, b0=b0, n_pos=st.n_pos, draw_index=pos,
-                            store=self.store[g.param][:, :, 0])
-            specs.append(spec)
+        ns, n = len(self.samplers), plan.n
+        specs = self._gamma_specs(0, slice(None))  # (a block's offset inside a sweep's draw indices; its whole store)
         # one library call for the whole run -- or, with a ring store, one per half of the ring: the drain stream empties
         # the half just filled while the next call fills the other (same draw indices, same results as the single call)
         it, burn = 0, self.n_burn
@@ -201,7 +193,7 @@ class MCMC:
             k = min(self._half, self.n_iter - it)
             if self._drain is not None:
                 self._drain.acquire(it)
-            eng.gmrf_run(n, plan["terms"], specs, burn, k, self.n_thin, self.store[nn.param],
+            eng.gmrf_run(n, plan.terms, specs, burn, k, self.n_thin, self.store[nn.param],
                          self._scratch(n), draw_index0=nn._sweep * ns, draws_per_sweep=ns, first_slot=it % self._n_dev,
                          log_post_store=self.store["log_post"] if f["log_post"] else None)
             for s in self.samplers:
@@ -216,9 +208,6 @@ class MCMC:
         """{sampler index: [(response key, predictor parameter)]}: stored LinearCombination predictors that may be evaluated
         right after that sampler because nothing later in the sweep changes their inputs.  Only when every later sampler is a
         conjugate one (it replaces its own parameter and nothing else) whose parameter the predictor does not use."""
-        from openmcmc_amd.parameter import LinearCombination
-        from openmcmc_amd.sampler.sampler import MixtureAllocation, NormalGamma, NormalNormal
-
         plan = {}
         if self._fused is not None or self.model.response is None:
             return plan
@@ -247,17 +236,10 @@ class MCMC:
         if (self._fused is not None and self._fused["log_post"] and self.n_iter > 0
                 and all(getattr(s, "inject", None) is None for s in self.samplers)):
             self._run_fused_in_c()
-            eng.check_status()
-            if self._drain is not None:
-                self._drain.wait()  # like the reference, run_mcmc returns with the whole store where the user reads it
-            return
+            return self._finish()
         if self._mala_block_route():
             self._run_mala_blocks()
-            eng.check_status()
-            if self._drain is not None:
-                self._drain.wait()
-            self._print_acceptance()
-            return
+            return self._finish()
         early = self._early_freeze_plan()
         for i_it in range(-self.n_burn, self.n_iter):
             storing = i_it >= 0
@@ -317,7 +299,11 @@ class MCMC:
                     par._frozen = None
             if self._drain is not None and ((i_it + 1) % self._half == 0 or i_it == self.n_iter - 1):
                 self._drain.release(i_it - i_it % self._half, i_it + 1)
-        eng.check_status()  # raises numpy.linalg.LinAlgError like gmrf.py:518 if a factorisation failed
+        self._finish()
+
+    def _finish(self):
+        """The end of run_mcmc: like the reference it returns with the whole store where the user reads it."""
+        self.engine.check_status()  # raises numpy.linalg.LinAlgError like gmrf.py:518 if a factorisation failed
         if self._drain is not None:
             self._drain.wait()
         self._print_acceptance()

@@ -9,7 +9,7 @@ how chains are sharded over GPUs.
 """
 
 from abc import ABC, abstractmethod
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Union
 
 import numpy as np
@@ -38,6 +38,8 @@ class MCMCSampler(ABC):
         self._position, self._n_samplers, self._sweep = 0, 1, 0
         self._plan = None
         self.inject = None  # test hook: callable(sampler, sweep) -> injected draws (device tensor)
+        self._later_params = frozenset()  # the parameters the rest of the sweep samples after this block (MCMC sets it)
+        self._rep_structs = {}  # NormalNormal: the structures of replicated responses, by key
 
     def bind(self, engine, position=0, n_samplers=1):
         self.engine, self._position, self._n_samplers = engine, position, n_samplers
@@ -117,6 +119,57 @@ def _as_chain_scalar(engine, state, key):
 
 
 @dataclass
+class _Piece:
+    """What Q and b receive from one distribution of the conditional model."""
+
+    key: str
+    dist: object
+    st: object                # its NormalStructure (of n_rep * M for a replicated response)
+    design: object = None     # A of a regression likelihood, None for the identity
+    offset: bool = False      # the rest of the mean is per chain: d_c in y - d_c
+    center: object = None     # the shared (n, 1) vector the term is centred at
+    chain_vec: object = None  # ("mean", dist) / ("response", key): the term is centred at a per-chain vector
+    replicated: bool = False
+
+    def chain_terms(self, op):
+        """The per-chain contributions of the piece through its operator `op`: the offset before the vector."""
+        found = [ChainTerm("offset", self.dist, self.st.scale_key, op)] if self.offset else []
+        return found + ([ChainTerm(*self.chain_vec, self.st.scale_key, op)] if self.chain_vec is not None else [])
+
+
+@dataclass
+class ChainTerm:
+    """One per-chain contribution to the right-hand side: b_c += s_c op v_c (sampler.py:181-192)."""
+
+    kind: str         # "offset": v_c = -s_c d_c, the scalar already inside; "mean" / "response": a sampled prior mean / response
+    what: object      # the distribution ("offset", "mean") or the state key ("response")
+    scale_key: object
+    op: object = None  # None (identity), ("tridiag", diag, off), ("band", rows) or ("dense", (p, n_obs) operator)
+
+
+@dataclass
+class NormalPlan:
+    """The device-side description of Q and b, built once per model; every route fills the fields it uses."""
+
+    kind: str = "dense"  # or "tridiag", "band", "ragged"
+    n: int = 0
+    terms_list: list = field(default_factory=list)  # one dict of device tensors per term ...
+    terms: object = None                            # ... and the library's struct of them
+    keys: list = field(default_factory=list)
+    limits: object = None          # (lower, upper) of a truncated prior
+    mixture_prior: object = None   # the prior, when its diagonal precision and mean are per chain
+    chain_terms: list = field(default_factory=list)   # [ChainTerm] in the order they are added to b_c
+    center_chain: list = field(default_factory=list)  # tridiag: [(term index, ChainTerm)] whose product the launch forms itself
+    quad_ok: list = field(default_factory=list)       # per term: the draw's quadratic form is the term's residual statistic
+    quad_factor: list = field(default_factory=list)   # ... times this
+    quad_terms: object = None      # band route of a long tridiagonal chain: the terms of its quadratic-form launch
+    replicated: bool = False
+    like: object = None            # ragged: (key, dist, structure) of the one likelihood
+    logdets: list = field(default_factory=list)  # tridiag: log det M_k per term
+    spectral: object = False       # dense: False until tried, then None or (k_mat, V, ev)
+
+
+@dataclass
 class NormalNormal(MCMCSampler):
     """Normal-Normal conjugate update (sampler.py:121-207): x ~ N(Q^{-1} b, Q^{-1}),
     Q = P + sum_k A_k' W_k A_k, b = P m + sum_k A_k' W_k (y_k - d_k).
@@ -129,10 +182,6 @@ class NormalNormal(MCMCSampler):
       ragged       a variable-size parameter with a mixture prior and a per-chain design matrix (reversible jump);
     a prior with domain limits switches the tridiagonal, dense and ragged routes to the truncated single-site scan (a
     truncated mixture prior included: scalar limits on a ragged parameter)."""
-
-    def __post_init__(self):
-        super().__post_init__()
-        self._is_response = {key: key == self.param for key in self.model.keys()}
 
     # -- plan: the device-side description of Q and b, built once --
     def _build_plan(self, state):
@@ -147,7 +196,7 @@ class NormalNormal(MCMCSampler):
                                    and is_chain(state[d.mean.form[self.param]]) for k, d in self.model.items())
             if per_chain_design or state[self.param].ragged is not None:
                 plan = self._ragged_plan(state, n)
-                plan["limits"] = self._ragged_limits(prior)
+                plan.limits = self._ragged_limits(prior)
                 return plan
         pieces = []  # one per distribution: what Q and b receive from it
         for key, dist in self.model.items():
@@ -156,15 +205,14 @@ class NormalNormal(MCMCSampler):
             if not isinstance(dist, Normal):
                 raise TypeError("NormalNormal handles Normal distributions only")
             st = dist.structure(state)
-            piece = {"key": key, "dist": dist, "st": st, "design": None, "offset": False}
-            if self._is_response[key]:
+            piece = _Piece(key, dist, st)
+            if key == self.param:
                 if _mean_is_chain(dist.mean, state):
                     # a prior mean that is itself sampled (hierarchical model): b_c += s_c M m_c every sweep on the
                     # device (sampler.py:181-183); nothing shared goes into the plan for this term
-                    piece["center"], piece["chain_vec"] = np.zeros((n, 1)), ("mean", dist)
+                    piece.center, piece.chain_vec = np.zeros((n, 1)), ("mean", dist)
                 else:
-                    mean = dist.mean.predictor(state)  # sampler.py:183: b += Q_rsp @ mean
-                    piece["center"] = np.asarray(mean, dtype=np.float64)
+                    piece.center = np.asarray(dist.mean.predictor(state), dtype=np.float64)  # sampler.py:183: b += Q_rsp @ mean
             else:
                 # likelihood: the parameter enters the mean linearly (sampler.py:185-192)
                 if isinstance(dist.mean, Identity):
@@ -177,21 +225,20 @@ class NormalNormal(MCMCSampler):
                                                   "its conditional is not Gaussian (use ManifoldMALA)")
                     A = state[dist.mean.form[self.param]]
                     if not _is_identity(A, n):
-                        piece["design"] = A
+                        piece.design = A
                     if dist.mean.has_chain_terms(state, exclude=self.param):
                         # per-chain offset d_c in y - d_c (e.g. a basis expansion B_c beta_c next to the GMRF):
                         # evaluated on the device every sweep and fed to the solve as a per-chain rhs
-                        piece["offset"], rest = True, 0.0
+                        piece.offset, rest = True, 0.0
                     else:
                         rest = dist.mean.predictor_conditional(state, term_to_exclude=self.param)
                 y = state[key]
                 if is_chain(y):
                     # a response that is itself sampled (the parameter is the mean of another sampled vector):
                     # b_c += s_c W (y_c - d) with y_c per chain (sampler.py:185-192)
-                    if piece["design"] is not None or piece["offset"] or y.shape[1] != 1:
+                    if piece.design is not None or piece.offset or y.shape[1] != 1:
                         raise NotImplementedError("per-chain response under a design matrix, with per-chain offsets, or replicated")
-                    piece["center"] = -np.asarray(rest, dtype=np.float64) * np.ones((n, 1))
-                    piece["chain_vec"] = ("response", key)
+                    piece.center, piece.chain_vec = -np.asarray(rest, dtype=np.float64) * np.ones((n, 1)), ("response", key)
                     pieces.append(piece)
                     continue
                 y = np.asarray(y, dtype=np.float64)
@@ -203,16 +250,13 @@ class NormalNormal(MCMCSampler):
                         # (the reference fails here too: b (p, 1) += A'W(y - d) of shape (p, n_rep), sampler.py:192)
                         raise NotImplementedError("replicated response under a LinearCombination mean")
                     y = y.mean(axis=1, keepdims=True)
-                    piece["st"] = st = self._replicated_structure(key, st, n_rep)
-                    piece["replicated"] = True
-                piece["center"] = y - rest
+                    piece.st, piece.replicated = self._replicated_structure(key, st, n_rep), True
+                piece.center = y - rest
             pieces.append(piece)
-        tridiagonal = all(pc["design"] is None and pc["st"].diag is not False and pc["st"].n == n for pc in pieces)
-        banded = all(pc["design"] is None and pc["st"].n == n and (pc["st"].diag is not False or pc["st"].band is not None)
-                     for pc in pieces)
+        tridiagonal = all(pc.design is None and pc.st.diag is not False and pc.st.n == n for pc in pieces)
+        banded = all(pc.design is None and pc.st.n == n and (pc.st.diag is not False or pc.st.band is not None) for pc in pieces)
         if mixture_prior:
-            plan = self._dense_plan(state, n, pieces)
-            plan["mixture_prior"] = prior
+            plan = self._dense_plan(state, n, pieces, mixture_prior=prior)
         elif tridiagonal and n <= self.TRIDIAG_WG_MAX:
             plan = self._tridiag_plan(state, n, pieces)
         elif banded:  # (long tridiagonal chains too: beyond one workgroup per chain the segmented lane kernels of the band
@@ -220,7 +264,7 @@ class NormalNormal(MCMCSampler):
             plan = self._band_plan(state, n, pieces)
         else:
             plan = self._dense_plan(state, n, pieces)
-        plan["limits"] = self._domain_limits(prior, n)
+        plan.limits = self._domain_limits(prior, n)
         return plan
 
     def _domain_limits(self, prior, n):
@@ -258,70 +302,61 @@ class NormalNormal(MCMCSampler):
         """The structure of n_rep * M (kept on the sampler so the device cache sees one stable matrix object)."""
         from openmcmc_amd.distribution.location_scale import NormalStructure
 
-        memo = self.__dict__.setdefault("_rep_structs", {})
-        hit = memo.get(key)
+        hit = self._rep_structs.get(key)
         if hit is None or hit[0] is not st.matrix or hit[1].n_pos != st.n_pos:
-            if st.diag is False:  # dense or banded wider than tridiagonal
-                rep = NormalStructure(n=st.n, matrix=st.matrix * float(n_rep), scale_key=st.scale_key, diag=False, off=None,
-                                      n_pos=st.n_pos, band=None if st.band is None else st.band * float(n_rep))
-            else:
-                diag = np.full(st.n, float(n_rep)) if st.diag is None else st.diag * float(n_rep)
-                off = None if st.off is None else st.off * float(n_rep)
-                rep = NormalStructure(n=st.n, matrix=st.matrix * float(n_rep), scale_key=st.scale_key, diag=diag, off=off,
-                                      n_pos=st.n_pos)
-            hit = memo[key] = (st.matrix, rep)
+            r, wide = float(n_rep), st.diag is False  # wide: dense, or banded with its band rows (no tridiagonal bands)
+            diag = False if wide else (np.full(st.n, r) if st.diag is None else st.diag * r)
+            off = None if wide or st.off is None else st.off * r
+            rep = NormalStructure(n=st.n, matrix=st.matrix * r, scale_key=st.scale_key, diag=diag, off=off, n_pos=st.n_pos,
+                                  band=None if st.band is None else st.band * r)
+            hit = self._rep_structs[key] = (st.matrix, rep)
         return hit[1]
 
     def _tridiag_plan(self, state, n, pieces):
         eng = self.engine
-        terms, keys, offsets = [], [], []
+        terms, caches = [], []
         for pc in pieces:
-            st = pc["st"]
-            if pc["offset"]:
-                if st.diag is not None or st.off is not None:
-                    raise NotImplementedError("per-chain offset under a non-identity response precision")
-                offsets.append((pc["dist"], st.scale_key))
-            cache = eng.model_cache(pc["dist"], state, st, pc["center"])
+            st = pc.st
+            if pc.offset and (st.diag is not None or st.off is not None):
+                raise NotImplementedError("per-chain offset under a non-identity response precision")
+            cache = eng.model_cache(pc.dist, state, st, pc.center)
             scale = _as_chain_scalar(eng, state, st.scale_key) if st.scale_key is not None else None
             terms.append({"diag": cache["diag"], "off": cache["off"], "rhs": cache["rhs"], "center": cache["center"],
                           "scale": None if scale is None else scale.scalar()})
-            keys.append(pc["key"])
+            caches.append(cache)
         # A term centred at a per-chain vector (sampled prior mean, sampled response): where the kernel takes it
         # (omc_tridiag_terms.center_chain: the workgroup-per-chain form) the launch forms s_c M v_c itself and its fused
         # quadratic form is the term's residual statistic; elsewhere the product vector is made by a launch of its own
-        # and fed in as a per-chain right-hand side.
-        in_launch = eng.tridiag_takes_center_chain(n) and sum(pc.get("chain_vec") is not None for pc in pieces) == 1  # (one per launch)
-        chain_rhs = [(pc["chain_vec"], pc["st"].scale_key, eng.model_cache(pc["dist"], state, pc["st"], pc["center"]))
-                     for pc in pieces if pc.get("chain_vec") is not None and not in_launch]
-        center_chain = [(k, pc["chain_vec"]) for k, pc in enumerate(pieces) if pc.get("chain_vec") is not None and in_launch]
+        # and fed in as a per-chain right-hand side.  The offsets (identity operator) come before the vectors.
+        in_launch = eng.tridiag_takes_center_chain(n) and sum(pc.chain_vec is not None for pc in pieces) == 1  # (one per launch)
+        offsets = [ChainTerm("offset", pc.dist, pc.st.scale_key) for pc in pieces if pc.offset]
+        vectors = [(k, ChainTerm(*pc.chain_vec, pc.st.scale_key, ("tridiag", caches[k]["diag"], caches[k]["off"])))
+                   for k, pc in enumerate(pieces) if pc.chain_vec is not None]
         # terms whose fused quadratic form equals the distribution's residual statistic for the state the draw leaves
-        quad_ok = [not pc["offset"] and not pc.get("replicated") and (pc.get("chain_vec") is None or in_launch) for pc in pieces]
+        quad_ok = [not pc.offset and not pc.replicated and (pc.chain_vec is None or in_launch) for pc in pieces]
         # ... and of those, the ones a LATER block of the same sweep invalidates before anybody could read them (the other
         # side of the term is sampled after this block: MCMC tells the sampler which parameters follow it): not computed
-        later = getattr(self, "_later_params", frozenset())
         for k, pc in enumerate(pieces):
-            cv = pc.get("chain_vec")
-            if quad_ok[k] and cv is not None:
-                other = cv[1].mean.get_param_list() if cv[0] == "mean" else [cv[1]]
-                if any(key in later for key in other):
-                    quad_ok[k] = False
+            if quad_ok[k] and pc.chain_vec is not None:
+                kind, what = pc.chain_vec
+                quad_ok[k] = not any(key in self._later_params for key in (what.mean.get_param_list() if kind == "mean" else [what]))
         # With a per-chain centre on the tridiagonal term the library has a specialised kernel for "that term + a scaled
         # identity" (the shifted smoother, omc_tridiag.hip SIG 3).  An unscaled term with a CONSTANT diagonal d0 (a Normal prior
         # N(m0, (d0 I)^-1), say) is that identity with the scalar d0: handed over in that form -- same precision, same right-hand
         # side; its fused quadratic form then lacks the factor d0, which is put back where the form is cached.
         quad_factor = [1.0] * len(pieces)
-        if center_chain and not offsets:
+        if in_launch and not offsets:
             for k, pc in enumerate(pieces):
-                st = pc["st"]
-                if st.scale_key is None and st.off is None and st.diag is not None and pc.get("chain_vec") is None \
+                st = pc.st
+                if st.scale_key is None and st.off is None and st.diag is not None and pc.chain_vec is None \
                         and np.ptp(st.diag) == 0.0 and st.diag[0] > 0.0:
-                    d0 = float(st.diag[0])
-                    cvec = eng.model_cache(pc["dist"], state, st, pc["center"])["center"]
+                    d0, cvec = float(st.diag[0]), caches[k]["center"]
                     terms[k] = {"diag": None, "off": None, "rhs": cvec, "center": cvec, "scale": eng.full((eng.n_chains,), d0)}
                     quad_factor[k] = d0
-        return {"kind": "tridiag", "n": n, "terms_list": terms, "terms": eng.tridiag_terms(terms, n), "keys": keys,
-                "offsets": offsets, "replicated": any(pc.get("replicated") for pc in pieces), "chain_rhs": chain_rhs,
-                "center_chain": center_chain, "quad_ok": quad_ok, "quad_factor": quad_factor}
+        return NormalPlan("tridiag", n, terms, eng.tridiag_terms(terms, n), [pc.key for pc in pieces],
+                          chain_terms=offsets + ([] if in_launch else [v for _, v in vectors]),
+                          center_chain=vectors if in_launch else [], quad_ok=quad_ok, quad_factor=quad_factor,
+                          replicated=any(pc.replicated for pc in pieces), logdets=[c["logdet"] for c in caches])
 
     def _ragged_plan(self, state, n_max):
         """Small variable-size parameter with a mixture prior (diagonal precision picked by an allocation) and
@@ -343,47 +378,41 @@ class NormalNormal(MCMCSampler):
             likes.append((key, dist, st))
         if len(likes) != 1:
             raise NotImplementedError("ragged NormalNormal: exactly one likelihood term")
-        return {"kind": "ragged", "n": n_max, "like": likes[0], "terms_list": [], "keys": []}
+        return NormalPlan("ragged", n_max, like=likes[0])
 
     def _band_plan(self, state, n, pieces):
         """Q_c = sum_k s_k[c] M_k with banded M_k wider than tridiagonal (RW2, seasonal, lattice GMRFs): natural-order
         band Cholesky per chain (omc_band_sample_canonical)."""
         eng = self.engine
-        terms, keys, chain_terms = [], [], []
+        terms, chain_terms = [], []
         for pc in pieces:
-            st = pc["st"]
-            cache = eng.band_cache(pc["dist"], st, pc["center"])
+            st = pc.st
+            cache = eng.band_cache(pc.dist, st, pc.center)
             scale = _as_chain_scalar(eng, state, st.scale_key) if st.scale_key is not None else None
-            rhs = cache["rhs"]
-            if rhs is None and cache["center"] is not None:
-                rhs = cache["center"]  # identity matrix: M m = m
+            rhs = cache["rhs"] if cache["rhs"] is not None else cache["center"]  # (identity matrix: M m = m)
             terms.append({"band": cache["band"], "rhs": rhs, "scale": None if scale is None else scale.scalar()})
-            keys.append(pc["key"])
-            op = None if cache["band"] is None else ("band", cache["band"])  # per-chain vectors go through M as a band product
-            if pc["offset"]:
-                chain_terms.append((("offset", pc["dist"]), st.scale_key, op))
-            if pc.get("chain_vec") is not None:
-                chain_terms.append((pc["chain_vec"], st.scale_key, op))
-        plan = {"kind": "band", "n": n, "terms_list": terms, "terms": eng.band_terms(terms, n), "keys": keys,
-                "chain_terms": chain_terms}
+            # per-chain vectors go through M as a band product
+            chain_terms += pc.chain_terms(None if cache["band"] is None else ("band", cache["band"]))
+        plan = NormalPlan("band", n, terms, eng.band_terms(terms, n), [pc.key for pc in pieces], chain_terms=chain_terms)
         # Long tridiagonal chains arrive here too (beyond one workgroup per chain the band route's segmented kernels, w = 1).  Their
         # quadratic forms (x - m_k)' M_k (x - m_k) are the residual statistics NormalGamma and log_p ask for right after the
         # draw: ONE launch over x for all terms (omc_tridiag_quadform) behind the draw, cached like the fused forms of the
         # workgroup-per-chain kernel -- instead of one pass per distribution and caller (3.3 per sweep at n = 20 000).
-        if all(pc["st"].diag is not False and not pc["offset"] and pc.get("chain_vec") is None and not pc.get("replicated") for pc in pieces):
-            caches = [eng.model_cache(pc["dist"], state, pc["st"], pc["center"]) for pc in pieces]
-            plan["quad_terms"] = eng.tridiag_terms([{"diag": c["diag"], "off": c["off"], "center": c["center"]} for c in caches], n)
+        if all(pc.st.diag is not False and not pc.offset and pc.chain_vec is None and not pc.replicated for pc in pieces):
+            caches = [eng.model_cache(pc.dist, state, pc.st, pc.center) for pc in pieces]
+            plan.quad_terms = eng.tridiag_terms([{"diag": c["diag"], "off": c["off"], "center": c["center"]} for c in caches], n)
+            plan.quad_ok, plan.quad_factor = [True] * len(pieces), [1.0] * len(pieces)
         return plan
 
-    def _dense_plan(self, state, n, pieces):
+    def _dense_plan(self, state, n, pieces, mixture_prior=None):
         """Q_c = sum_k s_k[c] M_k with dense M_k: prior precision as is, a regression likelihood as the
         Gram matrix A' W A (one fp64 GEMM at plan time) -- sampler.py:185-192, location_scale.py:238-241."""
         eng = self.engine
-        terms, keys, chain_terms = [], [], []
+        terms, chain_terms = [], []
         for pc in pieces:
-            st, A = pc["st"], pc["design"]
-            center = eng.to_device(pc["center"].reshape(-1))
-            per_chain = pc["offset"] or pc.get("chain_vec") is not None
+            st, A = pc.st, pc.design
+            center = eng.to_device(pc.center.reshape(-1))
+            per_chain = pc.offset or pc.chain_vec is not None
             if A is None:
                 if st.n != n:
                     raise ValueError("precision / parameter size mismatch")
@@ -409,18 +438,12 @@ class NormalNormal(MCMCSampler):
                 if per_chain:  # A' W as a (p, n_obs) operator on per-chain vectors of the observation space
                     Ad = A.toarray() if hasattr(A, "toarray") else np.asarray(A, dtype=np.float64)
                     op = eng.to_device(np.ascontiguousarray((Ad if st.diag is None else Ad * np.asarray(st.diag).reshape(-1, 1)).T))
-            # what the right-hand side receives per chain and per sweep (sampler.py:181-192): the part of the mean carried by
-            # other sampled parameters (b_c -= s_c A'W d_c), a sampled prior mean (b_c += s_c M m_c), a sampled response
-            # (b_c += s_c W y_c) -- each one GEMM over all chains with the term's shared operator
-            if pc["offset"]:
-                chain_terms.append((("offset", pc["dist"]), st.scale_key, op))
-            if pc.get("chain_vec") is not None:
-                chain_terms.append((pc["chain_vec"], st.scale_key, op))
+            # per chain and per sweep b_c -= s_c A'W d_c, += s_c M m_c, += s_c W y_c: each one GEMM over all chains with `op`
+            chain_terms += pc.chain_terms(None if op is None else ("dense", op))
             scale = _as_chain_scalar(eng, state, st.scale_key) if st.scale_key is not None else None
             terms.append({"mat": mat, "rhs": rhs, "scale": None if scale is None else scale.scalar()})
-            keys.append(pc["key"])
-        return {"kind": "dense", "n": n, "terms_list": terms, "terms": eng.dense_terms(terms, n), "keys": keys,
-                "chain_terms": chain_terms}
+        return NormalPlan("dense", n, terms, eng.dense_terms(terms, n), [pc.key for pc in pieces], chain_terms=chain_terms,
+                          mixture_prior=mixture_prior)
 
     spectral = True  # class-level switch: False keeps every dense draw on the per-chain factorisation
     TRIDIAG_WG_MAX = 16384  # largest n the workgroup-per-chain tridiagonal kernel takes (omc_tridiag.hip: seg_max_n(32))
@@ -428,19 +451,18 @@ class NormalNormal(MCMCSampler):
     def _spectral_plan(self, p):
         """(k_mat, V, ev) if the dense plan is `scaled identities + one shared matrix` (order >= 64), else None; the
         eigendecomposition is made once per plan."""
-        if "spectral" not in p:
-            mats = [k for k, t in enumerate(p["terms_list"]) if t["mat"] is not None]
-            p["spectral"] = None
-            if len(mats) == 1 and p["n"] >= 64 and p.get("mixture_prior") is None and p.get("limits") is None:
-                V, ev = self.engine.dense_spectral_prepare(p["terms_list"][mats[0]]["mat"])
-                p["spectral"] = (mats[0], V, ev)
-        return p["spectral"]
+        if p.spectral is False:
+            mats = [k for k, t in enumerate(p.terms_list) if t["mat"] is not None]
+            p.spectral = None
+            if len(mats) == 1 and p.n >= 64 and p.mixture_prior is None and p.limits is None:
+                p.spectral = (mats[0], *self.engine.dense_spectral_prepare(p.terms_list[mats[0]]["mat"]))  # (k_mat, V, ev)
+        return p.spectral
 
     def plan(self, state):
         p = self._plan
         if p is not None:
             # the per-chain scalars must still be the tensors the plan points at
-            for t, key in zip(p["terms_list"], p["keys"]):
+            for t, key in zip(p.terms_list, p.keys):
                 st_key = self.model[key].precision.scalar if isinstance(self.model[key].precision, ScaledMatrix) else None
                 if st_key is not None and state[st_key].scalar().data_ptr() != t["scale"].data_ptr():
                     p = None
@@ -449,114 +471,112 @@ class NormalNormal(MCMCSampler):
             p = self._plan = self._build_plan(state)
         return p
 
+    def _chain_vector(self, term, state, scale=None):
+        """The (C, rows) vector of a ChainTerm in this state: -s_c d_c (sampler.py:190-192), the sampled mean or response."""
+        kind, what, eng = term.kind, term.what, self.engine
+        if kind == "offset":
+            return what.mean.predictor_device(state, eng, exclude=self.param, alpha=-1.0, chain_scale=scale)
+        return what.mean.predictor_device(state, eng) if kind == "mean" and not isinstance(what.mean, Identity) else \
+            state[what.mean.form if kind == "mean" else what].vector()
+
+    def _add_chain_term(self, term, state, n, rhs_chain):
+        """rhs_chain + s_c op v_c (rhs_chain None: nothing so far); a tridiagonal operator accumulates in place."""
+        eng = self.engine
+        scale = state[term.scale_key].scalar() if term.scale_key is not None else None
+        v = self._chain_vector(term, state, scale)
+        route, *op = term.op if term.op is not None else (None, None)
+        if route == "tridiag":  # (diag, off): the first product makes the tensor, the later ones accumulate into it
+            return eng.tridiag_matvec_chain(n, *op, v, scale=scale, out=rhs_chain, accumulate=rhs_chain is not None)
+        op = op[0]
+        scale = None if term.kind == "offset" else scale  # (an offset carries its scalar already)
+        if route == "dense":  # (the scalar goes onto the vector, ahead of the GEMM)
+            t = eng.design_predict(op, v if scale is None else eng.tridiag_matvec_chain(v.shape[1], None, None, v, scale=scale))
+        elif route == "band":
+            t = eng.band_matvec_chain(n, op, v, scale=scale)
+        else:
+            t = v if scale is None else eng.tridiag_matvec_chain(n, None, None, v, scale=scale)  # s_c v_c (identity matrix)
+        return t if rhs_chain is None else eng.chain_lincomb(1.0, rhs_chain, 1.0, t)
+
+    def _mixture_prior_terms(self, p, state, rhs_chain):
+        """(diag_chain, rhs_chain) with the prior N(mean[alloc], diag(prec[alloc])^-1) (parameter.py:447,501): a per-chain
+        diagonal on Q and prec * mean on b (sampler.py:181-183), next to the shared likelihood terms."""
+        _, pmean, pprec, _ = p.mixture_prior.mixture_pieces(state, self.engine)
+        prior_rhs = pprec * pmean
+        return pprec, prior_rhs if rhs_chain is None else self.engine.chain_lincomb(1.0, prior_rhs, 1.0, rhs_chain)
+
+    def _cache_quads(self, state, x, quad, p):
+        """The quadratic forms of a draw are the residual statistics of these distributions for the new state: NormalGamma
+        and log_p take them from the engine's cache instead of a pass of their own over the state."""
+        new_state = dict(state)
+        new_state[self.param] = ChainArray(x)
+        for k, key in enumerate(p.keys):
+            if p.quad_ok[k]:
+                f = p.quad_factor[k]
+                self.engine.quad_cache_put(self.model[key], quad[k] if f == 1.0 else quad[k] * f, self.model[key].residual_inputs(new_state))
+
     def sample(self, current_state: dict, out=None) -> dict:
         """sampler.py:154-207.  `out`: optional (C, n) destination (e.g. a store slab)."""
         eng = self._need_engine()
         p = self.plan(current_state)
-        n = p["n"]
+        n = p.n
         z = self.inject(self, self._sweep) if self.inject is not None else None
-        if p["kind"] == "ragged":
+        if p.kind == "ragged":
             return self._sample_ragged(current_state, p, z)
         x = eng.empty(eng.n_chains, n) if out is None else out
         rhs_chain = None
-        for dist, scale_key in p.get("offsets", ()):  # b_c -= tau_c * d_c  (sampler.py:190-192)
-            scale = current_state[scale_key].scalar() if scale_key is not None else None
-            t = dist.mean.predictor_device(current_state, eng, exclude=self.param, alpha=-1.0, chain_scale=scale)
-            rhs_chain = t if rhs_chain is None else eng.chain_lincomb(1.0, rhs_chain, 1.0, t)
-        for (kind, what), scale_key, cache in p.get("chain_rhs", ()):  # per-chain prior mean / per-chain response
-            v = what.mean.predictor_device(current_state, eng) if kind == "mean" and not isinstance(what.mean, Identity) else \
-                current_state[what.mean.form if kind == "mean" else what].vector()
-            scale = current_state[scale_key].scalar() if scale_key is not None else None
-            if rhs_chain is None:
-                rhs_chain = eng.tridiag_matvec_chain(n, cache["diag"], cache["off"], v, scale=scale)
-            else:
-                eng.tridiag_matvec_chain(n, cache["diag"], cache["off"], v, scale=scale, out=rhs_chain, accumulate=True)
-        for (kind, what), scale_key, op in p.get("chain_terms", ()):  # dense and band routes: the same three kinds, through `op`
-            scale = current_state[scale_key].scalar() if scale_key is not None else None
-            if kind == "offset":
-                v = what.mean.predictor_device(current_state, eng, exclude=self.param, alpha=-1.0, chain_scale=scale)
-            else:
-                v = what.mean.predictor_device(current_state, eng) if kind == "mean" and not isinstance(what.mean, Identity) else \
-                    current_state[what.mean.form if kind == "mean" else what].vector()
-                if scale is not None and op is not None and not isinstance(op, tuple):
-                    v = eng.tridiag_matvec_chain(v.shape[1], None, None, v, scale=scale)  # s_c v_c (identity matrix)
-            if op is None:
-                t = v if (scale is None or kind == "offset") else eng.tridiag_matvec_chain(n, None, None, v, scale=scale)
-            elif isinstance(op, tuple):
-                t = eng.band_matvec_chain(n, op[1], v, scale=None if kind == "offset" else scale)
-            else:
-                t = eng.design_predict(op, v)
-            rhs_chain = t if rhs_chain is None else eng.chain_lincomb(1.0, rhs_chain, 1.0, t)
-        if p["limits"] is not None:
+        for term in p.chain_terms:  # per-chain offsets, prior means and responses
+            rhs_chain = self._add_chain_term(term, current_state, n, rhs_chain)
+        if p.limits is not None:
             # truncated prior: the scan starts from the current value and `z` carries the injected UNIFORMS
-            lower, upper = p["limits"]
+            lower, upper = p.limits
             eng.chain_copy(current_state[self.param].vector(), x)
-            if p.get("mixture_prior") is not None:
-                # prior N(mean[alloc], diag(prec[alloc])^-1): the per-chain diagonal on Q and prec * mean on b, as below
-                _, pmean, pprec, _ = p["mixture_prior"].mixture_pieces(current_state, eng)
-                prior_rhs = pprec * pmean
-                eng.dense_gibbs_truncated(n, p["terms"], x, lower=lower, upper=upper, u=z, diag_chain=pprec,
-                                          rhs_chain=prior_rhs if rhs_chain is None else eng.chain_lincomb(1.0, prior_rhs, 1.0, rhs_chain),
+            if p.mixture_prior is not None:
+                pprec, rhs_chain = self._mixture_prior_terms(p, current_state, rhs_chain)
+                eng.dense_gibbs_truncated(n, p.terms, x, lower=lower, upper=upper, u=z, diag_chain=pprec, rhs_chain=rhs_chain,
                                           draw_index=self._draw_index())
             else:
-                gibbs = {"tridiag": eng.tridiag_gibbs_truncated, "band": eng.band_gibbs_truncated}.get(p["kind"], eng.dense_gibbs_truncated)
-                gibbs(n, p["terms"], x, lower=lower, upper=upper, u=z, rhs_chain=rhs_chain, draw_index=self._draw_index())
-        elif p["kind"] == "tridiag":
-            vecs = [None] * len(p["keys"])
-            for k, (kind, what) in p.get("center_chain", ()):
-                vecs[k] = what.mean.predictor_device(current_state, eng) if kind == "mean" and not isinstance(what.mean, Identity) else \
-                    current_state[what.mean.form if kind == "mean" else what].vector()
-            if p.get("center_chain"):
-                eng.set_center_chain(p["terms"], vecs, n)
-            quad = eng.empty(len(p["keys"]), eng.n_chains) if any(p.get("quad_ok", ())) else None
-            skip = sum(1 << k for k, ok in enumerate(p.get("quad_ok", ())) if not ok) if quad is not None else 0
+                gibbs = {"tridiag": eng.tridiag_gibbs_truncated, "band": eng.band_gibbs_truncated}.get(p.kind, eng.dense_gibbs_truncated)
+                gibbs(n, p.terms, x, lower=lower, upper=upper, u=z, rhs_chain=rhs_chain, draw_index=self._draw_index())
+        elif p.kind == "tridiag":
+            if p.center_chain:
+                vecs = [None] * len(p.keys)
+                for k, term in p.center_chain:
+                    vecs[k] = self._chain_vector(term, current_state)
+                eng.set_center_chain(p.terms, vecs, n)
+            quad = eng.empty(len(p.keys), eng.n_chains) if any(p.quad_ok) else None
+            skip = sum(1 << k for k, ok in enumerate(p.quad_ok) if not ok) if quad is not None else 0
             if skip:
                 eng.set_option("tridiag_quad_skip", skip)
             try:
-                eng.tridiag_sample_canonical(n, p["terms"], x, z=z, rhs_chain=rhs_chain, draw_index=self._draw_index(), quad_out=quad)
+                eng.tridiag_sample_canonical(n, p.terms, x, z=z, rhs_chain=rhs_chain, draw_index=self._draw_index(), quad_out=quad)
             finally:
                 if skip:
                     eng.set_option("tridiag_quad_skip", 0)
             if quad is not None:
-                # the quadratic forms of the launch are the residual statistics of these distributions for the new state:
-                # NormalGamma and log_p take them from here instead of a pass of their own over the state
-                new_state = dict(current_state)
-                new_state[self.param] = ChainArray(x)
-                for k, key in enumerate(p["keys"]):
-                    if p["quad_ok"][k]:
-                        f = p.get("quad_factor", (1.0,) * len(p["keys"]))[k]
-                        eng.quad_cache_put(self.model[key], quad[k] if f == 1.0 else quad[k] * f, self.model[key].residual_inputs(new_state))
-        elif p["kind"] == "band":
-            eng.band_sample_canonical(n, p["terms"], x, z=z, rhs_chain=rhs_chain, draw_index=self._draw_index())
-            if p.get("quad_terms") is not None:
-                quad = eng.empty(len(p["keys"]), eng.n_chains)
-                eng.tridiag_quadform(n, p["quad_terms"], x, quad)
-                new_state = dict(current_state)
-                new_state[self.param] = ChainArray(x)
-                for k, key in enumerate(p["keys"]):
-                    eng.quad_cache_put(self.model[key], quad[k], self.model[key].residual_inputs(new_state))
-        elif p.get("mixture_prior") is not None:
-            # prior N(mean[alloc], diag(prec[alloc])^-1) (parameter.py:447,501): a per-chain diagonal on Q and
-            # prec * mean on b (sampler.py:181-183), next to the shared likelihood terms
-            _, pmean, pprec, _ = p["mixture_prior"].mixture_pieces(current_state, eng)
-            prior_rhs = pprec * pmean
-            eng.dense_sample_canonical(n, p["terms"], x, z=z, diag_chain=pprec, draw_index=self._draw_index(),
-                                       rhs_chain=prior_rhs if rhs_chain is None else eng.chain_lincomb(1.0, prior_rhs, 1.0, rhs_chain))
-        elif z is None and self.spectral and self._spectral_plan(p) is not None:
+                self._cache_quads(current_state, x, quad, p)
+        elif p.kind == "band":
+            eng.band_sample_canonical(n, p.terms, x, z=z, rhs_chain=rhs_chain, draw_index=self._draw_index())
+            if p.quad_terms is not None:
+                quad = eng.empty(len(p.keys), eng.n_chains)
+                eng.tridiag_quadform(n, p.quad_terms, x, quad)
+                self._cache_quads(current_state, x, quad, p)
+        elif p.mixture_prior is not None:
+            pprec, rhs_chain = self._mixture_prior_terms(p, current_state, rhs_chain)
+            eng.dense_sample_canonical(n, p.terms, x, z=z, diag_chain=pprec, rhs_chain=rhs_chain, draw_index=self._draw_index())
+        elif z is None and self.spectral and (spectral := self._spectral_plan(p)) is not None:
             # Q_c = a_c I + b_c M with one shared M: the draw in M's eigenbasis -- two GEMMs over all chains instead of
             # one factorisation per chain.  Same conditional law and the reference's mean and log det; not its path-wise
             # image of the draws, so a replay with injected draws (z given) takes the factorisation below.
-            k_mat, V, ev = self._spectral_plan(p)
-            eng.dense_spectral_sample(n, p["terms"], k_mat, V, ev, x, rhs_chain=rhs_chain, draw_index=self._draw_index())
+            eng.dense_spectral_sample(n, p.terms, *spectral, x, rhs_chain=rhs_chain, draw_index=self._draw_index())
         else:
-            eng.dense_sample_canonical(n, p["terms"], x, z=z, rhs_chain=rhs_chain, draw_index=self._draw_index())
+            eng.dense_sample_canonical(n, p.terms, x, z=z, rhs_chain=rhs_chain, draw_index=self._draw_index())
         current_state[self.param] = ChainArray(x)
         self._sweep += 1
         return current_state
 
     def _sample_ragged(self, state, p, z):
         eng = self.engine
-        key, dist, st = p["like"]
+        key, dist, st = p.like
         prior = self.model[self.param]
         cur = state[self.param]
         _, pmean, pprec, count = prior.mixture_pieces(state, eng)
@@ -572,10 +592,10 @@ class NormalNormal(MCMCSampler):
                 y = eng.to_device(np.asarray(state[key], dtype=np.float64).reshape(-1) - np.asarray(host).reshape(-1))
         gram, rhs = eng.design_gram_batched(B.columns(), w=w, resid_shared=y, resid_chain=rest, count=B.count(state))
         scale = _as_chain_scalar(eng, state, st.scale_key).scalar() if st.scale_key is not None else None
-        if p["limits"] is not None:
+        if p.limits is not None:
             # truncated prior: one scan of single-site updates from the current value; `z` carries the injected UNIFORMS
             x = cur.vector().clone()
-            eng.small_gibbs_truncated(gram, rhs, pprec, x, lower=p["limits"][0], upper=p["limits"][1], lik_scale=scale,
+            eng.small_gibbs_truncated(gram, rhs, pprec, x, lower=p.limits[0], upper=p.limits[1], lik_scale=scale,
                                       prior_mean=pmean, count=count, u=z, draw_index=self._draw_index())
         else:
             x = eng.small_sample_canonical(gram, rhs, pprec, lik_scale=scale, prior_mean=pmean, count=count, z=z,
@@ -603,6 +623,7 @@ class NormalGamma(MCMCSampler):
         super().__post_init__()
         others = [k for k in self.model.keys() if k != self.param]
         self.normal_param = others[0]
+        self._ab_dev = {}  # device copies of the mixture route's prior shapes and rates
         precision = self.model[self.normal_param].precision
         if not isinstance(precision, (Identity, ScaledMatrix, MixtureParameterMatrix)):
             raise TypeError("precision must be either Identity, ScaledMatrix or MixtureParameterMatrix")
@@ -638,7 +659,7 @@ class NormalGamma(MCMCSampler):
             raise NotImplementedError("NormalGamma on a variable-size mixture")
         alloc = state[dist.precision.allocation].vector()
         a0, b0 = self.model[self.param].host_shape_rate_vec(state, K)
-        consts = self.__dict__.setdefault("_ab_dev", {})
+        consts = self._ab_dev
         key = (a0.tobytes(), b0.tobytes())
         if key not in consts:
             consts[key] = (eng.to_device(a0), eng.to_device(b0))

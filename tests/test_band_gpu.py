@@ -174,7 +174,7 @@ def test_rw2_smoother_replays_reference(golden):
     samplers[1].inject = lambda s, it: torch.full((C,), float(G["g"][it, 0]), dtype=torch.float64, device=dev)
     samplers[2].inject = lambda s, it: torch.full((C,), float(G["g"][it, 1]), dtype=torch.float64, device=dev)
     M = MCMC(st, samplers, model=mdl, n_burn=n_burn, n_iter=n_iter, n_chains=C)
-    assert samplers[0].plan(M.state)["kind"] == "band"
+    assert samplers[0].plan(M.state).kind == "band"
     M.run_mcmc()
     got = M.collect()
     for c in range(C):
@@ -221,7 +221,7 @@ def test_rw2_per_chain_rhs_pieces_replay_reference(golden, tag):
     C = 3
     M = MCMC(state, normals + gammas, model=mdl, n_burn=int(G["n_burn"]), n_iter=int(G["n_iter"]), n_chains=C)
     eng = M.engine
-    assert normals[0].plan(M.state)["kind"] == "band"
+    assert normals[0].plan(M.state).kind == "band"
     for i, smp in enumerate(normals):
         smp.inject = lambda s_, t, i=i: eng.to_device(np.tile(G[k + "z"][t, cuts[i]:cuts[i + 1]], (C, 1)))
     for i, smp in enumerate(gammas):
@@ -254,7 +254,7 @@ def test_replicated_response_under_dense_and_band_precision(golden, tag):
     smp = NormalNormal("x", mdl)
     M = MCMC(state, [smp], model=mdl, n_burn=0, n_iter=int(G[k + "n_iter"]), n_chains=C)
     eng = M.engine
-    assert smp.plan(M.state)["kind"] == ("dense" if tag == "d" else "band")
+    assert smp.plan(M.state).kind == ("dense" if tag == "d" else "band")
     smp.inject = lambda s_, t: eng.to_device(np.tile(G[k + "z"][t], (C, 1)))
     M.run_mcmc()
     got = M.collect()
@@ -329,7 +329,7 @@ def test_long_tridiagonal_chains_take_the_band_route():
             samplers[0].inject = lambda s_, it: eng.to_device(np.tile(z[it], (C, 1)))
             samplers[1].inject = lambda s_, it: eng.full((C,), g[it, 0])
             samplers[2].inject = lambda s_, it: eng.full((C,), g[it, 1])
-            assert samplers[0].plan(M.state)["kind"] == route
+            assert samplers[0].plan(M.state).kind == route
             M.run_mcmc()
             out[route] = M.collect()
     finally:
