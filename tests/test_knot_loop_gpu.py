@@ -155,6 +155,311 @@ def test_knot_loop_kernel_against_numpy(n, weights, shared, offset, with_tau):
     eng.close()
 
 
+# ------------------------------------------------------------------------------------------------ the kernel's edges
+# Every case below is a row of KNOT_CASES: the arguments of knot_inputs().  The reference needs no GPU, so the condition
+# on the inputs (no accept decision within 1e-6 of its threshold) can be checked for the whole table on the host.
+MARGIN = 1e-6
+
+
+def gauss_column(X, knot, scale):
+    return np.exp(-(((X - knot) / scale) ** 2) / 2.0) / np.sqrt(2 * np.pi) / scale
+
+
+def knot_inputs(n, kmax, counts, seed, scale=0.8, weights=True, shared=True, offset=True, with_tau=True, step=0.4,
+                lower=-5.0, upper=5.0):
+    """Host arrays of one call: len(counts) chains, the chain c has min(counts[c], kmax) live knots."""
+    C = len(counts)
+    rng = np.random.default_rng(seed)
+    X = np.linspace(lower, upper, n)
+    count = np.array(counts, dtype=float)
+    live = np.minimum(count, kmax).astype(int)
+    theta = rng.uniform(lower, upper, size=(C, kmax))
+    beta = rng.standard_normal((C, kmax))
+    B = np.zeros((C, kmax, n))
+    for c in range(C):
+        theta[c, live[c]:] = 0.0
+        beta[c, live[c]:] = 0.0
+    inp = dict(n=n, C=C, kmax=kmax, X=X, count=count, live=live, theta=theta, beta=beta, B=B, scale=scale,
+               y=np.sin(X) + 0.3 * rng.standard_normal(n), w=0.5 + rng.random(n) if weights else None,
+               shared=0.1 * np.cos(X) if shared else None, offset=0.2 * rng.standard_normal((C, n)) if offset else None,
+               tau=2.0 + 8.0 * rng.random(C) if with_tau else None, step=step, lower=lower, upper=upper,
+               uz=rng.random((kmax, C)), uu=rng.random((kmax, C)))
+    fill_basis(inp)
+    return inp
+
+
+def fill_basis(inp):
+    for c in range(inp["C"]):
+        for j in range(inp["live"][c]):
+            inp["B"][c, j] = gauss_column(inp["X"], inp["theta"][c, j], inp["scale"])
+
+
+def knot_reference(inp, theta=None, B=None):
+    """knot_loop_numpy for every chain, and the condition on the inputs: every decision it takes is at least MARGIN
+    away from its threshold (a decision closer than rounding to it is legitimately undefined)."""
+    theta = inp["theta"] if theta is None else theta
+    B = inp["B"] if B is None else B
+    out, margin = [], np.inf
+    for c in range(inp["C"]):
+        k = inp["live"][c]
+        th, Bn, acc, las = knot_loop_numpy(inp["X"], inp["scale"], inp["y"], inp["shared"],
+                                           None if inp["offset"] is None else inp["offset"][c], inp["w"],
+                                           1.0 if inp["tau"] is None else inp["tau"][c], inp["beta"][c], theta[c], k, B[c],
+                                           inp["step"], inp["lower"], inp["upper"], inp["uz"][:, c], inp["uu"][:, c])
+        if k:
+            margin = min(margin, float(np.min(np.abs(np.log(inp["uu"][:k, c]) - np.array(las)))))
+        out.append((th, Bn, np.array(acc, dtype=np.int32), np.array(las)))
+    assert margin >= MARGIN, margin
+    return out
+
+
+def knot_device(eng, inp, theta=None, B=None, inject=True, outputs=True, draw_index=0, counters=None):
+    """One omc_knot_loop call; returns (theta, B, accept, log_alpha, n_accept, n_proposal) on the host."""
+    import torch
+
+    d = eng.to_device
+    C, kmax = inp["C"], inp["kmax"]
+    dB, dth = d(inp["B"] if B is None else B), d(inp["theta"] if theta is None else theta)
+    if counters is None:
+        counters = (torch.zeros(C, dtype=torch.int64, device=eng.device), torch.zeros(C, dtype=torch.int64, device=eng.device))
+    acc_out = torch.full((kmax, C), -1, dtype=torch.int32, device=eng.device) if outputs else None
+    la_out = eng.full((kmax, C), float("nan")) if outputs else None
+    opt = lambda v: None if v is None else d(v)  # noqa: E731
+    eng.knot_loop(d(inp["X"]), inp["scale"], d(inp["y"]), dB, d(inp["beta"]), dth, d(inp["count"]), inp["step"], inp["lower"],
+                  inp["upper"], add_shared=opt(inp["shared"]), add_chain=opt(inp["offset"]), w=opt(inp["w"]), tau=opt(inp["tau"]),
+                  inject_z=d(inp["uz"]) if inject else None, inject_u=d(inp["uu"]) if inject else None, draw_index=draw_index,
+                  accept_count=counters[0], proposal_count=counters[1], accept_out=acc_out, log_alpha_out=la_out)
+    eng.check_status()
+    host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731
+    return host(dth), host(dB), host(acc_out), host(la_out), host(counters[0]), host(counters[1])
+
+
+def knot_compare(inp, got, ref, n_acc_before=None):
+    """The bars of test_knot_loop_kernel_against_numpy: equal decisions, log_alpha to 1e-9, knots to 1e-12, basis to 1e-14."""
+    gth, gB, gacc, gla, n_acc, n_prop = got
+    for c in range(inp["C"]):
+        k = inp["live"][c]
+        th_ref, B_ref, acc_ref, la_ref = ref[c]
+        assert np.array_equal(gacc[:k, c], acc_ref), c
+        assert np.all(gacc[k:, c] == -1)
+        assert np.allclose(gla[:k, c], la_ref, rtol=1e-9, atol=1e-9), c
+        assert np.all(np.isnan(gla[k:, c]))
+        assert np.allclose(gth[c], th_ref, rtol=0, atol=1e-12), c
+        assert np.allclose(gB[c], B_ref, rtol=0, atol=1e-14), c
+        assert int(n_acc[c]) - (0 if n_acc_before is None else int(n_acc_before[c])) == int(acc_ref.sum()), c
+
+
+# C = 3, kmax = 4, counts {4, 1, 0}, every optional argument present.  What each n is there for (1024 threads, row i =
+# tid + q * 1024, q < NR; NR = 5 up to n = 5120, the lean NR = 10 above):
+#   1, 2          nearly every thread is beyond n, reads row n - 1 and drops it; n - 1 = 0
+#   63, 64, 65    one wave of rows, and one row into the second wave (the block sum over waves with empty partners)
+#   1023..1025    one row short of a full first pass, exactly full, one row into q = 1
+#   5119..5121    the last n of the register-resident instantiation (one short, exactly 5 rows per thread) and the first
+#                 n of the lean one
+#   10239, 10240  the lean instantiation one row short and exactly full: the largest n the entry point accepts
+ROW_COUNTS = (1, 2, 63, 64, 65, 1023, 1024, 1025, 5119, 5120, 5121, 10239, 10240)
+KNOT_CASES = {f"rows{n}": dict(n=n, kmax=4, counts=(4, 1, 0), seed=100 + n) for n in ROW_COUNTS}
+# every optional argument absent (no weights, offsets or tau), in both instantiations
+KNOT_CASES["bare700"] = dict(n=700, kmax=4, counts=(4, 1, 0), seed=7, weights=False, shared=False, offset=False, with_tau=False)
+KNOT_CASES["bare6000"] = dict(n=6000, kmax=4, counts=(4, 1, 0), seed=8, weights=False, shared=False, offset=False, with_tau=False)
+# scale == 1.0 skips the two divisions by the scale (kn_basis); the same other inputs at 0.8
+KNOT_CASES["unit"] = dict(n=1500, kmax=5, counts=(5, 2, 3), seed=21, scale=1.0)
+KNOT_CASES["scaled"] = dict(n=1500, kmax=5, counts=(5, 2, 3), seed=21, scale=0.8)
+# kmax = 1: one step, one proposal per chain, the `live` list of one entry; kmax = 64: 5 * 64 doubles of LDS per chain and
+# chains that finish at different times; count = kmax + 2 must run as count = kmax
+KNOT_CASES["kmax1"] = dict(n=300, kmax=1, counts=(1, 0, 1), seed=31)
+KNOT_CASES["kmax64"] = dict(n=300, kmax=64, counts=(64, 1, 0, 33), seed=32)
+KNOT_CASES["overfull"] = dict(n=300, kmax=4, counts=(6, 2, 4), seed=33)
+
+
+@pytest.mark.parametrize("name", list(KNOT_CASES))
+def test_knot_loop_edges_against_numpy(name):
+    """omc_knot_loop against knot_loop_numpy at the row counts, scales and column counts listed at KNOT_CASES."""
+    from openmcmc_amd.engine import Engine
+
+    inp = knot_inputs(**KNOT_CASES[name])
+    ref = knot_reference(inp)
+    eng = Engine(inp["C"], seed=2)
+    got = knot_device(eng, inp)
+    knot_compare(inp, got, ref)
+    # a chain with count > kmax proposes kmax knots, not count
+    assert np.array_equal(got[5], inp["live"].astype(np.int64))
+    eng.close()
+
+
+def test_knot_loop_refuses_more_rows_than_its_registers_hold():
+    """n = 10241 needs an eleventh row per thread: the entry point answers OMC_INVALID_ARG (a ValueError here) before any
+    launch, and leaves the knots and the basis as they were."""
+    import torch
+
+    from openmcmc_amd.engine import Engine
+
+    inp = knot_inputs(n=10241, kmax=4, counts=(4, 1, 0), seed=1)
+    eng = Engine(3, seed=2)
+    d = eng.to_device
+    dB, dth = d(inp["B"]), d(inp["theta"])
+    n_acc = torch.zeros(3, dtype=torch.int64, device=eng.device)
+    with pytest.raises(ValueError):
+        eng.knot_loop(d(inp["X"]), inp["scale"], d(inp["y"]), dB, d(inp["beta"]), dth, d(inp["count"]), inp["step"], inp["lower"],
+                      inp["upper"], inject_z=d(inp["uz"]), inject_u=d(inp["uu"]), accept_count=n_acc, proposal_count=n_acc)
+    eng.check_status()
+    assert np.array_equal(dB.cpu().numpy(), inp["B"]) and np.array_equal(dth.cpu().numpy(), inp["theta"])
+    assert not n_acc.cpu().numpy().any()
+    eng.close()
+
+
+def test_plan_falls_back_above_the_kernels_row_limit():
+    """A basis of 10241 rows keeps RandomWalkLoop on the launch-by-launch route: no plan, no error; 10240 rows still plan."""
+    from openmcmc_amd.engine import Engine
+    from openmcmc_amd.mcmc import MCMC
+
+    for n, planned in ((10240, True), (10241, False)):
+        y, X, P, k0, th0, be0 = small_problem(2, n, 3)
+        eng = Engine(2, seed=1)
+        mdl, state, samplers = build(y, X, P, 3, eng, th0, be0, k0.astype(float))
+        state = MCMC(state, samplers, model=mdl, n_burn=0, n_iter=1, n_chains=2, engine=eng).state
+        assert (samplers[4]._knot_plan(state) is not None) == planned, n
+        eng.close()
+
+
+def test_knot_loop_zero_coefficient_on_a_live_knot():
+    """beta[c, j] == 0.0 for a live j: column j is left out of the kernel's `live` list (the columns of the first residual),
+    but its step still runs.  The move does not change the fitted values, so log_alpha is lq_rev - lq_fwd; the accept
+    uniform of that step is tiny, so the move is accepted and theta[c, j] and column j of B must be rewritten; the steps
+    after it must agree as well."""
+    from openmcmc_amd.engine import Engine
+
+    inp = knot_inputs(n=1300, kmax=5, counts=(5, 3, 5), seed=41)
+    j = 2
+    inp["beta"][0, j] = 0.0
+    inp["beta"][1, 1] = 0.0
+    inp["uu"][j, 0] = 1e-30
+    ref = knot_reference(inp)
+    mu = inp["theta"][0, j]
+    step, lo, hi = inp["step"], inp["lower"], inp["upper"]
+    z = stats.truncnorm.ppf(inp["uz"][j, 0], (lo - mu) / step, (hi - mu) / step, loc=mu, scale=step)
+    lq_f = stats.truncnorm.logpdf(z, (lo - mu) / step, (hi - mu) / step, loc=mu, scale=step)
+    lq_r = stats.truncnorm.logpdf(mu, (lo - z) / step, (hi - z) / step, loc=z, scale=step)
+    # the reference's two quadratic forms are the same bits: what is left is the rounding of (q + lq_r) - (q + lq_f)
+    half_q = 0.5 * inp["tau"][0] * np.sum(inp["w"] * (inp["y"] - inp["B"][0].T @ inp["beta"][0] - inp["offset"][0] - inp["shared"]) ** 2)
+    assert abs(ref[0][3][j] - (lq_r - lq_f)) <= 8 * np.spacing(half_q)
+    assert ref[0][2][j] == 1
+    eng = Engine(inp["C"], seed=2)
+    got = knot_device(eng, inp)
+    knot_compare(inp, got, ref)
+    assert abs(got[3][j, 0] - (lq_r - lq_f)) <= 1e-9
+    assert abs(got[0][0, j] - z) <= 1e-12 and got[0][0, j] != mu
+    assert np.allclose(got[1][0, j], gauss_column(inp["X"], z, inp["scale"]), rtol=0, atol=1e-14)
+    eng.close()
+
+
+def test_knot_loop_knots_on_the_ends_of_the_domain():
+    """Knots exactly at `lower` and `upper`, a step three times as wide as the domain (the truncated normal is then nearly
+    the uniform law on the domain) and proposal uniforms 2**-53 and 1 - 2**-53, the ends of the generator's range.
+    The accept uniforms are tiny, so every proposal is accepted and stands in theta: inside [lower, upper], and equal to
+    the reference's.
+
+    A knot in the INTERIOR with the uniform 2**-53 is run too, but held to the domain only: SciPy's own quantile is some
+    2e-14 off at this width (it answers -2.1e-14 for the median of a window symmetric about 0), which for that proposal is
+    -5.000000000000018, outside the domain, with a forward density of -inf -- no reference for a kernel that stays inside.
+    Every proposal that IS compared is asserted to lie in the domain on the reference's side first."""
+    from openmcmc_amd.engine import Engine
+
+    inp = knot_inputs(n=900, kmax=4, counts=(4, 4, 2), seed=51, step=30.0)
+    lo, hi = inp["lower"], inp["upper"]
+    inp["theta"][0, :4] = [lo, hi, lo, hi]
+    inp["theta"][1, :4] = [hi, lo, 0.0, hi]
+    inp["theta"][2, :2] = [lo, hi]
+    fill_basis(inp)
+    tiny, top = 2.0**-53, 1.0 - 2.0**-53
+    inp["uz"][:, 0] = [tiny, tiny, top, top]
+    inp["uz"][:, 1] = [top, top, top, 0.5]
+    inp["uz"][:, 2] = [tiny, top, 0.5, 0.5]
+    inp["uu"][:] = 1e-300
+    inp["tau"][:] = 1e-3  # a weak likelihood: log_alpha stays far above log(1e-300)
+    ref = knot_reference(inp)
+    for c in range(3):  # conditions on the inputs: every move is accepted, and the reference's proposals are in the domain
+        k = inp["live"][c]
+        assert ref[c][2].all() and np.all((ref[c][0][:k] >= lo) & (ref[c][0][:k] <= hi))
+    eng = Engine(inp["C"], seed=2)
+    got = knot_device(eng, inp)
+    knot_compare(inp, got, ref)
+    inp["uz"][2, 1] = tiny  # the interior knot 0.0 of chain 1
+    inside = knot_device(eng, inp)
+    for g in (got, inside):
+        for c in range(3):
+            k = inp["live"][c]
+            assert np.all((g[0][c, :k] >= lo) & (g[0][c, :k] <= hi)), g[0][c]
+            assert np.isfinite(g[3][:k, c]).all() and g[2][:k, c].all()
+    assert abs(inside[0][1, 2] - lo) <= 1e-12
+    eng.close()
+
+
+def test_knot_loop_counters_add_up_and_outputs_are_optional():
+    """Two calls in a row add to accept_count and proposal_count (the second starts from the state the first left); a call
+    without accept_out and log_alpha_out leaves the same theta and B, bit for bit; the same call twice gives the same bits."""
+    import torch
+
+    from openmcmc_amd.engine import Engine
+
+    inp = knot_inputs(n=1100, kmax=4, counts=(4, 1, 3), seed=61)
+    ref1 = knot_reference(inp)
+    th1, B1 = np.stack([r[0] for r in ref1]), np.stack([r[1] for r in ref1])
+    ref2 = knot_reference(inp, theta=th1, B=B1)
+    eng = Engine(inp["C"], seed=2)
+    counters = (torch.full((3,), 5, dtype=torch.int64, device=eng.device), torch.full((3,), 9, dtype=torch.int64, device=eng.device))
+    got1 = knot_device(eng, inp, counters=counters)
+    knot_compare(inp, got1, ref1, n_acc_before=[5, 5, 5])
+    assert np.array_equal(got1[5], 9 + inp["live"])
+    got2 = knot_device(eng, inp, theta=got1[0], B=got1[1], counters=counters)
+    knot_compare(inp, got2, ref2, n_acc_before=got1[4])
+    assert np.array_equal(got2[5], 9 + 2 * inp["live"])
+    assert np.array_equal(got2[4], 5 + np.array([r1[2].sum() + r2[2].sum() for r1, r2 in zip(ref1, ref2)]))
+    assert got2[4].sum() > 15  # ... and some moves are accepted
+    quiet = knot_device(eng, inp, outputs=False)
+    again = knot_device(eng, inp)
+    for a in (quiet, again):
+        assert np.array_equal(a[0], got1[0]) and np.array_equal(a[1], got1[1])
+    assert np.array_equal(again[2], got1[2]) and np.array_equal(again[3], got1[3], equal_nan=True)
+    eng.close()
+
+
+DRAW_CASE = dict(n=800, kmax=6, counts=(6, 1, 0, 4), seed=71)
+DRAW_SEED, DRAW_INDEX, DRAW_OFFSET = 0x5EED_0000_0007, (3 << 32) | 17, (1 << 32) + 3
+
+
+def draw_case_inputs():
+    """DRAW_CASE with the uniforms the kernel draws itself: knot j of global chain g reads words 0-1 of block 2 j of g's
+    uniform stream for its proposal and words 0-1 of block 2 j + 1 for its decision."""
+    import philox_model as pm
+
+    inp = knot_inputs(**DRAW_CASE)
+    for c in range(inp["C"]):
+        x, y, _, _ = pm.rng_blocks(DRAW_SEED, DRAW_INDEX, "uniform", DRAW_OFFSET + c, np.arange(2 * inp["kmax"]))
+        u = pm.u53(x, y)
+        inp["uz"][:, c], inp["uu"][:, c] = u[0::2], u[1::2]
+    return inp
+
+
+def test_knot_loop_draws_in_the_kernel_are_the_host_model_word_for_word():
+    """inject_z = inject_u = None against the same call with the uniforms of philox_model injected: bit for bit.  The engine
+    holds global chains DRAW_OFFSET ... (above 2**32, so the high bits of the chain index are in the counter too)."""
+    from openmcmc_amd.engine import Engine
+
+    inp = draw_case_inputs()
+    ref = knot_reference(inp)
+    eng = Engine(inp["C"], seed=DRAW_SEED, chain_id_offset=DRAW_OFFSET)
+    drawn = knot_device(eng, inp, inject=False, draw_index=DRAW_INDEX)
+    injected = knot_device(eng, inp, inject=True, draw_index=DRAW_INDEX)
+    for a, b in zip(drawn, injected):
+        assert np.array_equal(a, b, equal_nan=True)
+    knot_compare(inp, drawn, ref)
+    # another draw index gives other proposals
+    other = knot_device(eng, inp, inject=False, draw_index=DRAW_INDEX + 1)
+    assert not np.array_equal(other[3], drawn[3], equal_nan=True)
+    eng.close()
+
+
 def test_plan_falls_back_when_the_model_does_not_match():
     """A trace hook, a prior narrower than the proposal's domain or a foreign callback keep the loop on the generic
     route (no error, same API)."""
