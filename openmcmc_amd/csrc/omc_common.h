@@ -99,6 +99,7 @@ struct omc_ctx {
   int mh_use_rocblas;  // 1: the products of the fused Metropolis-Hastings steps through rocBLAS DGEMM instead of omc_dgemm_small (cross-checks)
   int gram_use_rocblas;  // 1: X' diag(w) X through rocBLAS (scaled copy of X + DGEMM) instead of the own MFMA kernel (cross-checks)
   int dense_use_rocsolver;  // 1: factor dense precisions with rocSOLVER's batched potrf instead of the blocked route
+  int spectral_use_rocblas;  // 1: the products of the spectral dense draw through rocBLAS DGEMM instead of omc_dgemm_small (cross-checks)
   unsigned long long* stamps;  // diagnostic phase stamps of the segmented kernel (NULL = off)
   // diagnostic sweep clock (options "sweep_times_ptr" / "sweep_times_cap"): the workgroup-per-chain tridiagonal kernel writes
   // {s_memrealtime at entry, at exit} of every (sweep, chain) into a caller-owned ring [cap][n_chains][2] of uint64

@@ -67,6 +67,7 @@ omc_status omc_ctx_create(int32_t device, int64_t n_chains, uint64_t seed, int64
   c->debug_zero_z = 0;
   c->dense_use_rocsolver = 0;
   c->gram_use_rocblas = 0;
+  c->spectral_use_rocblas = 0;
   c->mh_use_rocblas = 0;
   c->mh_gemm_ksplit = 4;
   c->diag_algo = 0;
@@ -332,6 +333,10 @@ omc_status omc_ctx_set_option(omc_ctx* ctx, const char* name, int64_t value) {
   }
   if (!strcmp(name, "gram_use_rocblas")) {
     ctx->gram_use_rocblas = value != 0;
+    return OMC_OK;
+  }
+  if (!strcmp(name, "spectral_use_rocblas")) {
+    ctx->spectral_use_rocblas = value != 0;
     return OMC_OK;
   }
   if (!strcmp(name, "dense_use_rocsolver")) {

@@ -660,6 +660,31 @@ omc_status omc_dense_sample_canonical(omc_ctx* ctx, int64_t p, const omc_dense_t
 }
 
 // ---- spectral route of the dense conjugate draw ---------------------------------------------------------------------
+// out = in' for a p x p matrix (32 x 32 tiles through LDS): omc_dgemm_small takes its left operand untransposed
+__global__ void __launch_bounds__(256) k_transpose_sq(int64_t p, const double* __restrict__ in, double* __restrict__ out) {
+  __shared__ double tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int64_t i0 = (int64_t)blockIdx.y * 32, j0 = (int64_t)blockIdx.x * 32;
+  for (int r = ty; r < 32; r += 8)
+    if (i0 + r < p && j0 + tx < p) tile[r][tx] = in[(i0 + r) * p + j0 + tx];
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8)
+    if (j0 + r < p && i0 + tx < p) out[(j0 + r) * p + i0 + tx] = tile[tx][r];
+}
+
+// The three products of the draw (V' B, V Y, V M: p x p times the p x C block of all chains) go through omc_dgemm_small, whose
+// every output column is one accumulation over the contraction that does not depend on the number of columns or on the
+// column's place among them: a chain's draw is then the same bits in a context of any size (chains shard over GPUs).  A
+// library GEMM picks its kernel, and with it the order of summation, by the number of columns ("spectral_use_rocblas" 1
+// keeps that route for cross-checks).  The products are launched with the in-workgroup split of the contraction fixed at 4
+// (SPECTRAL_KSPLIT), not with the context's "mh_gemm_ksplit": that option tunes the Metropolis-Hastings steps and must not
+// move this draw's bits.  omc_dgemm_small has no transposed left operand, so V' is written out once per draw into the
+// workspace (p x p doubles next to the two [C][p] blocks).
+// (omc_dense_spectral_sample itself sets no upper limit on p -- only the eigensolver's entry point does -- and the own
+// kernel's indices are ints: beyond 46340 the library route.)
+#define SPECTRAL_KSPLIT 4
+static bool spectral_own_gemm(const omc_ctx* ctx, int64_t p) { return !ctx->spectral_use_rocblas && p <= 46340; }
+
 omc_status omc_dense_spectral_prepare(omc_ctx* ctx, int64_t p, const double* M, double* V_out, double* ev_out) {
   if (!ctx || p < 1 || p > 32768 || !M || !V_out || !ev_out) return OMC_INVALID_ARG;
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
@@ -693,13 +718,16 @@ omc_status omc_dense_spectral_sample(omc_ctx* ctx, int64_t p, const omc_dense_te
     if (k != k_mat && terms->mat[k]) return OMC_INVALID_ARG;  // every other term must be a scaled identity
   const int64_t C = ctx->n_chains;
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  omc_status st = omc_ensure_blas(ctx);
+  const bool own = spectral_own_gemm(ctx, p);
+  omc_status st = own ? OMC_OK : omc_ensure_blas(ctx);  // (the own products need no library handle)
   if (st != OMC_OK) return st;
-  rocblas_handle h = (rocblas_handle)ctx->blas;
-  st = omc_ensure_bytes(ctx, (void**)&ctx->dense_factor, &ctx->dense_factor_bytes, (size_t)2 * C * p * sizeof(double));
+  rocblas_handle h = own ? nullptr : (rocblas_handle)ctx->blas;
+  st = omc_ensure_bytes(ctx, (void**)&ctx->dense_factor, &ctx->dense_factor_bytes,
+                        ((size_t)2 * C * p + (own ? (size_t)p * p : 0)) * sizeof(double));
   if (st != OMC_OK) return st;
   double* W = ctx->dense_factor;       // [C][p]: V' rhs, then y
   double* Mw = W + C * p;              // [C][p]: m in the eigenbasis
+  double* Vt = Mw + C * p;             // [p][p]: V' (own products only)
   DenseTermsDev T{};
   T.n_terms = terms->n_terms;
   for (int k = 0; k < OMC_MAX_TERMS; ++k) {
@@ -713,12 +741,28 @@ omc_status omc_dense_spectral_sample(omc_ctx* ctx, int64_t p, const omc_dense_te
   hipLaunchKernelGGL(k_dense_rhs, dim3(gx(p), (unsigned)C), dim3(256), 0, ctx->stream, T, p, C, rhs_chain, ld_rhs, x_out, ld_x);
   OMC_HIP_CHECK(hipGetLastError());
   const double one = 1.0, zero = 0.0;
-  OMC_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_transpose, rocblas_operation_none, (rocblas_int)p, (rocblas_int)C, (rocblas_int)p,
-                               &one, V, (rocblas_int)p, x_out, (rocblas_int)ld_x, &zero, W, (rocblas_int)p));
+  if (own) {
+    const unsigned tg = (unsigned)((p + 31) / 32);
+    hipLaunchKernelGGL(k_transpose_sq, dim3(tg, tg), dim3(256), 0, ctx->stream, p, V, Vt);
+    OMC_HIP_CHECK(hipGetLastError());
+    st = omc_dgemm_small(ctx, (int)p, (int)C, Vt, p, x_out, ld_x, (int)p, nullptr, 0, nullptr, 0, 0, 0, nullptr, W, p, nullptr,
+                         SPECTRAL_KSPLIT);
+    if (st != OMC_OK) return st;
+  } else {
+    OMC_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_transpose, rocblas_operation_none, (rocblas_int)p, (rocblas_int)C, (rocblas_int)p,
+                                 &one, V, (rocblas_int)p, x_out, (rocblas_int)ld_x, &zero, W, (rocblas_int)p));
+  }
   hipLaunchKernelGGL(k_spectral_scale, dim3((unsigned)C), dim3(256), 0, ctx->stream, T, (int)k_mat, p, C, ev, ctx->chain_offset,
                      omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL), z_inject, ld_z, W, p, mean_out ? Mw : nullptr, p,
                      logdet_out, ctx->d_bad_chain);
   OMC_HIP_CHECK(hipGetLastError());
+  if (own) {
+    st = omc_dgemm_small(ctx, (int)p, (int)C, V, p, W, p, (int)p, nullptr, 0, nullptr, 0, 0, 0, nullptr, x_out, ld_x, nullptr,
+                         SPECTRAL_KSPLIT);
+    if (st != OMC_OK || !mean_out) return st;
+    return omc_dgemm_small(ctx, (int)p, (int)C, V, p, Mw, p, (int)p, nullptr, 0, nullptr, 0, 0, 0, nullptr, mean_out, ld_mean, nullptr,
+                           SPECTRAL_KSPLIT);
+  }
   OMC_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_none, (rocblas_int)p, (rocblas_int)C, (rocblas_int)p, &one,
                                V, (rocblas_int)p, W, (rocblas_int)p, &zero, x_out, (rocblas_int)ld_x));
   if (mean_out)

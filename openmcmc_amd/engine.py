@@ -1001,14 +1001,37 @@ class Engine:
         """x = A^-1 b + L^-T z per chain, L = chol(A) (gmrf.py:167-198 for a dense per-chain precision of any order)."""
         torch = _torch()
         Cn, k, _ = A.shape
-        L, info = torch.linalg.cholesky_ex(A)
+        zz = self.fill_normal(k, draw_index) if z is None else z
+        out = self.empty(Cn, k)
+        # The batched factorisation and solves pick their kernels by the size of the batch (one matrix, a few, many), and with
+        # them the order of their sums.  Every call therefore sees the same batch, _CHAIN_BATCH matrices, the last block of
+        # chains filled up with copies of its last chain: a chain's draw is the same bits in a context of any size -- on the
+        # assumption that a batched kernel treats a matrix alike wherever it stands in a batch of that size (held by
+        # tests/test_draw_streams_gpu.py at 1, 64, 65 and 130 chains, not promised by the library).  The factorisations'
+        # status is read once, after the last batch.  chain_spd_ops below stays as it was: its results may differ in the last
+        # bits with the batch.  Against the one batched call this replaces (MI355X, per draw): 2.1-2.7 against 1.05 ms at 257
+        # chains of order 70, 7.4-7.7 against 3.6 ms at 1024 of order 100, 1.4 against 1.4 at 64 of order 200, 0.46 against 0.50 at 5.
+        B = self._CHAIN_BATCH
+        infos = []
+        for lo in range(0, Cn, B):
+            n = min(B, Cn - lo)
+            if n == B:
+                Ab, bb, zb = A[lo:lo + B], b[lo:lo + B], zz[lo:lo + B]
+            else:
+                idx = torch.arange(lo, lo + B, device=self.device).clamp_(max=Cn - 1)
+                Ab, bb, zb = A[idx], b[idx], zz[idx]
+            L, info = torch.linalg.cholesky_ex(Ab)
+            infos.append(info[:n])
+            w = torch.linalg.solve_triangular(L, bb.unsqueeze(2), upper=False)
+            if mean_out is not None:
+                mean_out[lo:lo + n] = torch.linalg.solve_triangular(L.transpose(1, 2), w, upper=True).squeeze(2)[:n]
+            out[lo:lo + n] = torch.linalg.solve_triangular(L.transpose(1, 2), w + zb.unsqueeze(2), upper=True).squeeze(2)[:n]
+        info = torch.cat(infos)
         if bool((info != 0).any().item()):
             raise np.linalg.LinAlgError(f"Matrix is not positive definite (chain {int(torch.nonzero(info)[0].item())})")
-        w = torch.linalg.solve_triangular(L, b.unsqueeze(2), upper=False)
-        if mean_out is not None:
-            mean_out.copy_(torch.linalg.solve_triangular(L.transpose(1, 2), w, upper=True).squeeze(2))
-        zz = self.fill_normal(k, draw_index) if z is None else z
-        return torch.linalg.solve_triangular(L.transpose(1, 2), w + zz.unsqueeze(2), upper=True).squeeze(2).contiguous()
+        return out
+
+    _CHAIN_BATCH = 64
 
     def rj_matched_transition(self, gram_cur, gram_prop, count, birth, del_index, coef_cur, scale, limits, lq_fwd,
                               lq_rev, inject=None, draw_index=0, sub=0):

@@ -68,6 +68,16 @@ def normals(seed, draw_index, global_chain, n):
     return out[:n]
 
 
+def uniforms(seed, draw_index, global_chain, n, sub=0):
+    """First n elements of the chain's 'uniform' stream as omc_elem_uniform defines them: element e is half e & 1 of
+    block sub + (e >> 1), through u53.  Integer arithmetic and one exact scaling: the device's values bit for bit."""
+    nb = (n + 1) // 2
+    x, y, z, w = rng_blocks(seed, draw_index, "uniform", global_chain, (sub + np.arange(nb, dtype=np.uint64)) & MASK)
+    out = np.empty(2 * nb)
+    out[0::2], out[1::2] = u53(x, y), u53(z, w)
+    return out[:n]
+
+
 # ---- counters and the gamma stream (omc_common.h: field map, omc_standard_gamma) ----------------------------------
 GAMMA_BLOCKS = 513      # blocks one Gamma(a) draw may read: 0 (the a < 1 boost) and 1 + 2j, 2 + 2j for 256 attempts
 COMPONENT_SHIFT = 24    # mixture component k of k_mixture_normal_gamma reads blocks from (k + 1) << COMPONENT_SHIFT

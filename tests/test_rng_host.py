@@ -28,6 +28,37 @@ def test_philox4x32_10_known_answers(ctr, key, expect):
     assert tuple(int(v[0]) for v in out) == expect
 
 
+@pytest.mark.parametrize("n", [1, 2, 7, 64, 131])
+@pytest.mark.parametrize("sub", [0, 3, 1 << 24])
+@pytest.mark.parametrize("chain", [0, 5, 2**32 - 1, 2**32 + 62, (0xAB << 32) | 9])
+def test_uniforms_helper_is_elem_uniform_written_out(n, sub, chain):
+    """philox_model.uniforms against omc_elem_uniform restated element by element on rng_blocks and u53: odd and even n,
+    sub != 0, chain ids on both sides of 2^32 (the high byte of the chain id lives in c3 bits 16-23)."""
+    seed, draw = 0x0123_4567_89AB_CDEF, (5 << 32) | 7
+    got = pm.uniforms(seed, draw, chain, n, sub=sub)
+    assert got.shape == (n,) and got.dtype == np.float64
+    for e in range(n):
+        x, y, z, w = pm.rng_blocks(seed, draw, "uniform", chain, [sub + (e >> 1)])
+        lo, hi = (z, w) if e & 1 else (x, y)
+        v = int(lo[0]) ^ (int(hi[0]) << 21)       # u53 in Python integers: (v + 1) 2^-53, exact in float64
+        assert got[e] == (v + 1) / 2.0**53
+        assert got[e] == pm.u53(lo, hi)[0]
+    assert np.all(got > 0.0) and np.all(got <= 1.0)
+
+
+def test_uniforms_helper_reads_the_counter_fields():
+    """A change of any one field of the counter changes the stream; a prefix of a longer request is the shorter one."""
+    base = dict(seed=11, draw_index=(5 << 32) | 7, global_chain=2**32 + 1, n=9)
+    ref = pm.uniforms(**base)
+    assert np.array_equal(pm.uniforms(**{**base, "n": 4}), ref[:4])
+    assert np.array_equal(pm.uniforms(**base, sub=2)[:5], ref[4:])          # sub shifts by whole blocks
+    for change in (dict(seed=12), dict(draw_index=7), dict(draw_index=(5 << 32) | 8), dict(global_chain=1),
+                   dict(global_chain=2**32 + 2)):
+        assert not np.any(pm.uniforms(**{**base, **change}) == ref)
+    x, y, _, _ = pm.rng_blocks(11, (5 << 32) | 7, "normal", 2**32 + 1, [0])
+    assert pm.u53(x, y)[0] != ref[0]                                         # the purpose field
+
+
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
