@@ -87,49 +87,90 @@ omc_status omc_ctx_destroy(omc_ctx* ctx);
  * (returns OMC_NOT_POSDEF; the latch is cleared).                                            */
 omc_status omc_ctx_status(omc_ctx* ctx, int64_t* first_bad_chain);
 omc_status omc_ctx_synchronize(omc_ctx* ctx);
-/* Tuning knobs, by name: "tridiag_algo" (0 auto, 1 serial lane-per-chain, 2 segmented),
- * "tridiag_seg" (nodes per lane: 0 auto, 8, 10, 16, 20, 32), "tridiag_generic" (1: never use the
- * instantiation specialised for the two-term smoother structure; for cross-checks), "tridiag_quad_skip" (bit k set: the generic
- * workgroup-per-chain draw skips term k's fused quadratic form -- a hierarchical sweep knows which of them a later block will
- * invalidate --, that quad_out entry is then meaningless), "tridiag_newton_max" (0..64,
- * default 4: Newton corrections of the segment joins before the sequential fallback takes over; 0 forces it),
- * "tridiag_perturb_ppb" (tests: relative error, in 1e-9, put on the segments' start pivots so that the join test must
- * reject them), "run_sweeps_per_launch" (1..32, default 32: sweeps omc_gmrf_run issues per launch), "run_reenter" (0..2, default 2:
- * within such a launch a chain's workgroup restarts itself for the next sweep instead of one workgroup per sweep and chain;
- * 2: without a barrier in front of the restart, the scales handed from sweep to sweep through LDS; by default the
- * restarting form is taken when the chains fill the CUs in whole rounds and the (sweep, chain) grid otherwise, an
- * explicit setting holds for every chain count),
- * "diag_algo" (0 auto; 1 the short-series form of omc_store_rhat_ess, M <= 64; 2 its blocks of lags),
- * "hist_algo" (0 auto; 1 omc_store_histogram always finds the bin by bisection, also with evenly spaced edges: same counts),
- * "reduce_algo" (0 auto; 1 omc_store_reduce takes the short-row form, rows staged in LDS, where a row fits; 2 always a wave per row:
- * same results, SUM to rounding),
- * "hist2d_algo" (0 auto; bit 0: omc_store_histogram2d always takes the direct form, atomic adds to the output without counters in
- * LDS; bit 1: it always finds the bins by bisection; same counts either way),
- * "rank_tile" (0 = 8192, or a power of two 64 .. 8192: keys of an LDS tile of the sort behind omc_store_ranks; same results bit for
- * bit), "rank_chunk" (0 auto, else the elements omc_store_ranks / omc_store_rank_diagnostics / omc_store_hdi / omc_store_autocorr work on at a time),
- * "autocorr_slice" (0 = 2048, else the rows of a time slice of omc_store_autocorr, at least 1: same results to rounding),
- * "band_algo" (0 auto; 1 narrow bands one lane per chain in ONE piece; 2 one workgroup per chain, a column per step; 3 one
- * workgroup per chain in blocks of 16 columns, the next block factorised ahead, the window update on the matrix cores -- auto
- * takes it from w = 9, and from w = 4 on up to 3072 chains, where a lane per chain leaves the SIMDs to lone waves), "band_seg_overlap"
- * (8..65536, default 192: columns of warm-up before a segment of the segmented narrow-band route), "band_seg_count" (0, 2..128;
- * default 0: the number of segments of that route is chosen for the device's SIMDs; same results to rounding),
- * "band_blocked_threads" (0, 4, 8, 16 or 512; default 0: the blocked band kernel picks its form by what fits a CU -- four waves per
- * chain for bands narrower than 16, 128-register forms with several workgroups to a CU when there are more chains than CUs;
- * 512 keeps eight waves and one workgroup per CU, 4 / 16 / 8 force the 128-register forms: same results to rounding),
- * "dense_overlap" (0/1, default 1: the blocked dense factorisation runs the two halves of the chains on two streams,
- * forked from and joined into the context's stream by events; bit-identical results), "dense_use_rocsolver" (1: rocSOLVER's
- * potrf instead of the blocked route; cross-checks), "dense_blocked_min" (default 144: smallest order that takes the blocked
- * factorisation; rocSOLVER's small kernels below), "dense_panel_old" (1: the blocked factorisation's panel as ONE kernel per
- * block column, as in rounds 1-3, instead of the register-resident diagonal factor + matrix-core row update; same factor bit for
- * bit, cross-checks and A/B timing).
- * Diagnostics of omc_gmrf_run: "sweep_times_cap" then "sweep_times_ptr" = capacity (in sweeps, >= 64) and device address
- * of a caller-owned ring [cap][C][2] of uint64: wave 0 of the workgroup of every (sweep, chain) leaves the device's
- * constant-rate counter (s_memrealtime; rate: counter "wall_clock_khz") at its entry and at its exit in record
- * (position + sweep) mod cap; the position restarts at 0 when either option is set and advances by the sweeps of every
- * launch (counter "sweep_times_pos"); 0 = off (the default).  One 16-byte store per workgroup and sweep.
- * "run_event_begin" / "run_event_end" = a caller-owned hipEvent_t (as an integer; 0 = none, the default): omc_gmrf_run records
- * it on the context's stream in front of its first / behind its last launch (several-sweeps-per-launch route).
- * Unknown name -> OMC_INVALID_ARG.                                                            */
+/* Options, by name.  Every option is listed here with the values it accepts and its default; a value outside them and an
+ * unknown name return OMC_INVALID_ARG and change nothing.  (One table in the library holds the names and ranges:
+ * openmcmc_amd/csrc/omc_options.h.)
+ * Tridiagonal draw:
+ *   "tridiag_algo"          0..2, default 0: 0 auto, 1 serial lane-per-chain, 2 segmented.
+ *   "tridiag_seg"           0, 8, 10, 16, 20 or 32, default 0: nodes per lane of the segmented kernel, 0 auto.
+ *   "tridiag_generic"       any value, kept as value != 0, default 0: 1 = never use the instantiation specialised for the two-term
+ *                           smoother structure (cross-checks).
+ *   "tridiag_quad_skip"     0..15, default 0: bit k set = the generic workgroup-per-chain draw skips term k's fused quadratic form
+ *                           (a hierarchical sweep knows which of them a later block will invalidate); that quad_out entry is then
+ *                           meaningless.
+ *   "tridiag_newton_max"    0..64, default 4: Newton corrections of the segment joins before the sequential fallback takes over;
+ *                           0 forces it.
+ *   "tridiag_perturb_ppb"   0..1 000 000 000, default 0 (tests): relative error, in 1e-9, put on the segments' start pivots so that
+ *                           the join test must reject them.
+ *   "debug_zero_z"          any value, kept as (int)value, default 0 (timing what-if only): non-zero = the fused tridiagonal sweeps
+ *                           skip the generation of their normal draws and use zeros; the results are not draws.
+ * omc_gmrf_run:
+ *   "run_sweeps_per_launch" 1..32, default 32: sweeps omc_gmrf_run issues per launch.
+ *   "run_reenter"           0..2, default 2: within such a launch a chain's workgroup restarts itself for the next sweep instead of
+ *                           one workgroup per sweep and chain; 2: without a barrier in front of the restart, the scales handed from
+ *                           sweep to sweep through LDS.  By default the restarting form is taken when the chains fill the CUs in
+ *                           whole rounds and the (sweep, chain) grid otherwise; an explicit setting holds for every chain count.
+ *   "run_block_sweeps"      0..32, default 0: sweeps a self-restarting workgroup walks before a fresh workgroup takes over; 0 = all
+ *                           sweeps of the launch.
+ *   "run_event_begin", "run_event_end"   any value, default 0: a caller-owned hipEvent_t (as an integer; 0 = none) that
+ *                           omc_gmrf_run records on the context's stream in front of its first / behind its last launch
+ *                           (several-sweeps-per-launch route).
+ *   "sweep_times_cap", then "sweep_times_ptr"   the sweep clock: capacity (in sweeps; 0 or >= 64, default 0) and device address
+ *                           (any value, default 0 = off; a non-zero address needs a capacity >= 64) of a caller-owned ring
+ *                           [cap][C][2] of uint64: wave 0 of the workgroup of every (sweep, chain) leaves the device's
+ *                           constant-rate counter (s_memrealtime; rate: counter "wall_clock_khz") at its entry and at its exit in
+ *                           record (position + sweep) mod cap.  The position restarts at 0 when either option is set and advances
+ *                           by the sweeps of every launch (counter "sweep_times_pos"); a change of the capacity switches the clock
+ *                           off until a pointer is given for the new one.  One 16-byte store per workgroup and sweep.
+ *   "stamps_ptr"            any value, default 0 = off (diagnostic): device address of a caller-owned buffer [C][16][16] of uint64
+ *                           for the phase stamps of the segmented tridiagonal kernel, and in the library built with
+ *                           OMC_KERNEL_STAMPS of k_band_blocked and k_chol_panel.
+ * Store summaries:
+ *   "diag_algo"             0..2, default 0: 0 auto; 1 the short-series form of omc_store_rhat_ess, M <= 64; 2 its blocks of lags.
+ *   "hist_algo"             0..1, default 0: 1 = omc_store_histogram always finds the bin by bisection, also with evenly spaced
+ *                           edges: same counts.
+ *   "reduce_algo"           0..2, default 0: 0 auto; 1 omc_store_reduce takes the short-row form, rows staged in LDS, where a row
+ *                           fits; 2 always a wave per row: same results, SUM to rounding.
+ *   "hist2d_algo"           0..3, default 0: bit 0 = omc_store_histogram2d always takes the direct form, atomic adds to the output
+ *                           without counters in LDS; bit 1 = it always finds the bins by bisection; same counts either way.
+ *   "rank_tile"             0 or a power of two 64..8192, default 0 = 8192: keys of an LDS tile of the sort behind
+ *                           omc_store_ranks; same results bit for bit.
+ *   "rank_chunk"            >= 0 (int64), default 0 = auto: the elements omc_store_ranks / omc_store_rank_diagnostics /
+ *                           omc_store_hdi / omc_store_autocorr work on at a time.
+ *   "autocorr_slice"        >= 0 (int64), default 0 = 2048: the rows of a time slice of omc_store_autocorr; same results to
+ *                           rounding.
+ * Band route:
+ *   "band_algo"             0..3, default 0: 0 auto; 1 narrow bands one lane per chain in ONE piece; 2 one workgroup per chain, a
+ *                           column per step; 3 one workgroup per chain in blocks of 16 columns, the next block factorised ahead, the
+ *                           window update on the matrix cores -- auto takes it from w = 9, and from w = 4 on up to 3072 chains,
+ *                           where a lane per chain leaves the SIMDs to lone waves.
+ *   "band_seg_overlap"      8..65536, default 192: columns of warm-up before a segment of the segmented narrow-band route.
+ *   "band_seg_count"        0 or 2..128, default 0: the number of segments of that route, 0 = chosen for the device's SIMDs; same
+ *                           results to rounding.
+ *   "band_blocked_threads"  0, 4, 8, 16 or 512, default 0: the blocked band kernel picks its form by what fits a CU -- four waves
+ *                           per chain for bands narrower than 16, 128-register forms with several workgroups to a CU when there are
+ *                           more chains than CUs; 512 keeps eight waves and one workgroup per CU, 4 / 16 / 8 force the
+ *                           128-register forms: same results to rounding.
+ * Dense route and design-matrix helpers:
+ *   "dense_overlap"         0..1, default 1: the blocked dense factorisation runs the two halves of the chains on two streams,
+ *                           forked from and joined into the context's stream by events; bit-identical results.
+ *   "dense_use_rocsolver"   any value, kept as value != 0, default 0: 1 = rocSOLVER's potrf instead of the blocked route
+ *                           (cross-checks).
+ *   "dense_blocked_min"     1..32768, default 144: smallest order that takes the blocked factorisation; rocSOLVER's small kernels
+ *                           below.
+ *   "dense_panel_old"       0..1, default 0: 1 = the blocked factorisation's panel as ONE kernel per block column, as in rounds
+ *                           1-3, instead of the register-resident diagonal factor + matrix-core row update; same factor bit for
+ *                           bit (cross-checks and A/B timing).
+ *   "spectral_use_rocblas"  any value, kept as value != 0, default 0: 1 = the products of omc_dense_spectral_sample through
+ *                           rocBLAS DGEMM instead of the library's own fp64 MFMA GEMM (cross-checks; the own products give a chain
+ *                           the same bits in a context of any size).
+ *   "gram_use_rocblas"      any value, kept as value != 0, default 0: 1 = omc_gram through rocBLAS (a scaled copy of X and a
+ *                           DGEMM) instead of the library's own MFMA kernel (cross-checks).
+ * Metropolis-Hastings steps:
+ *   "mh_gemm_ksplit"        1, 2 or 4, default 4: groups of four waves per workgroup that cut the contraction of the steps' own
+ *                           small-state GEMM; same results to rounding.
+ *   "mh_use_rocblas"        any value, kept as value != 0, default 0: 1 = the products of the fused steps through rocBLAS DGEMM
+ *                           instead of the own GEMM (cross-checks).                                                        */
 omc_status omc_ctx_set_option(omc_ctx* ctx, const char* name, int64_t value);
 /* Diagnostic counters, by name (synchronises): "tridiag_join_fallbacks" = chain-updates of the segmented
  * tridiagonal kernel whose pivot joins did not meet the Newton tolerance within its iteration limit and were

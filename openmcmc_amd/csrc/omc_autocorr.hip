@@ -217,10 +217,9 @@ extern "C" omc_status omc_store_autocorr(omc_ctx* ctx, int64_t n_iter, int64_t s
   if ((W_max + 31) / 32 > 0x7fffffffLL) return ac_invalid("omc_store_autocorr: more columns than one launch takes");
   const size_t n_mean = mean_out ? 0 : (size_t)C * n_idx, n_part = (size_t)n_slices * n_lb * A_L * W_max, n_g = (size_t)(L + 1) * W_max,
                n_cen = idx ? (size_t)N * W_max : 0;
-  omc_status st = omc_ensure_bytes(ctx, &ctx->rank_ws, &ctx->rank_ws_bytes,
-                                   RANK_HEAD + (n_mean + n_part + n_g + n_cen) * sizeof(double) + (size_t)W_max * sizeof(int32_t));
+  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (n_mean + n_part + n_g + n_cen) * sizeof(double) + (size_t)W_max * sizeof(int32_t));
   if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws;
+  char* ws = (char*)ctx->rank_ws.p;
   double* mean = mean_out ? mean_out : (double*)(ws + RANK_HEAD);
   double* part = (double*)(ws + RANK_HEAD) + n_mean;
   double* g = part + n_part;

@@ -16,8 +16,6 @@
 
 #include "omc_band_common.h"
 
-omc_status omc_ensure_bytes(omc_ctx* ctx, void** buf, size_t* have, size_t need);  // omc_dense.hip
-
 #define BAND_WMAX 128
 
 // k_band_sample's two LDS images at bandwidth w, offsets in doubles: the kernel's pointers and the host's size from one place.
@@ -1282,8 +1280,7 @@ omc_status omc_band_sample_canonical(omc_ctx* ctx, int64_t n, int64_t w, const o
   // + flags (2 per group) and the block counters of the four launches that compose (ints)
   const size_t seg_doubles = segmented ? scr_doubles + (size_t)groups + 2 * (size_t)groups * nblk + 2 : 0;
   const size_t rt_doubles = (lane_fits && rhs_chain) ? (size_t)n * groups * 64 : 0;  // the per-chain right-hand side, transposed
-  omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->workspace, &ctx->workspace_bytes,
-                                   (base_doubles + seg_doubles + rt_doubles) * sizeof(double));
+  omc_status st = omc_ensure(ctx, ctx->workspace, (base_doubles + seg_doubles + rt_doubles) * sizeof(double));
   if (st != OMC_OK) return st;
   if (rt_doubles) {
     double* rt = ctx->workspace + base_doubles + seg_doubles;

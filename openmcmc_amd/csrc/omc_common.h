@@ -5,130 +5,8 @@
 
 #include "omcmc_hip.h"
 
-#define OMC_LAUNCH_LOG_MAX 64
-#define OMC_SWEEP_RING_MIN 64  // >= 2 * OMC_RUN_MAX: a launch never laps its own records
-struct omc_ctx {
-  int device;
-  int dev_cus;  // compute units of the device, asked of the driver once (omc_ctx_create; 256 if it does not say)
-  int64_t n_chains;
-  uint64_t seed;
-  int64_t chain_offset;
-  hipStream_t stream;
-  bool own_stream;
-  long long* d_bad_chain;  // device word: min local chain index with a non-positive pivot, or LLONG_MAX
-  unsigned long long* d_fallbacks;  // device word behind d_bad_chain: chain-updates that took the sequential join fallback
-                                    // (d_fallbacks + 1: hand-overs of a several-sweeps launch that never arrived; + 2: groups of the
-                                    //  segmented band route handed to the one-piece kernel; + 3: groups that needed its second attempt)
-  void* d_gamma_tab;                // generic tridiagonal instantiation: device image of a launch's Normal-Gamma blocks and streams
-  unsigned long long* d_handoff;    // omc_gmrf_run: [n_chains][16] hand-over lines, allocated on first use
-  uint32_t run_epoch;               // tag counter of the hand-over lines
-  int run_sweeps_per_launch;        // omc_gmrf_run: sweeps per launch (1 = one launch per sweep)
-  int run_reenter;                  // omc_gmrf_run: 1, 2 = a chain's workgroup restarts itself for the next sweep of the launch
-  int run_block_sweeps;             // omc_gmrf_run: sweeps a self-restarting workgroup walks before a fresh one takes over (0: the whole launch)
-  int run_reenter_force;            // 1: take that form whatever the chain count (tests); 0: only when the chains fill the CUs in whole rounds
-  hipEvent_t run_ev_begin, run_ev_end;  // options "run_event_begin" / "run_event_end": caller-owned events omc_gmrf_run records around its launches
-  double* long_band; size_t long_band_bytes;  // chains beyond one workgroup: the terms in band storage (omc_tridiag.hip, long_chain_draw)
-  double* long_quad; size_t long_quad_bytes;  // ... and the sweep's quadratic forms [term][chain]
-  double* workspace;       // scratch for the serial kernel (l vectors), grown on demand
-  size_t workspace_bytes;
-  // scratch of a store summary that is consumed before the call returns or the next summary starts: the word(s) of the index and
-  // edge checks (omc_store_shared.hip, omc_hist.hip), partial column moments (omc_store_shared.hip: omc_store_moments and
-  // omc_store_cov), radix histograms (omc_store.hip), partial minima / maxima (omc_hist.hip), lag sums and Geyer state (omc_diag.hip)
-  void* store_ws; size_t store_ws_bytes;
-  double* cov_ws; size_t cov_ws_bytes;  // omc_cov.hip: means, variances and partial tiles of omc_store_cov
-  void* rank_ws; size_t rank_ws_bytes;  // omc_rank.hip, omc_hdi.hip: keys, series and per-element words of a chunk (its own: it calls omc_store_rhat_ess, which uses store_ws); omc_autocorr.hip: partial lag sums and centred draws of a chunk (omc_col_moments uses store_ws)
-  // dense path (omc_dense.hip): rocBLAS handle and workspaces, created on first use
-  void* blas;
-  // blocked dense factorisation: second half of the chains on a side stream (forked from / joined into `stream` by events),
-  // so that one half's panel kernel (one workgroup per chain, latency-bound) runs under the other half's update GEMM
-  void* blas_aux;
-  hipStream_t aux_stream;
-  hipEvent_t ev_fork, ev_join;
-  int dense_blocked_min;  // option "dense_blocked_min": smallest order that takes the blocked factorisation (rocSOLVER below)
-  int dense_overlap;  // option "dense_overlap": 1 (default) = split the chains in two halves when there are >= 64; 0 = one batch
-  double* dense_factor; size_t dense_factor_bytes;
-  double* dense_winv; size_t dense_winv_bytes;  // blocked factorisation: inverses of the current diagonal blocks [C][64][64]
-  int dense_panel_old;  // option "dense_panel_old": 1 = the one-kernel panel of rounds 1-3 (cross-checks)
-  int* dense_info; size_t dense_info_bytes;
-  double* slice_buf; size_t slice_buf_bytes;  // partial products of a sliced contraction (omc_design_predict) [S][C][n]
-  double* dense_tmp; size_t dense_tmp_bytes;
-  double* rj_tmp; size_t rj_tmp_bytes;   // omc_knot_loop: the proposals of all knots
-  double* mh_work; size_t mh_work_bytes;  // omc_mala.hip
-  // What the fused Metropolis-Hastings steps (omc_mala.hip) keep between calls, one struct per route: device buffers, grown on
-  // demand and freed with the context, and the caller's pointers they were filled for.  reset() (omc_mh_invalidate) forgets
-  // the pointers and keeps the buffers.
-  struct {  // omc_mala_step
-    double* prep; size_t prep_bytes;  // cached drift matrix and L^{-T} of the current (Q, L, step)
-    const double* Q; const double* L; double step; int64_t d;
-    void reset() { Q = nullptr; L = nullptr; step = 0.0; d = 0; }
-  } mala;
-  struct {  // omc_mala_step_white, omc_mala_run_white
-    double* prep; size_t prep_bytes; const double* L; const double* mu; int64_t d;
-    double* a; size_t a_bytes; const double* x; int64_t ld;  // a = L'(x - mu) of the state at x
-    double* traj; size_t traj_bytes;  // omc_mala_run_white: the whitened states of two blocks of steps [2][32][C][d]
-    hipEvent_t ev[4];  // ... trajectory of block b written (0, 1) / mapped back by the product on the side stream (2, 3)
-    void reset() { L = nullptr; mu = nullptr; d = 0; x = nullptr; }
-  } white;
-  struct {  // omc_rw_step_white
-    double* a; size_t a_bytes; const double* x; int64_t ld; const double* mu; double* mu_neg; size_t mu_bytes;
-    void reset() { x = nullptr; mu = nullptr; }
-  } rww;
-  struct {  // omc_rw_step, omc_rw_step_white: LQ with a zero upper triangle, then its transpose
-    double* prep; size_t prep_bytes; const double* LQ; int64_t d;
-    void reset() { LQ = nullptr; d = 0; }
-  } rw;
-  int tridiag_algo;  // 0 auto, 1 serial, 2 segmented
-  int tridiag_seg;   // 0 auto, else nodes per lane
-  int debug_zero_z;  // diagnostic: skip the draw generation (timing what-if only)
-  int tridiag_newton_max;  // Newton join corrections before the sequential fallback (default OMC_NEWTON_MAX = 4; 0 forces the fallback: tests)
-  int tridiag_quad_skip;    // bit k: the generic tridiagonal draw does not take term k's fused quadratic form (its quad_out entry is left unwritten)
-  int tridiag_perturb_ppb;  // tests only: relative error (parts per billion) put on the Moebius start values of the segment joins
-  int tridiag_generic;  // 1: never take the structure-specialised instantiation of the segmented kernel (tests)
-  int band_algo;  // 0 auto, 1 lane-per-chain in one piece (narrow bands), 2 workgroup-per-chain
-  int diag_algo;  // omc_store_rhat_ess: 0 auto, 1 short-series form (M <= 64), 2 blocks of lags
-  int hist_algo;  // omc_store_histogram: 0 auto (arithmetic guess of the bin when the edges are evenly spaced), 1 always the bisection
-  int reduce_algo;  // omc_store_reduce: 0 auto, 1 short rows staged in LDS, 2 a wave per row
-  int hist2d_algo;  // omc_store_histogram2d: bit 0 always the direct form (atomic adds to the output, no LDS counters), bit 1 always the bisection
-  int rank_tile;  // omc_rank.hip: keys of an LDS tile of the sort, a power of two 64 .. 8192 (0: 8192)
-  int64_t rank_chunk;  // omc_rank.hip: elements per chunk (0: what fits the workspace budget)
-  int64_t autocorr_slice;  // omc_autocorr.hip: rows per time slice (0: 2048)
-  int band_seg_overlap;  // segmented lane kernel: columns of warm-up before a segment (default 192)
-  int band_seg_count;    // segmented lane kernel: number of segments (0 = chosen for the SIMDs; tuning and tests)
-  int band_blocked_threads;  // blocked band kernel: 0 = form chosen by what fits a CU; 512, 4, 8, 16 force one (A/B, tests; band_blocked_choose)
-  int mh_gemm_ksplit;  // omc_dgemm_small: groups of four waves per workgroup cutting the contraction (1, 2 or 4)
-  int mh_use_rocblas;  // 1: the products of the fused Metropolis-Hastings steps through rocBLAS DGEMM instead of omc_dgemm_small (cross-checks)
-  int gram_use_rocblas;  // 1: X' diag(w) X through rocBLAS (scaled copy of X + DGEMM) instead of the own MFMA kernel (cross-checks)
-  int dense_use_rocsolver;  // 1: factor dense precisions with rocSOLVER's batched potrf instead of the blocked route
-  int spectral_use_rocblas;  // 1: the products of the spectral dense draw through rocBLAS DGEMM instead of omc_dgemm_small (cross-checks)
-  unsigned long long* stamps;  // diagnostic phase stamps of the segmented kernel (NULL = off)
-  // diagnostic sweep clock (options "sweep_times_ptr" / "sweep_times_cap"): the workgroup-per-chain tridiagonal kernel writes
-  // {s_memrealtime at entry, at exit} of every (sweep, chain) into a caller-owned ring [cap][n_chains][2] of uint64
-  unsigned long long* sweep_times;
-  int64_t sweep_times_cap, sweep_times_pos;
-  // launch log of the last omc_gmrf_run call (omc_ctx_launch_log): host clock around every kernel launch it issued
-  struct LaunchRec { double t_begin, t_end; int n_sweeps, form; int64_t ring_pos; };
-  LaunchRec launch_log[OMC_LAUNCH_LOG_MAX];
-  int launch_log_n, launch_log_total;
-};
-
 void omc_set_error(const char* what, hipError_t e);
 void omc_set_error_text(const char* text);  // any other library failure (RCCL) for omc_last_error()
-void omc_dense_release(omc_ctx* ctx);
-int omc_reentry_probe_result(omc_ctx* ctx);  // omc_tridiag.hip: 1 if the loaded kernel descriptors match what a self-restart reproduces
-// omc_gemm.hip: small-state fp64 MFMA GEMM, C = A0 B0 (+ A1 B1) (+ addv per column), column-major
-omc_status omc_dgemm_small(omc_ctx* ctx, int M, int N, const double* A0, int64_t lda0, const double* B0, int64_t ldb0, int K0,
-                           const double* A1, int64_t lda1, const double* B1, int64_t ldb1, int K1, int tri, const double* addv,
-                           double* Cout, int64_t ldc, const int* colmask = nullptr, int ksplit = 0);
-omc_status omc_ensure_bytes(omc_ctx* ctx, void** buf, size_t* have, size_t need);  // grow-on-demand workspace (omc_dense.hip)
-// omc_gemm.hip: C = A B (+ addv per column) for thousands of columns (64 x 64 tiles, one operand pair)
-omc_status omc_dgemm_wide(omc_ctx* ctx, int M, int N, const double* A, int64_t lda, const double* B, int64_t ldb, int K, int tri,
-                          const double* addv, double* Cout, int64_t ldc);
-omc_status omc_ensure_aux(omc_ctx* ctx);  // side stream + its events and BLAS handle, made on first use (omc_dense.hip)
-// omc_hist.hip: one read-back for a selection and its edges.  got[0] = 1: an index outside [0, size), a NaN edge or a decreasing pair of
-// edges; got[1] = 1: some row of edges is not evenly spaced
-omc_status omc_hist_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64_t size, const double* edges, int64_t edge_rows, int n_bins,
-                          int32_t got[2]);
-extern "C" omc_status omc_gram_mfma_launch(omc_ctx* ctx, int64_t n, int64_t p, const double* X, const double* w, double* G_out);  // omc_gram.hip  // destroys the rocBLAS handle if one was created
 
 #define OMC_HIP_CHECK(expr)                  \
   do {                                       \
@@ -138,6 +16,185 @@ extern "C" omc_status omc_gram_mfma_launch(omc_ctx* ctx, int64_t n, int64_t p, c
       return OMC_HIP_ERROR;                  \
     }                                        \
   } while (0)
+
+// A device allocation and its owner: freed when the owner goes (omc_ctx_destroy frees every buffer of the context by deleting
+// the context; nothing names them one by one).  Reads as the pointer; not copyable, so none is ever freed twice.
+template <class T>
+struct omc_buf {
+  T* p = nullptr;
+  size_t bytes = 0;  // what omc_ensure recorded (0 for the fixed-size allocations made with hipMalloc(&buf.p, ...) directly)
+  omc_buf() = default;
+  omc_buf(const omc_buf&) = delete;
+  omc_buf& operator=(const omc_buf&) = delete;
+  ~omc_buf() { if (p) (void)hipFree(p); }
+  operator T*() const { return p; }
+};
+
+#define OMC_LAUNCH_LOG_MAX 64
+#define OMC_SWEEP_RING_MIN 64  // >= 2 * OMC_RUN_MAX: a launch never laps its own records
+// Every member has its default here: `new omc_ctx()` is a complete context but for what omc_ctx_create takes from its arguments
+// and the device.  The options among them are set by name through the table of omc_options.h.
+struct omc_ctx {
+  int device = 0;
+  int dev_cus = 256;  // compute units of the device, asked of the driver once (omc_ctx_create; 256 if it does not say)
+  int64_t n_chains = 0;
+  uint64_t seed = 0;
+  int64_t chain_offset = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  omc_buf<long long> status_words;  // the eight device words of the status latch and the counters; the two pointers below point into them
+  long long* d_bad_chain = nullptr;  // device word: min local chain index with a non-positive pivot, or LLONG_MAX
+  unsigned long long* d_fallbacks = nullptr;  // device word behind d_bad_chain: chain-updates that took the sequential join fallback
+                                    // (d_fallbacks + 1: hand-overs of a several-sweeps launch that never arrived; + 2: groups of the
+                                    //  segmented band route handed to the one-piece kernel; + 3: groups that needed its second attempt)
+  omc_buf<void> d_gamma_tab;        // generic tridiagonal instantiation: device image of a launch's Normal-Gamma blocks and streams
+  omc_buf<unsigned long long> d_handoff;  // omc_gmrf_run: [n_chains][16] hand-over lines, allocated on first use
+  uint32_t run_epoch = 1;           // tag counter of the hand-over lines
+  int run_sweeps_per_launch = 32;   // omc_gmrf_run: sweeps per launch (1 = one launch per sweep)
+  int run_reenter = 2;              // omc_gmrf_run: 1, 2 = a chain's workgroup restarts itself for the next sweep of the launch
+  int run_block_sweeps = 0;         // omc_gmrf_run: sweeps a self-restarting workgroup walks before a fresh one takes over (0: the whole launch)
+  int run_reenter_force = 0;        // 1: take that form whatever the chain count (tests); 0: only when the chains fill the CUs in whole rounds
+  hipEvent_t run_ev_begin = nullptr, run_ev_end = nullptr;  // options "run_event_begin" / "run_event_end": caller-owned events omc_gmrf_run records around its launches
+  omc_buf<double> long_band;  // chains beyond one workgroup: the terms in band storage (omc_tridiag.hip, long_chain_draw)
+  omc_buf<double> long_quad;  // ... and the sweep's quadratic forms [term][chain]
+  omc_buf<double> workspace;  // scratch for the serial kernel (l vectors), grown on demand
+  // scratch of a store summary that is consumed before the call returns or the next summary starts: the word(s) of the index and
+  // edge checks (omc_store_shared.hip, omc_hist.hip), partial column moments (omc_store_shared.hip: omc_store_moments and
+  // omc_store_cov), radix histograms (omc_store.hip), partial minima / maxima (omc_hist.hip), lag sums and Geyer state (omc_diag.hip)
+  omc_buf<void> store_ws;
+  omc_buf<double> cov_ws;  // omc_cov.hip: means, variances and partial tiles of omc_store_cov
+  omc_buf<void> rank_ws;  // omc_rank.hip, omc_hdi.hip: keys, series and per-element words of a chunk (its own: it calls omc_store_rhat_ess, which uses store_ws); omc_autocorr.hip: partial lag sums and centred draws of a chunk (omc_col_moments uses store_ws)
+  // rocBLAS handle of the context's stream, created on first use (omc_ensure_blas)
+  void* blas = nullptr;
+  // blocked dense factorisation: second half of the chains on a side stream (forked from / joined into `stream` by events),
+  // so that one half's panel kernel (one workgroup per chain, latency-bound) runs under the other half's update GEMM
+  void* blas_aux = nullptr;
+  hipStream_t aux_stream = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // option "dense_blocked_min": smallest order that takes the blocked factorisation (rocSOLVER below).  144: measured crossover
+  // with rocSOLVER: even at 128, the blocked route 1.3-1.8x faster at 200
+  int dense_blocked_min = 144;
+  int dense_overlap = 1;  // option "dense_overlap": 1 (default) = split the chains in two halves when there are >= 64; 0 = one batch
+  omc_buf<double> dense_factor;
+  omc_buf<double> dense_winv;  // blocked factorisation: inverses of the current diagonal blocks [C][64][64]
+  int dense_panel_old = 0;  // option "dense_panel_old": 1 = the one-kernel panel of rounds 1-3 (cross-checks)
+  omc_buf<int> dense_info;
+  omc_buf<double> slice_buf;  // partial products of a sliced contraction (omc_design_predict) [S][C][n]
+  omc_buf<double> dense_tmp;
+  omc_buf<double> rj_tmp;   // omc_knot_loop: the proposals of all knots
+  omc_buf<double> mh_work;  // omc_mala.hip
+  // What the fused Metropolis-Hastings steps (omc_mala.hip) keep between calls, one struct per route: device buffers, grown on
+  // demand and freed with the context, and the caller's pointers they were filled for.  reset() (omc_mh_invalidate) forgets
+  // the pointers and keeps the buffers.
+  struct {  // omc_mala_step
+    omc_buf<double> prep;  // cached drift matrix and L^{-T} of the current (Q, L, step)
+    const double* Q = nullptr; const double* L = nullptr; double step = 0.0; int64_t d = 0;
+    void reset() { Q = nullptr; L = nullptr; step = 0.0; d = 0; }
+  } mala;
+  struct {  // omc_mala_step_white, omc_mala_run_white
+    omc_buf<double> prep; const double* L = nullptr; const double* mu = nullptr; int64_t d = 0;
+    omc_buf<double> a; const double* x = nullptr; int64_t ld = 0;  // a = L'(x - mu) of the state at x
+    omc_buf<double> traj;  // omc_mala_run_white: the whitened states of two blocks of steps [2][32][C][d]
+    hipEvent_t ev[4] = {};  // ... trajectory of block b written (0, 1) / mapped back by the product on the side stream (2, 3)
+    void reset() { L = nullptr; mu = nullptr; d = 0; x = nullptr; }
+  } white;
+  struct {  // omc_rw_step_white
+    omc_buf<double> a; const double* x = nullptr; int64_t ld = 0; const double* mu = nullptr; omc_buf<double> mu_neg;
+    void reset() { x = nullptr; mu = nullptr; }
+  } rww;
+  struct {  // omc_rw_step, omc_rw_step_white: LQ with a zero upper triangle, then its transpose
+    omc_buf<double> prep; const double* LQ = nullptr; int64_t d = 0;
+    void reset() { LQ = nullptr; d = 0; }
+  } rw;
+  int tridiag_algo = 0;  // 0 auto, 1 serial, 2 segmented
+  int tridiag_seg = 0;   // 0 auto, else nodes per lane
+  int debug_zero_z = 0;  // diagnostic: skip the draw generation (timing what-if only)
+  int tridiag_newton_max = 4;  // Newton join corrections before the sequential fallback (default OMC_NEWTON_MAX = 4; 0 forces the fallback: tests)
+  int tridiag_quad_skip = 0;    // bit k: the generic tridiagonal draw does not take term k's fused quadratic form (its quad_out entry is left unwritten)
+  int tridiag_perturb_ppb = 0;  // tests only: relative error (parts per billion) put on the Moebius start values of the segment joins
+  int tridiag_generic = 0;  // 1: never take the structure-specialised instantiation of the segmented kernel (tests)
+  int band_algo = 0;  // 0 auto, 1 lane-per-chain in one piece (narrow bands), 2 workgroup-per-chain
+  int diag_algo = 0;  // omc_store_rhat_ess: 0 auto, 1 short-series form (M <= 64), 2 blocks of lags
+  int hist_algo = 0;  // omc_store_histogram: 0 auto (arithmetic guess of the bin when the edges are evenly spaced), 1 always the bisection
+  int reduce_algo = 0;  // omc_store_reduce: 0 auto, 1 short rows staged in LDS, 2 a wave per row
+  int hist2d_algo = 0;  // omc_store_histogram2d: bit 0 always the direct form (atomic adds to the output, no LDS counters), bit 1 always the bisection
+  int rank_tile = 0;  // omc_rank.hip: keys of an LDS tile of the sort, a power of two 64 .. 8192 (0: 8192)
+  int64_t rank_chunk = 0;  // omc_rank.hip: elements per chunk (0: what fits the workspace budget)
+  int64_t autocorr_slice = 0;  // omc_autocorr.hip: rows per time slice (0: 2048)
+  int band_seg_overlap = 192;  // segmented lane kernel: columns of warm-up before a segment
+  int band_seg_count = 0;    // segmented lane kernel: number of segments (0 = chosen for the SIMDs; tuning and tests)
+  int band_blocked_threads = 0;  // blocked band kernel: 0 = form chosen by what fits a CU; 512, 4, 8, 16 force one (A/B, tests; band_blocked_choose)
+  int mh_gemm_ksplit = 4;  // omc_dgemm_small: groups of four waves per workgroup cutting the contraction (1, 2 or 4)
+  int mh_use_rocblas = 0;  // 1: the products of the fused Metropolis-Hastings steps through rocBLAS DGEMM instead of omc_dgemm_small (cross-checks)
+  int gram_use_rocblas = 0;  // 1: X' diag(w) X through rocBLAS (scaled copy of X + DGEMM) instead of the own MFMA kernel (cross-checks)
+  int dense_use_rocsolver = 0;  // 1: factor dense precisions with rocSOLVER's batched potrf instead of the blocked route
+  int spectral_use_rocblas = 0;  // 1: the products of the spectral dense draw through rocBLAS DGEMM instead of omc_dgemm_small (cross-checks)
+  unsigned long long* stamps = nullptr;  // diagnostic phase stamps of the segmented kernel (NULL = off)
+  // diagnostic sweep clock (options "sweep_times_ptr" / "sweep_times_cap"): the workgroup-per-chain tridiagonal kernel writes
+  // {s_memrealtime at entry, at exit} of every (sweep, chain) into a caller-owned ring [cap][n_chains][2] of uint64
+  unsigned long long* sweep_times = nullptr;
+  int64_t sweep_times_cap = 0, sweep_times_pos = 0;
+  // launch log of the last omc_gmrf_run call (omc_ctx_launch_log): host clock around every kernel launch it issued
+  struct LaunchRec { double t_begin, t_end; int n_sweeps, form; int64_t ring_pos; };
+  LaunchRec launch_log[OMC_LAUNCH_LOG_MAX] = {};
+  int launch_log_n = 0, launch_log_total = 0;
+};
+
+// Grow-on-demand workspace of the context: nothing to do when `buf` holds `need` bytes.  Else the stream is drained (work in
+// flight may still read the old block), the block freed and forgotten, and the new size recorded only once the new block
+// exists: a failed allocation leaves an empty buffer, never a freed one that still claims its size.
+template <class T>
+omc_status omc_ensure(omc_ctx* ctx, omc_buf<T>& buf, size_t need) {
+  if (buf.bytes >= need) return OMC_OK;
+  OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (buf.p) OMC_HIP_CHECK(hipFree(buf.p));
+  buf.p = nullptr;
+  buf.bytes = 0;
+  OMC_HIP_CHECK(hipMalloc((void**)&buf.p, need));
+  buf.bytes = need;
+  return OMC_OK;
+}
+
+// omc_ctx.hip: the context's rocBLAS handle / its side stream with that stream's events and handle, made on first use
+// (OMC_BLAS_CHECK and the rocBLAS headers: omc_blas.h); omc_ctx_release_blas destroys both handles, the side stream and every
+// event made for it (omc_ctx_destroy, in front of the buffers)
+omc_status omc_ensure_blas(omc_ctx* ctx);
+omc_status omc_ensure_aux(omc_ctx* ctx);
+void omc_ctx_release_blas(omc_ctx* ctx);
+int omc_reentry_probe_result(omc_ctx* ctx);  // omc_tridiag.hip: 1 if the loaded kernel descriptors match what a self-restart reproduces
+// omc_gemm.hip: small-state fp64 MFMA GEMM, C = A0 B0 (+ A1 B1) (+ addv per column), column-major
+omc_status omc_dgemm_small(omc_ctx* ctx, int M, int N, const double* A0, int64_t lda0, const double* B0, int64_t ldb0, int K0,
+                           const double* A1, int64_t lda1, const double* B1, int64_t ldb1, int K1, int tri, const double* addv,
+                           double* Cout, int64_t ldc, const int* colmask = nullptr, int ksplit = 0);
+// omc_gemm.hip: C = A B (+ addv per column) for thousands of columns (64 x 64 tiles, one operand pair)
+omc_status omc_dgemm_wide(omc_ctx* ctx, int M, int N, const double* A, int64_t lda, const double* B, int64_t ldb, int K, int tri,
+                          const double* addv, double* Cout, int64_t ldc);
+// omc_hist.hip: one read-back for a selection and its edges.  got[0] = 1: an index outside [0, size), a NaN edge or a decreasing pair of
+// edges; got[1] = 1: some row of edges is not evenly spaced
+omc_status omc_hist_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64_t size, const double* edges, int64_t edge_rows, int n_bins,
+                          int32_t got[2]);
+extern "C" omc_status omc_gram_mfma_launch(omc_ctx* ctx, int64_t n, int64_t p, const double* X, const double* w, double* G_out);  // omc_gram.hip
+
+// A copy of the caller's dense terms for a kernel to take by value: the kernels read all OMC_MAX_TERMS slots, so those beyond
+// n_terms are NULL whatever the caller left there.  keep_diag = false drops the per-chain diagonal (the spectral draw has none).
+inline omc_dense_terms omc_dense_terms_clean(const omc_dense_terms* terms, bool keep_diag) {
+  omc_dense_terms T{};
+  T.n_terms = terms->n_terms;
+  for (int k = 0; k < terms->n_terms && k < OMC_MAX_TERMS; ++k) { T.mat[k] = terms->mat[k]; T.rhs[k] = terms->rhs[k]; T.scale[k] = terms->scale[k]; }
+  T.diag_chain = keep_diag ? terms->diag_chain : nullptr;
+  return T;
+}
+// launchers of kernels that a second file uses (one definition each), on the context's stream with grid (gx, chains), 256 threads.
+// The caller chooses gx and checks hipGetLastError.  omc_dense.hip, k_dense_rhs: b[c] = sum_k s_k[c] rhs_k + rhs_chain[c];
+// omc_design.hip, k_copy_rows: dst[c][0..p) = src[c][0..p)
+void omc_launch_dense_rhs(omc_ctx* ctx, unsigned gx, const omc_dense_terms& T, int64_t p, const double* rhs_chain, int64_t ld_rhs, double* b,
+                          int64_t ld_b);
+void omc_launch_copy_rows(omc_ctx* ctx, unsigned gx, int64_t p, const double* src, int64_t ld_s, double* dst, int64_t ld_d);
+// blocks of 256 that cover n, between 1 and 4096: the x extent of the dense route's and the design helpers' grids
+inline unsigned omc_gx(int64_t n) {
+  const int64_t g = (n + 255) / 256;
+  return (unsigned)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
+}
 
 #define OMC_NO_BAD_CHAIN 0x7fffffffffffffffLL
 

@@ -202,7 +202,7 @@ extern "C" omc_status omc_store_cov(omc_ctx* ctx, int64_t n_iter, int64_t size_a
   // workspace: means and variances of both sides, the word of the index check, then the partial tiles [splits][batches][n_a][n_b]
   const size_t n_ma = (size_t)batches * n_a, n_mb = symmetric ? 0 : (size_t)batches * n_b;
   const size_t n_part = (size_t)splits * batches * n_a * n_b;
-  omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->cov_ws, &ctx->cov_ws_bytes, (2 * n_ma + 2 * n_mb + 1 + n_part) * sizeof(double));
+  omc_status st = omc_ensure(ctx, ctx->cov_ws, (2 * n_ma + 2 * n_mb + 1 + n_part) * sizeof(double));
   if (st != OMC_OK) return st;
   double* mean_a = ctx->cov_ws;
   double* var_a = mean_a + n_ma;

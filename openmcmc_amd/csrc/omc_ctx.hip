@@ -1,9 +1,10 @@
-// Context, status latch, options.
+// Context: creation and release, its BLAS handles and side stream, status latch, counters, options (the table: omc_options.h).
 #include <string.h>
 
 #include <string>
 
-#include "omc_common.h"
+#include "omc_blas.h"
+#include "omc_options.h"
 
 static thread_local std::string g_last_error;
 
@@ -12,6 +13,45 @@ void omc_set_error(const char* what, hipError_t e) {
 }
 
 void omc_set_error_text(const char* text) { g_last_error = text; }
+
+omc_status omc_ensure_blas(omc_ctx* ctx) {
+  if (!ctx->blas) {
+    rocblas_handle h;
+    OMC_BLAS_CHECK(rocblas_create_handle(&h));
+    OMC_BLAS_CHECK(rocblas_set_stream(h, ctx->stream));
+    OMC_BLAS_CHECK(rocblas_set_pointer_mode(h, rocblas_pointer_mode_host));
+    ctx->blas = (void*)h;
+  }
+  return OMC_OK;
+}
+
+// side stream, its BLAS handle and the fork / join events of the blocked factorisation (made on first use)
+omc_status omc_ensure_aux(omc_ctx* ctx) {
+  if (ctx->blas_aux) return OMC_OK;
+  OMC_HIP_CHECK(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
+  OMC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+  OMC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+  rocblas_handle h;
+  OMC_BLAS_CHECK(rocblas_create_handle(&h));
+  OMC_BLAS_CHECK(rocblas_set_stream(h, ctx->aux_stream));
+  OMC_BLAS_CHECK(rocblas_set_pointer_mode(h, rocblas_pointer_mode_host));
+  ctx->blas_aux = (void*)h;
+  return OMC_OK;
+}
+
+void omc_ctx_release_blas(omc_ctx* ctx) {
+  if (ctx->blas) rocblas_destroy_handle((rocblas_handle)ctx->blas);
+  ctx->blas = nullptr;
+  if (ctx->blas_aux) {
+    rocblas_destroy_handle((rocblas_handle)ctx->blas_aux);
+    hipEventDestroy(ctx->ev_fork);
+    hipEventDestroy(ctx->ev_join);
+    hipStreamDestroy(ctx->aux_stream);
+    for (int i = 0; i < 4; ++i)  // omc_mala_run_white made them behind omc_ensure_aux
+      if (ctx->white.ev[i]) { hipEventDestroy(ctx->white.ev[i]); ctx->white.ev[i] = nullptr; }
+    ctx->blas_aux = nullptr;
+  }
+}
 
 extern "C" {
 
@@ -27,71 +67,28 @@ omc_status omc_ctx_create(int32_t device, int64_t n_chains, uint64_t seed, int64
   OMC_HIP_CHECK(hipGetDeviceCount(&count));
   if (device < 0 || device >= count) return OMC_INVALID_ARG;
   OMC_HIP_CHECK(hipSetDevice(device));
-  omc_ctx* c = new omc_ctx();
+  omc_ctx* c = new omc_ctx();  // every default: omc_common.h
   c->device = device;
-  c->dev_cus = 256;
   if (hipDeviceGetAttribute(&c->dev_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->dev_cus <= 0) c->dev_cus = 256;
   c->n_chains = n_chains;
   c->seed = seed;
   c->chain_offset = chain_id_offset;
   c->own_stream = (create_stream != 0);
-  c->workspace = nullptr;
-  c->long_band = nullptr; c->long_band_bytes = 0; c->long_quad = nullptr; c->long_quad_bytes = 0;
-  c->workspace_bytes = 0;
-  c->blas = nullptr;
-  c->store_ws = nullptr; c->store_ws_bytes = 0;
-  c->cov_ws = nullptr; c->cov_ws_bytes = 0;
-  c->rank_ws = nullptr; c->rank_ws_bytes = 0;
-  c->dense_factor = nullptr; c->dense_factor_bytes = 0;
-  c->dense_winv = nullptr; c->dense_winv_bytes = 0; c->dense_panel_old = 0;
-  c->dense_info = nullptr; c->dense_info_bytes = 0;
-  c->slice_buf = nullptr; c->slice_buf_bytes = 0;
-  c->dense_tmp = nullptr; c->dense_tmp_bytes = 0;
-  c->rj_tmp = nullptr; c->rj_tmp_bytes = 0;
-  c->mh_work = nullptr; c->mh_work_bytes = 0;
-  c->mala = {}; c->white = {}; c->rww = {}; c->rw = {};  // no buffers, no events, nothing cached
-  c->tridiag_algo = 0;
-  c->tridiag_seg = 0;
-  c->tridiag_generic = 0;
-  c->tridiag_newton_max = 4;
-  c->tridiag_perturb_ppb = 0;
-  c->tridiag_quad_skip = 0;
-  c->stamps = nullptr;
-  c->sweep_times = nullptr; c->sweep_times_cap = 0; c->sweep_times_pos = 0;
-  c->launch_log_n = 0; c->launch_log_total = 0;
-  c->blas_aux = nullptr;
-  c->aux_stream = nullptr;
-  c->ev_fork = c->ev_join = nullptr;
-  c->dense_overlap = 1;
-  c->dense_blocked_min = 144;  // measured crossover with rocSOLVER: even at 128, the blocked route 1.3-1.8x faster at 200
-  c->debug_zero_z = 0;
-  c->dense_use_rocsolver = 0;
-  c->gram_use_rocblas = 0;
-  c->spectral_use_rocblas = 0;
-  c->mh_use_rocblas = 0;
-  c->mh_gemm_ksplit = 4;
-  c->diag_algo = 0;
-  c->hist_algo = 0;
-  c->hist2d_algo = 0;
-  c->reduce_algo = 0;
-  c->rank_tile = 0; c->rank_chunk = 0;
-  c->autocorr_slice = 0;
-  c->band_algo = 0; c->band_seg_overlap = 192; c->band_seg_count = 0; c->band_blocked_threads = 0;
-  if (c->own_stream) {
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { omc_set_error("hipStreamCreate", e); delete c; return OMC_HIP_ERROR; }
-  } else {
-    c->stream = (hipStream_t)stream;
+  c->stream = (hipStream_t)stream;
+  const long long init[8] = {OMC_NO_BAD_CHAIN, 0, 0, 0, 0, 0, 0, 0};  // the status words
+  const char* what = "hipStreamCreate";
+  hipError_t e = c->own_stream ? hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) : hipSuccess;
+  if (e != hipSuccess) c->own_stream = false;  // nothing to destroy
+  if (e == hipSuccess) { what = "hipMalloc"; e = hipMalloc(&c->status_words.p, sizeof(init)); }
+  if (e == hipSuccess) { what = "hipMemcpy"; e = hipMemcpy(c->status_words, init, sizeof(init), hipMemcpyHostToDevice); }
+  if (e != hipSuccess) {
+    omc_set_error(what, e);
+    if (c->own_stream) hipStreamDestroy(c->stream);
+    delete c;  // frees the status words
+    return OMC_HIP_ERROR;
   }
-  c->d_gamma_tab = nullptr;
-  c->run_ev_begin = c->run_ev_end = nullptr;
-  c->d_handoff = nullptr; c->run_epoch = 1; c->run_sweeps_per_launch = 32; c->run_reenter = 2; c->run_reenter_force = 0; c->run_block_sweeps = 0;
-  hipError_t e = hipMalloc(&c->d_bad_chain, 8 * sizeof(long long));
-  if (e != hipSuccess) { omc_set_error("hipMalloc", e); delete c; return OMC_HIP_ERROR; }
+  c->d_bad_chain = c->status_words;
   c->d_fallbacks = (unsigned long long*)(c->d_bad_chain + 1);
-  long long init[8] = {OMC_NO_BAD_CHAIN, 0, 0, 0, 0, 0, 0, 0};
-  e = hipMemcpy(c->d_bad_chain, init, sizeof(init), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { omc_set_error("hipMemcpy", e); hipFree(c->d_bad_chain); delete c; return OMC_HIP_ERROR; }
   *out = c;
   return OMC_OK;
 }
@@ -100,32 +97,10 @@ omc_status omc_ctx_destroy(omc_ctx* ctx) {
   if (!ctx) return OMC_INVALID_ARG;
   hipSetDevice(ctx->device);
   hipStreamSynchronize(ctx->stream);
-  if (ctx->workspace) hipFree(ctx->workspace);
-  if (ctx->store_ws) hipFree(ctx->store_ws);
-  if (ctx->cov_ws) hipFree(ctx->cov_ws);
-  if (ctx->rank_ws) hipFree(ctx->rank_ws);
-  if (ctx->long_band) hipFree(ctx->long_band);
-  if (ctx->long_quad) hipFree(ctx->long_quad);
-  if (ctx->d_gamma_tab) hipFree(ctx->d_gamma_tab);
-  if (ctx->d_handoff) hipFree(ctx->d_handoff);
-  if (ctx->dense_factor) hipFree(ctx->dense_factor);
-  if (ctx->dense_winv) hipFree(ctx->dense_winv);
-  if (ctx->dense_info) hipFree(ctx->dense_info);
-  if (ctx->slice_buf) hipFree(ctx->slice_buf);
-  if (ctx->dense_tmp) hipFree(ctx->dense_tmp);
-  if (ctx->rj_tmp) hipFree(ctx->rj_tmp);
-  if (ctx->mh_work) hipFree(ctx->mh_work);
-  if (ctx->mala.prep) hipFree(ctx->mala.prep);
-  if (ctx->white.prep) hipFree(ctx->white.prep);
-  if (ctx->white.a) hipFree(ctx->white.a);
-  if (ctx->white.traj) hipFree(ctx->white.traj);
-  if (ctx->rww.a) hipFree(ctx->rww.a);
-  if (ctx->rww.mu_neg) hipFree(ctx->rww.mu_neg);
-  if (ctx->rw.prep) hipFree(ctx->rw.prep);
-  omc_dense_release(ctx);
-  hipFree(ctx->d_bad_chain);
-  if (ctx->own_stream) hipStreamDestroy(ctx->stream);
-  delete ctx;
+  omc_ctx_release_blas(ctx);
+  const hipStream_t owned = ctx->own_stream ? ctx->stream : nullptr;
+  delete ctx;  // every omc_buf of the context frees itself
+  if (owned) hipStreamDestroy(owned);
   return OMC_OK;
 }
 
@@ -162,23 +137,12 @@ omc_status omc_ctx_status(omc_ctx* ctx, int64_t* first_bad_chain) {
 
 omc_status omc_ctx_counter(omc_ctx* ctx, const char* name, int64_t* value) {
   if (!ctx || !name || !value) return OMC_INVALID_ARG;
-  if (!strcmp(name, "run_handoff_timeouts")) {
+  static const struct { const char* name; int word; } device_counters[] = {  // words behind d_fallbacks (omc_common.h)
+      {"tridiag_join_fallbacks", 0}, {"run_handoff_timeouts", 1}, {"band_join_fallbacks", 2}, {"band_join_retries", 3}};
+  for (const auto& dc : device_counters) {
+    if (strcmp(name, dc.name)) continue;
     unsigned long long v = 0;
-    OMC_HIP_CHECK(hipMemcpyAsync(&v, ctx->d_fallbacks + 1, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-    OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    *value = (int64_t)v;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "band_join_retries")) {
-    unsigned long long v = 0;
-    OMC_HIP_CHECK(hipMemcpyAsync(&v, ctx->d_fallbacks + 3, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-    OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    *value = (int64_t)v;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "band_join_fallbacks")) {
-    unsigned long long v = 0;
-    OMC_HIP_CHECK(hipMemcpyAsync(&v, ctx->d_fallbacks + 2, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
+    OMC_HIP_CHECK(hipMemcpyAsync(&v, ctx->d_fallbacks + dc.word, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
     OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     *value = (int64_t)v;
     return OMC_OK;
@@ -198,13 +162,6 @@ omc_status omc_ctx_counter(omc_ctx* ctx, const char* name, int64_t* value) {
     *value = ctx->sweep_times_pos;
     return OMC_OK;
   }
-  if (!strcmp(name, "tridiag_join_fallbacks")) {
-    unsigned long long v = 0;
-    OMC_HIP_CHECK(hipMemcpyAsync(&v, ctx->d_fallbacks, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-    OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    *value = (int64_t)v;
-    return OMC_OK;
-  }
   return OMC_INVALID_ARG;
 }
 
@@ -222,172 +179,7 @@ omc_status omc_ctx_launch_log(omc_ctx* ctx, double* out, int64_t cap, int64_t* n
 
 omc_status omc_ctx_set_option(omc_ctx* ctx, const char* name, int64_t value) {
   if (!ctx || !name) return OMC_INVALID_ARG;
-  if (!strcmp(name, "tridiag_algo")) {
-    if (value < 0 || value > 2) return OMC_INVALID_ARG;
-    ctx->tridiag_algo = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "tridiag_seg")) {
-    if (value != 0 && value != 8 && value != 10 && value != 16 && value != 20 && value != 32) return OMC_INVALID_ARG;
-    ctx->tridiag_seg = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "run_sweeps_per_launch")) {
-    if (value < 1 || value > 32) return OMC_INVALID_ARG;
-    ctx->run_sweeps_per_launch = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "run_block_sweeps")) {
-    if (value < 0 || value > 32) return OMC_INVALID_ARG;
-    ctx->run_block_sweeps = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "run_reenter")) {
-    if (value < 0 || value > 2) return OMC_INVALID_ARG;
-    ctx->run_reenter = (int)value;
-    ctx->run_reenter_force = 1;  // an explicit choice holds for every chain count (tests, A/B runs)
-    return OMC_OK;
-  }
-  if (!strcmp(name, "tridiag_quad_skip")) {
-    if (value < 0 || value > 15) return OMC_INVALID_ARG;
-    ctx->tridiag_quad_skip = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "tridiag_perturb_ppb")) {
-    if (value < 0 || value > 1000000000) return OMC_INVALID_ARG;
-    ctx->tridiag_perturb_ppb = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "tridiag_newton_max")) {
-    if (value < 0 || value > 64) return OMC_INVALID_ARG;
-    ctx->tridiag_newton_max = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "tridiag_generic")) {
-    ctx->tridiag_generic = value != 0;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "band_algo")) {
-    if (value < 0 || value > 3) return OMC_INVALID_ARG;
-    ctx->band_algo = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "diag_algo")) {
-    if (value < 0 || value > 2) return OMC_INVALID_ARG;
-    ctx->diag_algo = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "hist_algo")) {
-    if (value < 0 || value > 1) return OMC_INVALID_ARG;
-    ctx->hist_algo = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "reduce_algo")) {
-    if (value < 0 || value > 2) return OMC_INVALID_ARG;
-    ctx->reduce_algo = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "hist2d_algo")) {
-    if (value < 0 || value > 3) return OMC_INVALID_ARG;
-    ctx->hist2d_algo = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "rank_tile")) {
-    if (value != 0 && (value < 64 || value > 8192 || (value & (value - 1)))) return OMC_INVALID_ARG;
-    ctx->rank_tile = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "rank_chunk")) {
-    if (value < 0) return OMC_INVALID_ARG;
-    ctx->rank_chunk = value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "autocorr_slice")) {
-    if (value < 0) return OMC_INVALID_ARG;
-    ctx->autocorr_slice = value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "band_seg_overlap")) {
-    if (value < 8 || value > 65536) return OMC_INVALID_ARG;
-    ctx->band_seg_overlap = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "band_seg_count")) {
-    if (value < 0 || value == 1 || value > 128) return OMC_INVALID_ARG;
-    ctx->band_seg_count = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "band_blocked_threads")) {
-    if (value != 0 && value != 512 && value != 4 && value != 8 && value != 16) return OMC_INVALID_ARG;
-    ctx->band_blocked_threads = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "mh_gemm_ksplit")) {
-    if (value != 1 && value != 2 && value != 4) return OMC_INVALID_ARG;
-    ctx->mh_gemm_ksplit = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "mh_use_rocblas")) {
-    ctx->mh_use_rocblas = value != 0;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "gram_use_rocblas")) {
-    ctx->gram_use_rocblas = value != 0;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "spectral_use_rocblas")) {
-    ctx->spectral_use_rocblas = value != 0;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "dense_use_rocsolver")) {
-    ctx->dense_use_rocsolver = value != 0;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "debug_zero_z")) {
-    ctx->debug_zero_z = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "dense_blocked_min")) {
-    if (value < 1 || value > 32768) return OMC_INVALID_ARG;
-    ctx->dense_blocked_min = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "dense_panel_old")) {
-    if (value != 0 && value != 1) return OMC_INVALID_ARG;
-    ctx->dense_panel_old = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "dense_overlap")) {
-    if (value != 0 && value != 1) return OMC_INVALID_ARG;
-    ctx->dense_overlap = (int)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "sweep_times_ptr")) {  // diagnostic: device ring [cap][n_chains][2] of uint64, 0 = off (set the capacity first)
-    if (value != 0 && ctx->sweep_times_cap < OMC_SWEEP_RING_MIN) return OMC_INVALID_ARG;
-    ctx->sweep_times = (unsigned long long*)(uintptr_t)value;
-    ctx->sweep_times_pos = 0;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "sweep_times_cap")) {
-    if (value != 0 && value < OMC_SWEEP_RING_MIN) return OMC_INVALID_ARG;
-    // a ring set earlier was sized for the OLD capacity: the clock stays off until a pointer is given for the new one
-    // (a larger capacity on the old pointer would have omc_gmrf_run write records past the ring's end)
-    if (value != ctx->sweep_times_cap) ctx->sweep_times = nullptr;
-    ctx->sweep_times_cap = value;
-    ctx->sweep_times_pos = 0;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "run_event_begin") || !strcmp(name, "run_event_end")) {
-    // a caller-owned hipEvent_t (0 = none): omc_gmrf_run records it on the context's stream in front of its first / behind its
-    // last launch -- the timing events of a caller whose own event calls cost more than the launch (an interpreter)
-    (name[10] == 'b' ? ctx->run_ev_begin : ctx->run_ev_end) = (hipEvent_t)(uintptr_t)value;
-    return OMC_OK;
-  }
-  if (!strcmp(name, "stamps_ptr")) {  // diagnostic: device buffer [n_chains][16][16] of uint64, 0 = off
-    ctx->stamps = (unsigned long long*)(uintptr_t)value;
-    return OMC_OK;
-  }
-  return OMC_INVALID_ARG;
+  return omc_option_apply(ctx, name, value);  // the table: omc_options.h
 }
 
 }  // extern "C"

@@ -1,68 +1,14 @@
-// Dense Normal-Normal path (regression-shaped conditionals): batched assembly + rocSOLVER batched
-// Cholesky + rocBLAS batched triangular solves, and the design-matrix GEMMs (fp64 MFMA through
-// rocBLAS).  Reference call sites: sampler.py:176-197, location_scale.py:234-242, gmrf.py:434,462,481.
+// Dense Normal-Normal path (regression-shaped conditionals), the canonical draw: batched assembly, batched Cholesky (blocked
+// here from order "dense_blocked_min" on, rocSOLVER below) and batched triangular solves.  Reference call sites:
+// sampler.py:176-197, gmrf.py:434,462,481.  The spectral route of the same draw: omc_spectral.hip; the design-matrix helpers:
+// omc_design.hip.
 #include <math.h>
-#include <rocblas/rocblas.h>
-#include <rocsolver/rocsolver.h>
 
-#include "omc_common.h"
-
-struct DenseTermsDev {
-  int n_terms;
-  const double* mat[OMC_MAX_TERMS];
-  const double* rhs[OMC_MAX_TERMS];
-  const double* scale[OMC_MAX_TERMS];
-  const double* diag_chain;  // [C][p] per-chain diagonal, or NULL
-};
-
-#define OMC_BLAS_CHECK(expr)                                   \
-  do {                                                         \
-    rocblas_status _s = (expr);                                \
-    if (_s != rocblas_status_success) {                        \
-      omc_set_error(#expr, hipErrorUnknown);                   \
-      return OMC_HIP_ERROR;                                    \
-    }                                                          \
-  } while (0)
-
-omc_status omc_ensure_blas(omc_ctx* ctx) {
-  if (!ctx->blas) {
-    rocblas_handle h;
-    OMC_BLAS_CHECK(rocblas_create_handle(&h));
-    OMC_BLAS_CHECK(rocblas_set_stream(h, ctx->stream));
-    OMC_BLAS_CHECK(rocblas_set_pointer_mode(h, rocblas_pointer_mode_host));
-    ctx->blas = (void*)h;
-  }
-  return OMC_OK;
-}
-
-// side stream, its BLAS handle and the fork / join events of the blocked factorisation (made on first use)
-omc_status omc_ensure_aux(omc_ctx* ctx) {
-  if (ctx->blas_aux) return OMC_OK;
-  OMC_HIP_CHECK(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-  OMC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-  OMC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-  rocblas_handle h;
-  OMC_BLAS_CHECK(rocblas_create_handle(&h));
-  OMC_BLAS_CHECK(rocblas_set_stream(h, ctx->aux_stream));
-  OMC_BLAS_CHECK(rocblas_set_pointer_mode(h, rocblas_pointer_mode_host));
-  ctx->blas_aux = (void*)h;
-  return OMC_OK;
-}
-
-omc_status omc_ensure_bytes(omc_ctx* ctx, void** buf, size_t* have, size_t need) {
-  if (*have >= need) return OMC_OK;
-  OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (*buf) OMC_HIP_CHECK(hipFree(*buf));
-  *buf = nullptr;
-  *have = 0;
-  OMC_HIP_CHECK(hipMalloc(buf, need));
-  *have = need;
-  return OMC_OK;
-}
+#include "omc_blas.h"
 
 // Q[c] = sum_k s_k[c] M_k, lower triangle only (column-major: element (row, col) at col*p + row, row >= col): the
 // factorisations read nothing else, and the upper half would be 1 GB of writes per sweep at p = 1000, C = 256
-__global__ void __launch_bounds__(256) k_dense_assemble(DenseTermsDev T, int64_t p, int64_t C, double* Q) {
+__global__ void __launch_bounds__(256) k_dense_assemble(omc_dense_terms T, int64_t p, int64_t C, double* Q) {
   const int64_t c = blockIdx.y;
   double sc[OMC_MAX_TERMS];
 #pragma unroll
@@ -84,7 +30,7 @@ __global__ void __launch_bounds__(256) k_dense_assemble(DenseTermsDev T, int64_t
 }
 
 // b[c] = sum_k s_k[c] rhs_k + rhs_chain[c]
-__global__ void k_dense_rhs(DenseTermsDev T, int64_t p, int64_t C, const double* rhs_chain, int64_t ld_rhs,
+__global__ void k_dense_rhs(omc_dense_terms T, int64_t p, int64_t C, const double* rhs_chain, int64_t ld_rhs,
                             double* b, int64_t ld_b) {
   const int64_t c = blockIdx.y;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < p; i += (int64_t)gridDim.x * blockDim.x) {
@@ -130,83 +76,6 @@ __global__ void k_add_draw(int64_t p, int64_t C, int64_t chain_offset, omc_rng_k
     t[c * ld_t + 2 * q] += z0;
     if (2 * q + 1 < p) t[c * ld_t + 2 * q + 1] += z1;
   }
-}
-
-// Spectral route: in the eigenbasis of the one shared matrix, Q_c = diag(d_c), d_c[i] = a_c + b_c ev[i].
-//   t holds V' rhs_c on entry; on exit m_c = t / d (into `mean` if given) and y_c = m_c + z / sqrt(d) (into t);
-//   logdet_c = sum log d; a non-positive d latches the chain like a failed factorisation.
-__global__ void __launch_bounds__(256) k_spectral_scale(DenseTermsDev T, int kmat, int64_t p, int64_t C, const double* ev,
-                                                        int64_t chain_offset, omc_rng_key key, const double* z, int64_t ld_z,
-                                                        double* t, int64_t ld_t, double* mean, int64_t ld_m, double* logdet,
-                                                        long long* bad) {
-  __shared__ double red[4];
-  const int64_t c = blockIdx.x;
-  double a = 0.0, b = 0.0;
-#pragma unroll
-  for (int k = 0; k < OMC_MAX_TERMS; ++k) {
-    if (k >= T.n_terms) continue;
-    const double sk = T.scale[k] ? T.scale[k][c] : 1.0;
-    if (k == kmat) b = sk;
-    else a += sk;
-  }
-  double acc = 0.0;
-  bool neg = false;
-  const int64_t npairs = (p + 1) / 2;
-  for (int64_t q = threadIdx.x; q < npairs; q += blockDim.x) {
-    double z0, z1;
-    if (z) {
-      z0 = z[c * ld_z + 2 * q];
-      z1 = (2 * q + 1 < p) ? z[c * ld_z + 2 * q + 1] : 0.0;
-    } else {
-      omc_normal_pair(omc_rng_block(key, chain_offset + c, (uint32_t)q), z0, z1);
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int64_t i = 2 * q + h;
-      if (i >= p) continue;
-      const double d = fma(b, ev[i], a);
-      neg |= !(d > 0.0);
-      const double r = 1.0 / d, m = t[c * ld_t + i] * r;
-      if (mean) mean[c * ld_m + i] = m;
-      t[c * ld_t + i] = fma(h ? z1 : z0, sqrt(r), m);
-      acc += log(d);
-    }
-  }
-  if (neg) atomicMin((unsigned long long*)bad, (unsigned long long)c);
-  if (!logdet) return;
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) logdet[c] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ void k_copy_rows(int64_t p, const double* src, int64_t ld_s, double* dst, int64_t ld_d) {
-  const int64_t c = blockIdx.y;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < p; i += (int64_t)gridDim.x * blockDim.x)
-    dst[c * ld_d + i] = src[c * ld_s + i];
-}
-
-// Xw[i][j] = w[i] * X[i][j]
-__global__ void k_scale_rows(int64_t n, int64_t p, const double* X, const double* w, double* out) {
-  const int64_t total = n * p;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = X[i] * w[i / p];
-}
-
-__global__ void __launch_bounds__(256) k_weighted_resid_sq(int64_t n, const double* y, const double* f, int64_t ld_f,
-                                                          const double* w, double* out) {
-  __shared__ double red[4];
-  const int64_t c = blockIdx.x;
-  const double* fc = f + c * ld_f;
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-    const double r = y[i] - fc[i];
-    acc = fma((w ? w[i] : 1.0) * r, r, acc);
-  }
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) out[c] = red[0] + red[1] + red[2] + red[3];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -540,7 +409,7 @@ static omc_status potrf_blocked_part(omc_ctx* ctx, rocblas_handle h, hipStream_t
 static omc_status potrf_blocked(omc_ctx* ctx, rocblas_handle h, int64_t p, double* Q, int64_t C) {
   OMC_HIP_CHECK(hipMemsetAsync(ctx->dense_info, 0, (size_t)C * sizeof(int), ctx->stream));
   {
-    const omc_status st0 = omc_ensure_bytes(ctx, (void**)&ctx->dense_winv, &ctx->dense_winv_bytes, (size_t)C * CH_NB * CH_NB * sizeof(double));
+    const omc_status st0 = omc_ensure(ctx, ctx->dense_winv, (size_t)C * CH_NB * CH_NB * sizeof(double));
     if (st0 != OMC_OK) return st0;
   }
   // The panel kernel is one latency-bound workgroup per chain and the update GEMM cannot start before it: in one batch the
@@ -579,23 +448,10 @@ static omc_status tri_solve(omc_ctx* ctx, rocblas_handle h, bool trans, int64_t 
   return OMC_OK;
 }
 
-static unsigned gx(int64_t n) {
-  int64_t g = (n + 255) / 256;
-  return (unsigned)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
-}
-
-void omc_dense_release(omc_ctx* ctx) {
-  if (ctx->blas) rocblas_destroy_handle((rocblas_handle)ctx->blas);
-  ctx->blas = nullptr;
-  if (ctx->blas_aux) {
-    rocblas_destroy_handle((rocblas_handle)ctx->blas_aux);
-    hipEventDestroy(ctx->ev_fork);
-    hipEventDestroy(ctx->ev_join);
-    hipStreamDestroy(ctx->aux_stream);
-    for (int i = 0; i < 4; ++i)
-      if (ctx->white.ev[i]) { hipEventDestroy(ctx->white.ev[i]); ctx->white.ev[i] = nullptr; }
-    ctx->blas_aux = nullptr;
-  }
+// for the spectral draw (omc_spectral.hip), which forms the same right-hand sides
+void omc_launch_dense_rhs(omc_ctx* ctx, unsigned gx, const omc_dense_terms& T, int64_t p, const double* rhs_chain, int64_t ld_rhs, double* b,
+                          int64_t ld_b) {
+  hipLaunchKernelGGL(k_dense_rhs, dim3(gx, (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, T, p, (int64_t)ctx->n_chains, rhs_chain, ld_rhs, b, ld_b);
 }
 
 extern "C" {
@@ -612,22 +468,14 @@ omc_status omc_dense_sample_canonical(omc_ctx* ctx, int64_t p, const omc_dense_t
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   omc_status st = omc_ensure_blas(ctx);
   if (st != OMC_OK) return st;
-  st = omc_ensure_bytes(ctx, (void**)&ctx->dense_factor, &ctx->dense_factor_bytes, (size_t)C * p * p * sizeof(double));
+  st = omc_ensure(ctx, ctx->dense_factor, (size_t)C * p * p * sizeof(double));
   if (st != OMC_OK) return st;
-  st = omc_ensure_bytes(ctx, (void**)&ctx->dense_info, &ctx->dense_info_bytes, (size_t)C * sizeof(int));
+  st = omc_ensure(ctx, ctx->dense_info, (size_t)C * sizeof(int));
   if (st != OMC_OK) return st;
-  DenseTermsDev T{};
-  T.n_terms = terms->n_terms;
-  for (int k = 0; k < OMC_MAX_TERMS; ++k) {
-    const bool on = k < terms->n_terms;
-    T.mat[k] = on ? terms->mat[k] : nullptr;
-    T.rhs[k] = on ? terms->rhs[k] : nullptr;
-    T.scale[k] = on ? terms->scale[k] : nullptr;
-  }
-  T.diag_chain = terms->diag_chain;
+  const omc_dense_terms T = omc_dense_terms_clean(terms, true);
   rocblas_handle h = (rocblas_handle)ctx->blas;
   double* Q = ctx->dense_factor;
-  hipLaunchKernelGGL(k_dense_assemble, dim3(gx(p * p) > 64 ? 64 : gx(p * p), (unsigned)C), dim3(256), 0, ctx->stream, T, p, C, Q);
+  hipLaunchKernelGGL(k_dense_assemble, dim3(omc_gx(p * p) > 64 ? 64 : omc_gx(p * p), (unsigned)C), dim3(256), 0, ctx->stream, T, p, C, Q);
   OMC_HIP_CHECK(hipGetLastError());
   if (p >= ctx->dense_blocked_min && !ctx->dense_use_rocsolver) {
     st = potrf_blocked(ctx, h, p, Q, C);
@@ -640,253 +488,22 @@ omc_status omc_dense_sample_canonical(omc_ctx* ctx, int64_t p, const omc_dense_t
                      logdet_out, ctx->d_bad_chain);
   OMC_HIP_CHECK(hipGetLastError());
   // w = L^{-1} b in x_out
-  hipLaunchKernelGGL(k_dense_rhs, dim3(gx(p), (unsigned)C), dim3(256), 0, ctx->stream, T, p, C, rhs_chain, ld_rhs, x_out, ld_x);
+  hipLaunchKernelGGL(k_dense_rhs, dim3(omc_gx(p), (unsigned)C), dim3(256), 0, ctx->stream, T, p, C, rhs_chain, ld_rhs, x_out, ld_x);
   OMC_HIP_CHECK(hipGetLastError());
   st = tri_solve(ctx, h, false, p, Q, x_out, ld_x, C);
   if (st != OMC_OK) return st;
   if (mean_out) {  // mu = L^{-T} w  (gmrf.py:196)
-    hipLaunchKernelGGL(k_copy_rows, dim3(gx(p), (unsigned)C), dim3(256), 0, ctx->stream, p, x_out, ld_x, mean_out, ld_mean);
+    omc_launch_copy_rows(ctx, omc_gx(p), p, x_out, ld_x, mean_out, ld_mean);
     OMC_HIP_CHECK(hipGetLastError());
     st = tri_solve(ctx, h, true, p, Q, mean_out, ld_mean, C);
     if (st != OMC_OK) return st;
   }
   // x = L^{-T} (w + z)
-  hipLaunchKernelGGL(k_add_draw, dim3(gx((p + 1) / 2), (unsigned)C), dim3(256), 0, ctx->stream, p, C, ctx->chain_offset,
+  hipLaunchKernelGGL(k_add_draw, dim3(omc_gx((p + 1) / 2), (unsigned)C), dim3(256), 0, ctx->stream, p, C, ctx->chain_offset,
                      omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL), z_inject, ld_z, x_out, ld_x);
   OMC_HIP_CHECK(hipGetLastError());
   st = tri_solve(ctx, h, true, p, Q, x_out, ld_x, C);
   if (st != OMC_OK) return st;
-  return OMC_OK;
-}
-
-// ---- spectral route of the dense conjugate draw ---------------------------------------------------------------------
-// out = in' for a p x p matrix (32 x 32 tiles through LDS): omc_dgemm_small takes its left operand untransposed
-__global__ void __launch_bounds__(256) k_transpose_sq(int64_t p, const double* __restrict__ in, double* __restrict__ out) {
-  __shared__ double tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int64_t i0 = (int64_t)blockIdx.y * 32, j0 = (int64_t)blockIdx.x * 32;
-  for (int r = ty; r < 32; r += 8)
-    if (i0 + r < p && j0 + tx < p) tile[r][tx] = in[(i0 + r) * p + j0 + tx];
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8)
-    if (j0 + r < p && i0 + tx < p) out[(j0 + r) * p + i0 + tx] = tile[tx][r];
-}
-
-// The three products of the draw (V' B, V Y, V M: p x p times the p x C block of all chains) go through omc_dgemm_small, whose
-// every output column is one accumulation over the contraction that does not depend on the number of columns or on the
-// column's place among them: a chain's draw is then the same bits in a context of any size (chains shard over GPUs).  A
-// library GEMM picks its kernel, and with it the order of summation, by the number of columns ("spectral_use_rocblas" 1
-// keeps that route for cross-checks).  The products are launched with the in-workgroup split of the contraction fixed at 4
-// (SPECTRAL_KSPLIT), not with the context's "mh_gemm_ksplit": that option tunes the Metropolis-Hastings steps and must not
-// move this draw's bits.  omc_dgemm_small has no transposed left operand, so V' is written out once per draw into the
-// workspace (p x p doubles next to the two [C][p] blocks).
-// (omc_dense_spectral_sample itself sets no upper limit on p -- only the eigensolver's entry point does -- and the own
-// kernel's indices are ints: beyond 46340 the library route.)
-#define SPECTRAL_KSPLIT 4
-static bool spectral_own_gemm(const omc_ctx* ctx, int64_t p) { return !ctx->spectral_use_rocblas && p <= 46340; }
-
-omc_status omc_dense_spectral_prepare(omc_ctx* ctx, int64_t p, const double* M, double* V_out, double* ev_out) {
-  if (!ctx || p < 1 || p > 32768 || !M || !V_out || !ev_out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  omc_status st = omc_ensure_blas(ctx);
-  if (st != OMC_OK) return st;
-  rocblas_handle h = (rocblas_handle)ctx->blas;
-  st = omc_ensure_bytes(ctx, (void**)&ctx->dense_tmp, &ctx->dense_tmp_bytes, (size_t)p * sizeof(double));
-  if (st != OMC_OK) return st;
-  st = omc_ensure_bytes(ctx, (void**)&ctx->dense_info, &ctx->dense_info_bytes, sizeof(int));
-  if (st != OMC_OK) return st;
-  OMC_HIP_CHECK(hipMemcpyAsync(V_out, M, (size_t)p * p * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  OMC_BLAS_CHECK(rocsolver_dsyevd(h, rocblas_evect_original, rocblas_fill_lower, (rocblas_int)p, V_out, (rocblas_int)p, ev_out,
-                                  ctx->dense_tmp, ctx->dense_info));
-  int info = 0;
-  OMC_HIP_CHECK(hipMemcpyAsync(&info, ctx->dense_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (info != 0) { omc_set_error_text("omc_dense_spectral_prepare: the eigensolver did not converge"); return OMC_HIP_ERROR; }
-  return OMC_OK;
-}
-
-omc_status omc_dense_spectral_sample(omc_ctx* ctx, int64_t p, const omc_dense_terms* terms, int32_t k_mat, const double* V,
-                                     const double* ev, const double* rhs_chain, int64_t ld_rhs, const double* z_inject,
-                                     int64_t ld_z, uint64_t draw_index, double* x_out, int64_t ld_x, double* mean_out,
-                                     int64_t ld_mean, double* logdet_out) {
-  if (!ctx || p < 1 || !terms || terms->n_terms < 1 || terms->n_terms > OMC_MAX_TERMS || k_mat < 0 || k_mat >= terms->n_terms)
-    return OMC_INVALID_ARG;
-  if (!V || !ev || !x_out || ld_x < p || (rhs_chain && ld_rhs < p) || (z_inject && ld_z < p) || (mean_out && ld_mean < p))
-    return OMC_INVALID_ARG;
-  if (terms->diag_chain || !terms->mat[k_mat]) return OMC_INVALID_ARG;
-  for (int k = 0; k < terms->n_terms; ++k)
-    if (k != k_mat && terms->mat[k]) return OMC_INVALID_ARG;  // every other term must be a scaled identity
-  const int64_t C = ctx->n_chains;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  const bool own = spectral_own_gemm(ctx, p);
-  omc_status st = own ? OMC_OK : omc_ensure_blas(ctx);  // (the own products need no library handle)
-  if (st != OMC_OK) return st;
-  rocblas_handle h = own ? nullptr : (rocblas_handle)ctx->blas;
-  st = omc_ensure_bytes(ctx, (void**)&ctx->dense_factor, &ctx->dense_factor_bytes,
-                        ((size_t)2 * C * p + (own ? (size_t)p * p : 0)) * sizeof(double));
-  if (st != OMC_OK) return st;
-  double* W = ctx->dense_factor;       // [C][p]: V' rhs, then y
-  double* Mw = W + C * p;              // [C][p]: m in the eigenbasis
-  double* Vt = Mw + C * p;             // [p][p]: V' (own products only)
-  DenseTermsDev T{};
-  T.n_terms = terms->n_terms;
-  for (int k = 0; k < OMC_MAX_TERMS; ++k) {
-    const bool on = k < terms->n_terms;
-    T.mat[k] = on ? terms->mat[k] : nullptr;
-    T.rhs[k] = on ? terms->rhs[k] : nullptr;
-    T.scale[k] = on ? terms->scale[k] : nullptr;
-  }
-  T.diag_chain = nullptr;
-  // b_c into x_out, W = V' B  (all chains: one GEMM; [C][p] row-major = column-major p x C)
-  hipLaunchKernelGGL(k_dense_rhs, dim3(gx(p), (unsigned)C), dim3(256), 0, ctx->stream, T, p, C, rhs_chain, ld_rhs, x_out, ld_x);
-  OMC_HIP_CHECK(hipGetLastError());
-  const double one = 1.0, zero = 0.0;
-  if (own) {
-    const unsigned tg = (unsigned)((p + 31) / 32);
-    hipLaunchKernelGGL(k_transpose_sq, dim3(tg, tg), dim3(256), 0, ctx->stream, p, V, Vt);
-    OMC_HIP_CHECK(hipGetLastError());
-    st = omc_dgemm_small(ctx, (int)p, (int)C, Vt, p, x_out, ld_x, (int)p, nullptr, 0, nullptr, 0, 0, 0, nullptr, W, p, nullptr,
-                         SPECTRAL_KSPLIT);
-    if (st != OMC_OK) return st;
-  } else {
-    OMC_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_transpose, rocblas_operation_none, (rocblas_int)p, (rocblas_int)C, (rocblas_int)p,
-                                 &one, V, (rocblas_int)p, x_out, (rocblas_int)ld_x, &zero, W, (rocblas_int)p));
-  }
-  hipLaunchKernelGGL(k_spectral_scale, dim3((unsigned)C), dim3(256), 0, ctx->stream, T, (int)k_mat, p, C, ev, ctx->chain_offset,
-                     omc_make_key(ctx->seed, draw_index, OMC_RNG_NORMAL), z_inject, ld_z, W, p, mean_out ? Mw : nullptr, p,
-                     logdet_out, ctx->d_bad_chain);
-  OMC_HIP_CHECK(hipGetLastError());
-  if (own) {
-    st = omc_dgemm_small(ctx, (int)p, (int)C, V, p, W, p, (int)p, nullptr, 0, nullptr, 0, 0, 0, nullptr, x_out, ld_x, nullptr,
-                         SPECTRAL_KSPLIT);
-    if (st != OMC_OK || !mean_out) return st;
-    return omc_dgemm_small(ctx, (int)p, (int)C, V, p, Mw, p, (int)p, nullptr, 0, nullptr, 0, 0, 0, nullptr, mean_out, ld_mean, nullptr,
-                           SPECTRAL_KSPLIT);
-  }
-  OMC_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_none, (rocblas_int)p, (rocblas_int)C, (rocblas_int)p, &one,
-                               V, (rocblas_int)p, W, (rocblas_int)p, &zero, x_out, (rocblas_int)ld_x));
-  if (mean_out)
-    OMC_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_none, (rocblas_int)p, (rocblas_int)C, (rocblas_int)p, &one,
-                                 V, (rocblas_int)p, Mw, (rocblas_int)p, &zero, mean_out, (rocblas_int)ld_mean));
-  return OMC_OK;
-}
-
-// X is [n][p] row-major = column-major p x n (lda = p).
-omc_status omc_gram(omc_ctx* ctx, int64_t n, int64_t p, const double* X, const double* w, double* G_out) {
-  if (!ctx || n < 1 || p < 1 || !X || !G_out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  if (!ctx->gram_use_rocblas && p <= 46340) return omc_gram_mfma_launch(ctx, n, p, X, w, G_out);  // own fp64 MFMA kernel (omc_gram.hip)
-  omc_status st = omc_ensure_blas(ctx);
-  if (st != OMC_OK) return st;
-  const double* B = X;
-  if (w) {
-    st = omc_ensure_bytes(ctx, (void**)&ctx->dense_tmp, &ctx->dense_tmp_bytes, (size_t)n * p * sizeof(double));
-    if (st != OMC_OK) return st;
-    hipLaunchKernelGGL(k_scale_rows, dim3(gx(n * p)), dim3(256), 0, ctx->stream, n, p, X, w, ctx->dense_tmp);
-    OMC_HIP_CHECK(hipGetLastError());
-    B = ctx->dense_tmp;
-  }
-  const double one = 1.0, zero = 0.0;
-  OMC_BLAS_CHECK(rocblas_dgemm((rocblas_handle)ctx->blas, rocblas_operation_none, rocblas_operation_transpose,
-                               (rocblas_int)p, (rocblas_int)p, (rocblas_int)n, &one, X, (rocblas_int)p, B,
-                               (rocblas_int)p, &zero, G_out, (rocblas_int)p));
-  return OMC_OK;
-}
-
-omc_status omc_design_rhs(omc_ctx* ctx, int64_t n, int64_t p, const double* X, const double* w, const double* y,
-                          double* out) {
-  if (!ctx || n < 1 || p < 1 || !X || !y || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  omc_status st = omc_ensure_blas(ctx);
-  if (st != OMC_OK) return st;
-  const double* v = y;
-  if (w) {
-    st = omc_ensure_bytes(ctx, (void**)&ctx->dense_tmp, &ctx->dense_tmp_bytes, (size_t)n * sizeof(double));
-    if (st != OMC_OK) return st;
-    hipLaunchKernelGGL(k_scale_rows, dim3(gx(n)), dim3(256), 0, ctx->stream, n, (int64_t)1, y, w, ctx->dense_tmp);
-    OMC_HIP_CHECK(hipGetLastError());
-    v = ctx->dense_tmp;
-  }
-  const double one = 1.0, zero = 0.0;
-  // out = A v with A = column-major p x n
-  OMC_BLAS_CHECK(rocblas_dgemv((rocblas_handle)ctx->blas, rocblas_operation_none, (rocblas_int)p, (rocblas_int)n, &one, X,
-                               (rocblas_int)p, v, 1, &zero, out, 1));
-  return OMC_OK;
-}
-
-// out[c][i] = sum_s part[s][c][i]  (slices of a long contraction, added in slice order: deterministic)
-__global__ void __launch_bounds__(256) k_sum_slices(int64_t n, int64_t C, int S, const double* __restrict__ part, double* __restrict__ out,
-                                                    int64_t ld_out) {
-  const int64_t c = blockIdx.y;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    double acc = 0.0;
-    for (int s = 0; s < S; ++s) acc += part[((int64_t)s * C + c) * n + i];
-    out[c * ld_out + i] = acc;
-  }
-}
-
-omc_status omc_design_predict(omc_ctx* ctx, int64_t n, int64_t p, const double* X, const double* beta, int64_t ld_beta,
-                              double* fitted, int64_t ld_fitted) {
-  if (!ctx || n < 1 || p < 1 || !X || !beta || !fitted || ld_beta < p || ld_fitted < n) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  omc_status st = omc_ensure_blas(ctx);
-  if (st != OMC_OK) return st;
-  const double one = 1.0, zero = 0.0;
-  // A short output under a long contraction (the transposed use: A'W applied to per-chain vectors of the observation space,
-  // n = parameters, p = observations) leaves the library with a handful of output tiles -- 16 workgroups for 1000 x 256 x
-  // 10 000, 1.6 ms.  Then the contraction is cut into slices (one strided-batched GEMM, a slice per batch entry) and the
-  // slices are added in order.
-  const int64_t C = ctx->n_chains;
-  const int64_t tiles = ((n + 127) / 128) * ((C + 127) / 128);
-  if (p >= 4096 && tiles < 128) {
-    int64_t S = 256 / tiles;
-    if (S > p / 512) S = p / 512;
-    if (S > 64) S = 64;
-    if (S >= 2) {
-      const int64_t ks = p / S;  // the last slice takes the remainder in a call of its own
-      st = omc_ensure_bytes(ctx, (void**)&ctx->slice_buf, &ctx->slice_buf_bytes, (size_t)S * C * n * sizeof(double));
-      if (st != OMC_OK) return st;
-      double* part = ctx->slice_buf;
-      OMC_BLAS_CHECK(rocblas_dgemm_strided_batched((rocblas_handle)ctx->blas, rocblas_operation_transpose, rocblas_operation_none,
-                                                   (rocblas_int)n, (rocblas_int)C, (rocblas_int)ks, &one, X, (rocblas_int)p,
-                                                   (rocblas_stride)ks, beta, (rocblas_int)ld_beta, (rocblas_stride)ks, &zero, part,
-                                                   (rocblas_int)n, (rocblas_stride)(n * C), (rocblas_int)(S - 1)));
-      const int64_t k_last = p - (S - 1) * ks;
-      OMC_BLAS_CHECK(rocblas_dgemm((rocblas_handle)ctx->blas, rocblas_operation_transpose, rocblas_operation_none, (rocblas_int)n,
-                                   (rocblas_int)C, (rocblas_int)k_last, &one, X + (S - 1) * ks, (rocblas_int)p,
-                                   beta + (S - 1) * ks, (rocblas_int)ld_beta, &zero, part + (S - 1) * n * C, (rocblas_int)n));
-      int64_t gx_ = (n + 255) / 256;
-      if (gx_ > 64) gx_ = 64;
-      hipLaunchKernelGGL(k_sum_slices, dim3((unsigned)gx_, (unsigned)C), dim3(256), 0, ctx->stream, n, C, (int)S, part, fitted, ld_fitted);
-      OMC_HIP_CHECK(hipGetLastError());
-      return OMC_OK;
-    }
-  }
-  // fitted (col-major n x C, ld = ld_fitted) = A' (n x p) * Beta (col-major p x C, ld = ld_beta)
-  OMC_BLAS_CHECK(rocblas_dgemm((rocblas_handle)ctx->blas, rocblas_operation_transpose, rocblas_operation_none,
-                               (rocblas_int)n, (rocblas_int)ctx->n_chains, (rocblas_int)p, &one, X, (rocblas_int)p, beta,
-                               (rocblas_int)ld_beta, &zero, fitted, (rocblas_int)ld_fitted));
-  return OMC_OK;
-}
-
-omc_status omc_chain_copy(omc_ctx* ctx, int64_t n, const double* src, int64_t ld_src, double* dst, int64_t ld_dst) {
-  if (!ctx || n < 1 || !src || !dst || ld_src < n || ld_dst < n) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  if (src == dst && ld_src == ld_dst) return OMC_OK;
-  unsigned g = gx(n);
-  if (g > 64) g = 64;
-  hipLaunchKernelGGL(k_copy_rows, dim3(g, (unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, n, src, ld_src, dst, ld_dst);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
-}
-
-omc_status omc_weighted_resid_sq(omc_ctx* ctx, int64_t n, const double* y, const double* fitted, int64_t ld_fitted,
-                                 const double* w, double* out) {
-  if (!ctx || n < 1 || !y || !fitted || ld_fitted < n || !out) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_weighted_resid_sq, dim3((unsigned)ctx->n_chains), dim3(256), 0, ctx->stream, n, y, fitted,
-                     ld_fitted, w, out);
-  OMC_HIP_CHECK(hipGetLastError());
   return OMC_OK;
 }
 

@@ -288,9 +288,9 @@ extern "C" omc_status omc_store_rhat_ess(omc_ctx* ctx, int64_t n_iter, int64_t s
   const size_t n_part = (size_t)G * nl * size, n_b = (size_t)G * 3 * size, n_st = (size_t)D_STATE * size;
   const size_t n_means = short_form ? 0 : (size_t)J * size;
   const size_t bytes = (n_part + n_b + n_st + n_means) * sizeof(double) + (size_t)(tiles + 1) * sizeof(int32_t);
-  omc_status s0 = omc_ensure_bytes(ctx, (void**)&ctx->store_ws, &ctx->store_ws_bytes, bytes);
+  omc_status s0 = omc_ensure(ctx, ctx->store_ws, bytes);
   if (s0 != OMC_OK) return s0;
-  double* part = (double*)ctx->store_ws;
+  double* part = (double*)ctx->store_ws.p;
   double* part_b = part + n_part;
   double* st = part_b + n_b;
   double* means = st + n_st;

@@ -130,7 +130,7 @@ extern "C" omc_status omc_gram_mfma_launch(omc_ctx* ctx, int64_t n, int64_t p, c
   int64_t kchunk = (n + splits - 1) / splits;
   kchunk = (kchunk + GR_BK - 1) / GR_BK * GR_BK;
   splits = (int)((n + kchunk - 1) / kchunk);
-  omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->dense_tmp, &ctx->dense_tmp_bytes, (size_t)splits * p * p * sizeof(double));
+  omc_status st = omc_ensure(ctx, ctx->dense_tmp, (size_t)splits * p * p * sizeof(double));
   if (st != OMC_OK) return st;
   hipLaunchKernelGGL(k_gram_mfma, dim3((unsigned)pairs, (unsigned)splits), dim3(256), 0, ctx->stream, n, (int)p, X, w,
                      ctx->dense_tmp, ntile, kchunk);

@@ -183,9 +183,9 @@ extern "C" omc_status omc_store_hdi(omc_ctx* ctx, int64_t n_iter, int64_t size, 
   const int64_t n_col_max = Kc * CC;
   const int64_t n_st = (P + RANK_G_TS - 1) / RANK_G_TS, n_et_max = (Kc + RANK_G_TE - 1) / RANK_G_TE;
   if (n_st * n_et_max * CC > 0x7fffffffLL || n_col_max * n_slices > 0x7fffffffLL) return OMC_INVALID_ARG;
-  omc_status st = omc_ensure_bytes(ctx, &ctx->rank_ws, &ctx->rank_ws_bytes, RANK_HEAD + (size_t)n_col_max * per_col + 64);
+  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (size_t)n_col_max * per_col + 64);
   if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws;
+  char* ws = (char*)ctx->rank_ws.p;
   uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
   int64_t* n_valid = (int64_t*)(keys + (size_t)n_col_max * P);
   uint64_t* part = (uint64_t*)(n_valid + n_col_max);

@@ -198,9 +198,9 @@ __global__ void k_hist_minmax_join(int64_t cols, int parts, const double* __rest
 // seen them (also omc_hist2d.hip)
 omc_status omc_hist_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64_t size, const double* edges, int64_t edge_rows, int n_bins,
                           int32_t got[2]) {
-  omc_status st = omc_ensure_bytes(ctx, &ctx->store_ws, &ctx->store_ws_bytes, 64);
+  omc_status st = omc_ensure(ctx, ctx->store_ws, 64);
   if (st != OMC_OK) return st;
-  int32_t* words = (int32_t*)ctx->store_ws;
+  int32_t* words = (int32_t*)ctx->store_ws.p;
   OMC_HIP_CHECK(hipMemsetAsync(words, 0, 2 * sizeof(int32_t), ctx->stream));
   omc_store_check_index_launch(ctx, idx, n_idx, size, nullptr, 0, 0, words);
   const int64_t n = edge_rows * (n_bins + 1);
@@ -237,9 +237,9 @@ extern "C" omc_status omc_store_minmax(omc_ctx* ctx, int64_t n_iter, int64_t siz
   const int64_t cols = batches * n_idx;
   double* part = nullptr;
   if (parts > 1) {
-    st = omc_ensure_bytes(ctx, &ctx->store_ws, &ctx->store_ws_bytes, (size_t)3 * parts * cols * sizeof(double));
+    st = omc_ensure(ctx, ctx->store_ws, (size_t)3 * parts * cols * sizeof(double));
     if (st != OMC_OK) return st;
-    part = (double*)ctx->store_ws;
+    part = (double*)ctx->store_ws.p;
   }
   hipLaunchKernelGGL(k_hist_minmax_part, dim3((unsigned)(tiles * batches), (unsigned)parts), dim3(HIST_THREADS), 0, ctx->stream, v, tiles, slices,
                      (int)(parts == 1), part, min_out, max_out, count_out);

@@ -264,7 +264,7 @@ extern "C" omc_status omc_knot_loop(omc_ctx* ctx, int64_t n, int64_t kmax, const
   if (rows > 10 || lds > 32 * 1024) return OMC_INVALID_ARG;  // the chain's residual lives in registers: n <= 10 240
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const int64_t Cn = ctx->n_chains;
-  omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->rj_tmp, &ctx->rj_tmp_bytes, (size_t)(4 * Cn * kmax) * sizeof(double));
+  omc_status st = omc_ensure(ctx, ctx->rj_tmp, (size_t)(4 * Cn * kmax) * sizeof(double));
   if (st != OMC_OK) return st;
   double* prop = (double*)ctx->rj_tmp;
   hipLaunchKernelGGL(k_knot_propose, dim3((unsigned)((Cn * kmax + 63) / 64)), dim3(64), 0, ctx->stream, Cn, ctx->chain_offset,

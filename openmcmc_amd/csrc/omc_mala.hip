@@ -8,22 +8,8 @@
 // (mh_odds, MhOdds::decide), the counters (mh_count), the pair of normals (mh_normal_pair) and the random walk's move
 // (mh_rw_move); the step's uniform is omc_chain_uniform (omc_common.h).  The kernels keep their own loops, registers and barriers.
 #include <math.h>
-#include <rocblas/rocblas.h>
-#include <rocsolver/rocsolver.h>
 
-#include "omc_common.h"
-
-#define OMC_BLAS_CHECK(expr)                                   \
-  do {                                                         \
-    rocblas_status _s = (expr);                                \
-    if (_s != rocblas_status_success) {                        \
-      omc_set_error(#expr, hipErrorUnknown);                   \
-      return OMC_HIP_ERROR;                                    \
-    }                                                          \
-  } while (0)
-
-omc_status omc_ensure_blas(omc_ctx* ctx);
-omc_status omc_ensure_bytes(omc_ctx* ctx, void** buf, size_t* have, size_t need);
+#include "omc_blas.h"
 
 static unsigned gx(int64_t n) {
   int64_t g = (n + 255) / 256;
@@ -142,7 +128,7 @@ static omc_status mh_workspace(omc_ctx* ctx, int64_t d, MhWork* w) {
   const int64_t C = ctx->n_chains;
   const size_t mat = (size_t)C * d;
   const size_t need = (13 * mat + 4 * (size_t)C) * sizeof(double) + (size_t)C * sizeof(int) + 64;
-  omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->mh_work, &ctx->mh_work_bytes, need);
+  omc_status st = omc_ensure(ctx, ctx->mh_work, need);
   if (st != OMC_OK) return st;
   double* base = ctx->mh_work;
   w->R = base; w->G = base + mat; w->M = base + 2 * mat; w->V = base + 3 * mat; w->XP = base + 4 * mat;
@@ -271,7 +257,7 @@ omc_status omc_dense_cholesky(omc_ctx* ctx, int64_t d, const double* A, double s
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   omc_status st = omc_ensure_blas(ctx);
   if (st != OMC_OK) return st;
-  st = omc_ensure_bytes(ctx, (void**)&ctx->dense_info, &ctx->dense_info_bytes, sizeof(int) * (size_t)(ctx->n_chains > 1 ? ctx->n_chains : 1));
+  st = omc_ensure(ctx, ctx->dense_info, sizeof(int) * (size_t)(ctx->n_chains > 1 ? ctx->n_chains : 1));
   if (st != OMC_OK) return st;
   hipLaunchKernelGGL(k_scale_copy, dim3(gx(d * d)), dim3(256), 0, ctx->stream, d * d, A, scale, L_out);
   OMC_HIP_CHECK(hipGetLastError());
@@ -407,7 +393,7 @@ static void draw_normals(omc_ctx* ctx, int64_t d, uint64_t draw_index, const dou
 static omc_status mala_prepare(omc_ctx* ctx, int64_t d, const double* Q, const double* L, double step) {
   auto& m = ctx->mala;
   if (m.Q == Q && m.L == L && m.step == step && m.d == d && m.prep) return OMC_OK;
-  omc_status st = omc_ensure_bytes(ctx, (void**)&m.prep, &m.prep_bytes, (size_t)5 * d * d * sizeof(double));
+  omc_status st = omc_ensure(ctx, m.prep, (size_t)5 * d * d * sizeof(double));
   if (st != OMC_OK) return st;
   rocblas_handle h = (rocblas_handle)ctx->blas;
   const rocblas_int di = (rocblas_int)d;
@@ -549,7 +535,7 @@ __global__ void __launch_bounds__(256) k_mala_white(int64_t d, int64_t chain_off
 static omc_status white_prepare(omc_ctx* ctx, int64_t d, const double* L, const double* mu) {
   auto& wh = ctx->white;
   if (wh.L == L && wh.mu == mu && wh.d == d && wh.prep) return OMC_OK;
-  omc_status st = omc_ensure_bytes(ctx, (void**)&wh.prep, &wh.prep_bytes, (size_t)(2 * d * d + 2 * d) * sizeof(double));
+  omc_status st = omc_ensure(ctx, wh.prep, (size_t)(2 * d * d + 2 * d) * sizeof(double));
   if (st != OMC_OK) return st;
   rocblas_handle h = (rocblas_handle)ctx->blas;
   const rocblas_int di = (rocblas_int)d;
@@ -578,7 +564,7 @@ static omc_status white_state(omc_ctx* ctx, int64_t d, const double* mu, const d
                               double** a) {
   auto& wh = ctx->white;
   const int64_t C = ctx->n_chains;
-  omc_status st = omc_ensure_bytes(ctx, (void**)&wh.a, &wh.a_bytes, (size_t)C * d * sizeof(double));
+  omc_status st = omc_ensure(ctx, wh.a, (size_t)C * d * sizeof(double));
   if (st != OMC_OK) return st;
   *a = wh.a;
   if (state_is_current && wh.x == x && wh.ld == ld_x) return OMC_OK;
@@ -630,7 +616,7 @@ omc_status omc_mala_run_white(omc_ctx* ctx, int64_t d, const double* mu, const d
   const int64_t KB = OMC_WHITE_RUN_BLOCK;
   if (x_store) {
     // two trajectory buffers: the product of block b runs on the side stream while the steps of block b + 1 run here
-    st = omc_ensure_bytes(ctx, (void**)&ctx->white.traj, &ctx->white.traj_bytes, (size_t)2 * KB * C * d * sizeof(double));
+    st = omc_ensure(ctx, ctx->white.traj, (size_t)2 * KB * C * d * sizeof(double));
     if (st != OMC_OK) return st;
     st = omc_ensure_aux(ctx);
     if (st != OMC_OK) return st;
@@ -692,7 +678,7 @@ omc_status omc_mala_run_white(omc_ctx* ctx, int64_t d, const double* mu, const d
 static omc_status rw_prepare(omc_ctx* ctx, int64_t d, const double* LQ, bool* fresh) {
   auto& rw = ctx->rw;
   if (rw.LQ == LQ && rw.d == d && rw.prep) return OMC_OK;
-  omc_status st = omc_ensure_bytes(ctx, (void**)&rw.prep, &rw.prep_bytes, (size_t)2 * d * d * sizeof(double));
+  omc_status st = omc_ensure(ctx, rw.prep, (size_t)2 * d * d * sizeof(double));
   if (st != OMC_OK) return st;
   lower_pair(ctx, d, LQ, rw.prep);
   rw.LQ = LQ; rw.d = d;
@@ -779,7 +765,7 @@ omc_status omc_rw_step_white(omc_ctx* ctx, int64_t d, const double* mu, const do
   st = rw_prepare(ctx, d, LQ, &fresh);
   if (st != OMC_OK) return st;
   const double* Lt = ctx->rw.prep + d * d;
-  st = omc_ensure_bytes(ctx, (void**)&rww.mu_neg, &rww.mu_bytes, (size_t)2 * d * sizeof(double));
+  st = omc_ensure(ctx, rww.mu_neg, (size_t)2 * d * sizeof(double));
   if (st != OMC_OK) return st;
   double* negLtmu = nullptr;
   if (mu) {  // -L_Q' mu, once per (L_Q, mu)
@@ -793,7 +779,7 @@ omc_status omc_rw_step_white(omc_ctx* ctx, int64_t d, const double* mu, const do
   }
   if (rww.mu != mu) fresh = true;
   rww.mu = mu;
-  st = omc_ensure_bytes(ctx, (void**)&rww.a, &rww.a_bytes, (size_t)C * d * sizeof(double));
+  st = omc_ensure(ctx, rww.a, (size_t)C * d * sizeof(double));
   if (st != OMC_OK) return st;
   double* a = rww.a;
   if (fresh || !(state_is_current && rww.x == x && rww.ld == ld_x)) {  // a = L_Q'(x - mu)

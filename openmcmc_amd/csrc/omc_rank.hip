@@ -173,9 +173,9 @@ extern "C" omc_status omc_store_ranks(omc_ctx* ctx, int64_t n_iter, int64_t size
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const size_t per_elem = (size_t)g.P * sizeof(uint64_t) + sizeof(int32_t);
   const int64_t Kc = rank_chunk(ctx, per_elem, n_idx);
-  omc_status st = omc_ensure_bytes(ctx, &ctx->rank_ws, &ctx->rank_ws_bytes, RANK_HEAD + (size_t)Kc * per_elem + 64);
+  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (size_t)Kc * per_elem + 64);
   if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws;
+  char* ws = (char*)ctx->rank_ws.p;
   uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
   int32_t* flags = (int32_t*)(ws + RANK_HEAD + (size_t)Kc * g.P * sizeof(uint64_t));
   st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size);
@@ -207,9 +207,9 @@ extern "C" omc_status omc_store_rank_diagnostics(omc_ctx* ctx, int64_t n_iter, i
   // per element: keys [P], the four series [N C][4], median and two quantiles, R-hat and ESS of the four series, the flag word
   const size_t per_elem = (size_t)g.P * sizeof(uint64_t) + (size_t)N * C * 4 * sizeof(double) + (3 + 8) * sizeof(double) + sizeof(int32_t);
   const int64_t Kc = rank_chunk(ctx, per_elem, n_idx);
-  omc_status st = omc_ensure_bytes(ctx, &ctx->rank_ws, &ctx->rank_ws_bytes, RANK_HEAD + (size_t)Kc * per_elem + 64);
+  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (size_t)Kc * per_elem + 64);
   if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws;
+  char* ws = (char*)ctx->rank_ws.p;
   uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
   double* series = (double*)(keys + (size_t)Kc * g.P);
   double* stats = series + (size_t)N * C * 4 * Kc;

@@ -794,7 +794,7 @@ omc_status omc_design_resid_sq_batched(omc_ctx* ctx, int64_t n, int64_t kmax, co
     OMC_HIP_CHECK(hipGetLastError());
     return OMC_OK;
   }
-  omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->mh_work, &ctx->mh_work_bytes, (size_t)C * parts * sizeof(double));
+  omc_status st = omc_ensure(ctx, ctx->mh_work, (size_t)C * parts * sizeof(double));
   if (st != OMC_OK) return st;
   hipLaunchKernelGGL(k_design_resid_sq, dim3((unsigned)parts, (unsigned)C), dim3(256), 0, ctx->stream, n, kmax, B, coef,
                      add_chain, add_shared, y, w, ctx->mh_work);
@@ -821,7 +821,7 @@ static omc_status design_gram_launch(omc_ctx* ctx, int64_t n, int64_t kmax, cons
                        resid_chain, count, gram, rhs, B_alt, count_alt, select);
   } else {
     const size_t per = (size_t)(kmax * kmax + kmax);
-    omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->mh_work, &ctx->mh_work_bytes, (size_t)C * parts * per * sizeof(double));
+    omc_status st = omc_ensure(ctx, ctx->mh_work, (size_t)C * parts * per * sizeof(double));
     if (st != OMC_OK) return st;
     double* gp = ctx->mh_work;
     double* rp = rhs ? gp + (size_t)C * parts * kmax * kmax : nullptr;

@@ -370,9 +370,9 @@ omc_status omc_store_quantiles(omc_ctx* ctx, int64_t n_iter, int64_t size, const
   const size_t budget = (size_t)256 << 20;
   int64_t Kc = (int64_t)(budget / per_col) & ~(int64_t)(Q_COLS - 1);
   if (Kc > K) Kc = (K + Q_COLS - 1) & ~(int64_t)(Q_COLS - 1);
-  omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->store_ws, &ctx->store_ws_bytes, (size_t)Kc * per_col + 64 + Q_TARGETS * 8);
+  omc_status st = omc_ensure(ctx, ctx->store_ws, (size_t)Kc * per_col + 64 + Q_TARGETS * 8);
   if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->store_ws;
+  char* ws = (char*)ctx->store_ws.p;
   uint32_t* hist = (uint32_t*)ws;                                   ws += (size_t)Kc * Q_TARGETS * 256 * 4;
   uint64_t* prefix = (uint64_t*)ws;                                 ws += (size_t)Kc * Q_TARGETS * 8;
   int64_t* rank = (int64_t*)ws;                                     ws += (size_t)Kc * Q_TARGETS * 8;

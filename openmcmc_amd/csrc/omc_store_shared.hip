@@ -160,9 +160,9 @@ omc_status omc_store_check_index(omc_ctx* ctx, int32_t* word, const int64_t* idx
                                  int64_t n_b, int64_t size_b) {
   if (!idx_a && !idx_b) return OMC_OK;
   if (!word) {
-    omc_status st = omc_ensure_bytes(ctx, &ctx->store_ws, &ctx->store_ws_bytes, 64);
+    omc_status st = omc_ensure(ctx, ctx->store_ws, 64);
     if (st != OMC_OK) return st;
-    word = (int32_t*)ctx->store_ws;
+    word = (int32_t*)ctx->store_ws.p;
   }
   OMC_HIP_CHECK(hipMemsetAsync(word, 0, sizeof(int32_t), ctx->stream));
   omc_store_check_index_launch(ctx, idx_a, n_a, size_a, idx_b, n_b, size_b, word);
@@ -185,9 +185,9 @@ omc_status omc_col_moments(omc_ctx* ctx, const StoreView& view, double* mean_out
   if (slices < 1) slices = 1;
   if (slices > 1024) slices = 1024;
   const int64_t rpb = (v.R + slices - 1) / slices;
-  omc_status st = omc_ensure_bytes(ctx, &ctx->store_ws, &ctx->store_ws_bytes, (size_t)slices * v.batches * 3 * v.n * sizeof(double));
+  omc_status st = omc_ensure(ctx, ctx->store_ws, (size_t)slices * v.batches * 3 * v.n * sizeof(double));
   if (st != OMC_OK) return st;
-  double* part = (double*)ctx->store_ws;
+  double* part = (double*)ctx->store_ws.p;
   const dim3 grid((unsigned)groups, (unsigned)slices);
   if (v.idx) hipLaunchKernelGGL(k_store_moments_part<true>, grid, dim3(256), 0, ctx->stream, v, tiles, rpb, part);
   else hipLaunchKernelGGL(k_store_moments_part<false>, grid, dim3(256), 0, ctx->stream, v, tiles, rpb, part);

@@ -143,14 +143,13 @@ static bool reentry_descriptor_ok(uint32_t private_size, uint32_t rsrc2, uint32_
 static int g_reentry_ok = -1;  // -1: not probed yet (process-wide: one code object)
 static bool reentry_abi_ok(omc_ctx* ctx) {
   if (g_reentry_ok >= 0) return g_reentry_ok != 0;
-  uint32_t* d = nullptr;
+  omc_buf<uint32_t> d;  // freed on return
   uint32_t h[6] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u};
-  bool ok = hipMalloc(&d, sizeof(h)) == hipSuccess;
+  bool ok = hipMalloc(&d.p, sizeof(h)) == hipSuccess;
   if (ok) {
-    hipLaunchKernelGGL(k_reentry_probe, dim3(1), dim3(64), 0, ctx->stream, d);
+    hipLaunchKernelGGL(k_reentry_probe, dim3(1), dim3(64), 0, ctx->stream, d.p);
     ok = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
          hipStreamSynchronize(ctx->stream) == hipSuccess;
-    hipFree(d);
   }
   ok = ok && reentry_descriptor_ok(h[0], h[1], h[2]) && reentry_descriptor_ok(h[3], h[4], h[5]);
   g_reentry_ok = ok ? 1 : 0;
@@ -435,12 +434,12 @@ static bool launch_seg(omc_ctx* ctx, const TriArgs& A_in) {
       // the Normal-Gamma blocks in device memory for the generic instantiation (stream-ordered copy: the previous launch
       // has read its image by the time this one is written)
       const size_t gb_bytes = sizeof(A.gb), gd_bytes = sizeof(A.gdraw);
-      if (!ctx->d_gamma_tab && hipMalloc(&ctx->d_gamma_tab, gb_bytes + gd_bytes) != hipSuccess) return false;
+      if (!ctx->d_gamma_tab && hipMalloc(&ctx->d_gamma_tab.p, gb_bytes + gd_bytes) != hipSuccess) return false;
       if (hipMemcpyAsync(ctx->d_gamma_tab, A.gb, gb_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return false;
-      if (hipMemcpyAsync((char*)ctx->d_gamma_tab + gb_bytes, A.gdraw, gd_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+      if (hipMemcpyAsync((char*)ctx->d_gamma_tab.p + gb_bytes, A.gdraw, gd_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         return false;
-      A.gb_dev = (const GammaDev*)ctx->d_gamma_tab;
-      A.gdraw_dev = (const unsigned long long*)((char*)ctx->d_gamma_tab + gb_bytes);
+      A.gb_dev = (const GammaDev*)ctx->d_gamma_tab.p;
+      A.gdraw_dev = (const unsigned long long*)((char*)ctx->d_gamma_tab.p + gb_bytes);
     }
     // workgroup-per-chain form: one workgroup per (sweep, chain), or per chain when the workgroups restart themselves
     const int64_t wg_per_chain = A.n_sweeps <= 0 ? 1 : (!A.reenter ? A.n_sweeps : (A.block_sweeps > 0 ? (A.n_sweeps + A.block_sweeps - 1) / A.block_sweeps : 1));
@@ -523,15 +522,8 @@ static omc_status launch_tridiag(omc_ctx* ctx, TriArgs& A) {
     if (!launch_seg_any(ctx, A, seg)) return OMC_INVALID_ARG;
   } else {
     if (!A.x) return OMC_INVALID_ARG;
-    const size_t need = (size_t)A.C * (size_t)n * sizeof(double);
-    if (ctx->workspace_bytes < need) {
-      OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (ctx->workspace) OMC_HIP_CHECK(hipFree(ctx->workspace));
-      ctx->workspace = nullptr;
-      ctx->workspace_bytes = 0;
-      OMC_HIP_CHECK(hipMalloc(&ctx->workspace, need));
-      ctx->workspace_bytes = need;
-    }
+    const omc_status st = omc_ensure(ctx, ctx->workspace, (size_t)A.C * (size_t)n * sizeof(double));
+    if (st != OMC_OK) return st;
     A.work = ctx->workspace;
     const int64_t grid = (A.C + 63) / 64;
     hipLaunchKernelGGL(k_tridiag_serial, dim3((unsigned)grid), dim3(64), 0, ctx->stream, A);
@@ -564,7 +556,7 @@ static omc_status long_chain_draw(omc_ctx* ctx, int64_t n, const omc_tridiag_ter
   const size_t per = 2 * (size_t)n * sizeof(double);
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   {
-    const omc_status st = omc_ensure_bytes(ctx, (void**)&ctx->long_band, &ctx->long_band_bytes, per * OMC_MAX_TERMS);
+    const omc_status st = omc_ensure(ctx, ctx->long_band, per * OMC_MAX_TERMS);
     if (st != OMC_OK) return st;
   }
   for (int k = 0; k < OMC_MAX_TERMS; ++k) {
@@ -653,7 +645,7 @@ omc_status omc_gmrf_sweep(omc_ctx* ctx, int64_t n, const omc_tridiag_terms* term
     const int nt = terms->n_terms;
     const int64_t C = ctx->n_chains;
     {
-      const omc_status st0 = omc_ensure_bytes(ctx, (void**)&ctx->long_quad, &ctx->long_quad_bytes, (size_t)OMC_MAX_TERMS * C * sizeof(double));
+      const omc_status st0 = omc_ensure(ctx, ctx->long_quad, (size_t)OMC_MAX_TERMS * C * sizeof(double));
       if (st0 != OMC_OK) return st0;
     }
     omc_status st = long_chain_draw(ctx, n, terms, rhs_chain, ld_rhs, z_inject, ld_z, draw_index, x_out, ld_x, nullptr, 0, nullptr);
@@ -738,7 +730,7 @@ omc_status omc_gmrf_run(omc_ctx* ctx, int64_t n, const omc_tridiag_terms* terms,
     OMC_HIP_CHECK(hipSetDevice(ctx->device));
     if (!ctx->d_handoff) {
       const size_t bytes = (size_t)C * OMC_HANDOFF_WORDS * sizeof(unsigned long long);
-      OMC_HIP_CHECK(hipMalloc(&ctx->d_handoff, bytes));
+      OMC_HIP_CHECK(hipMalloc(&ctx->d_handoff.p, bytes));
       OMC_HIP_CHECK(hipMemsetAsync(ctx->d_handoff, 0, bytes, ctx->stream));
       ctx->run_epoch = 1;
     }

@@ -60,10 +60,7 @@ template <bool DIAG>
 omc_status omc_trunc_dense_launch(omc_ctx* ctx, int64_t p, const omc_dense_terms* terms, const double* rhs_chain, int64_t ld_rhs,
                                   const double* lower, const double* upper, const double* u_inject, int64_t ld_u,
                                   uint64_t draw_index, double* x, int64_t ld_x) {
-  omc_dense_terms T{};  // (the kernel reads all OMC_MAX_TERMS slots: those beyond n_terms are NULL)
-  T.n_terms = terms->n_terms;
-  for (int k = 0; k < terms->n_terms; ++k) { T.mat[k] = terms->mat[k]; T.rhs[k] = terms->rhs[k]; T.scale[k] = terms->scale[k]; }
-  T.diag_chain = terms->diag_chain;
+  const omc_dense_terms T = omc_dense_terms_clean(terms, true);  // (the kernel reads all OMC_MAX_TERMS slots)
   return omc_launch(ctx, k_dense_gibbs_truncated<DIAG>, dim3((unsigned)ctx->n_chains), dim3(64), (size_t)p * sizeof(double),
                     ctx->n_chains, ctx->chain_offset, p, T, rhs_chain, ld_rhs, lower, upper, u_inject, ld_u,
                     omc_make_key(ctx->seed, draw_index, OMC_RNG_UNIFORM), x, ld_x, ctx->d_bad_chain);
