@@ -1096,6 +1096,47 @@ omc_status omc_store_reduce(omc_ctx* ctx, int64_t n_iter, int64_t size, const do
 omc_status omc_store_autocorr(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                               int64_t max_lag, int32_t per_chain, int32_t normalize, double* acf_out, double* tau_out,
                               int32_t* window_out, double* mean_out);
+/* Linear maps and posterior-predictive draws of the same store: m numbers per stored state (iteration, chain), each a linear
+ * combination of the selected elements of its row -- the fitted curve A beta on a grid, a set of contrasts or regional totals, the
+ * predictor of a reversible-jump model summed over its live components, the replicates y_rep = A beta + eps / sqrt(tau) of a
+ * posterior-predictive check: the loop over MCMC.store[...] of the reference that calls LinearCombination.predictor / Normal.rvs per
+ * stored draw.  The result is shaped like a store entry [n_iter][C][m], so every other summary of the store applies to it.
+ *   store, idx, n_idx and the NULL convention as omc_store_reduce (order kept, repeats allowed, n_idx may exceed size); an index
+ *   outside [0, size) is OMC_INVALID_ARG, found on the device before anything reads through it; out is then untouched.  Selection
+ *   position k = 0 .. n_idx - 1 is element idx[k] of the row (k itself without an index) with value x[k].
+ *   W         (device) [m][n_idx], row stride ld_w >= n_idx;   offset (device) [m] or NULL
+ *   base      (device) [n_iter][C][m] or NULL; may be out itself (accumulate in place: an element is read and written by the same thread)
+ *   prec      (device) [n_iter][C][prec_size], prec_size 0 (no noise; prec NULL), 1 or m;   z_inject (device) [n_iter][C][m] or NULL
+ *   out       (device) [n_iter][C][m]:
+ *     out[it][c][j] = base[it][c][j] + offset[j] + sum_k W[j][k] x[k]   (+ z[it][c][j] / sqrt(prec[it][c][j or 0]) with prec_size > 0)
+ *   NaN.  omit_nan != 0: a NaN x[k] is left out -- its term is 0 whatever W[j][k] is (np.nansum of the terms; the NaN padding of a
+ *     variable-size parameter means "component absent"); a row with nothing left gives base + offset.  omit_nan == 0: plain IEEE, as
+ *     store2d[:, idx] @ W.T in numpy: a NaN among the selected elements of a row makes all m outputs of that row NaN, inf * 0 is NaN.
+ *     Rows, columns and positions that pad a tile never reach a written output.
+ *   Noise.  z is z_inject where given (the library's convention for path-wise replays), else element j of the chain's normal
+ *     stream (purpose OMC_RNG_NORMAL, global chain chain_id_offset + c) at draw index (1 << 41) + it + (replicate << 44),
+ *     replicate 0 .. 15: a pure function of (seed, global chain, it, j, replicate), whatever the launch geometry and however the
+ *     chains are sharded.  One IEEE square root and one IEEE division per term; a precision that is not positive gives what IEEE
+ *     gives (inf, NaN).
+ *   OMC_INVALID_ARG, with a text in omc_last_error: ctx, store, W or out NULL, n_iter < 1, size < 1, m < 1, n_idx < 1 (or no index
+ *     and n_idx != size), ld_w < n_idx, prec_size not 0, 1 or m, prec and prec_size not given together, z_inject without prec,
+ *     replicate > 15, an index outside [0, size), more than 2^31 - 1 tiles of 64 rows or 65535 tiles of 128 outputs.
+ * Guarantees.  The contraction of a row is never split across workgroups and uses no atomics.  The order in which a row's terms
+ * are added depends on (n_idx, m) and the kernel's constants only -- not on the row's position, on R = n_iter C, on C or on the
+ * row's alignment.  So repeated calls are bit-equal, and a row's outputs are bit-equal however the rows are regrouped: fewer
+ * iterations, or chains sharded over contexts (the noise included).  Error of the linear part:
+ *   |out - exact| <= (n_idx + 2) 2^-53 (|base| + |offset| + sum_k |W[j][k] x[k]|),
+ * the bound of any order of additions of rounded or fused products (the form omc_store_reduce and omc_store_autocorr state).
+ * How: one kernel family on v_mfma_f64_16x16x4_f64.  A workgroup owns 64 rows and 128 output columns (with m <= 64: 128 rows and
+ * 64 columns, the same additions in the same order) and walks the whole contraction in slabs of 32 positions; rows and the W slab are staged in LDS (16-byte loads along the row without an index when
+ * size is even and store 16-byte aligned, else 8-byte loads, gathered through the index where there is one; NaN zeroed on the
+ * way in), the next slab is fetched under the multiplications, blocks of 16 columns without a real output are skipped.  With
+ * m <= 128 the store is read exactly once; wider m takes a second grid dimension over column tiles, each reading the store.
+ * No scratch.  Workspace: the word of the index check (store_ws); with an index the host reads that word back.  Runs on the
+ * context's stream.                                                                                                            */
+omc_status omc_store_project(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                             int64_t m, const double* W, int64_t ld_w, const double* offset, const double* base, int32_t omit_nan,
+                             const double* prec, int64_t prec_size, const double* z_inject, uint64_t replicate, double* out);
 /* Thinned copy of the store for a thinned gather: out[j] = store[first + j * every] (slabs of C * size doubles),
  * j = 0 .. ceil((n_iter - first) / every) - 1 (that count is left in *n_out when n_out is not NULL, host).           */
 omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int64_t first, int64_t every,

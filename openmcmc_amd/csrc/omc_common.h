@@ -251,6 +251,8 @@ __device__ __forceinline__ void omc_lds_barrier() { asm volatile("s_waitcnt lgkm
 //                   bits  0-39  sweep draw t * n_samplers + position (sweeps < 2^32, positions < 2^8; the fused run of
 //                               omc_tridiag.hip makes the same numbers: its sweep draw plus the block's position)
 //                   bit  40     prior draw of the start value: (1 << 40) + position (mcmc.py)
+//                   bit  41     posterior-predictive noise of stored iteration `it`: (1 << 41) + it, the replicate 0 .. 15 in
+//                               `sub` (omc_store_project; it < 2^32)
 //                   bits 44-47  `sub`, several draws of one purpose under one draw index (Gamma.rvs, Normal columns)
 //   block         ctr0: position within the draw.  Element e of a vector lives in half e & 1 of block sub + (e >> 1)
 //                 (omc_elem_uniform, omc_elem_normal).  A Gamma(a) draw reads blocks 0 .. OMC_GAMMA_BLOCKS - 1; mixture

@@ -1502,6 +1502,65 @@ class Engine:
         check(st)
         return acf, tau, window, mean
 
+    def store_project(self, store, W, index=None, offset=None, base=None, omit_nan=True, prec=None, z=None, replicate=0, out=None):
+        """Linear maps of a device store (n_iter, C, size) over the selected elements of every row, on the device
+        (omc_store_project): the device tensor (n_iter, C, m) with, for x the element at selection position k of row (it, c),
+        out[it, c, j] = base[it, c, j] + offset[j] + sum_k W[j, k] * x[k] -- store2d[:, index] @ W.T.  W (m, n_idx) and offset (m,)
+        are host arrays or device tensors; a 1-D W counts as one output, and the leading columns of a wider fp64 device matrix
+        are read where they lie (ld_w = its row stride).  base, prec and z are device stores (n_iter, C, m) --
+        prec (n_iter, C, 1) or (n_iter, C, m) -- of the same iterations.  With prec, z / sqrt(prec) is added: z the injected
+        normals, else element j of the chain's normal stream at draw index (1 << 41) + it + (replicate << 44), replicate
+        0 .. 15 -- the same numbers however the chains are sharded over engines.  omit_nan leaves NaN elements out (their terms
+        are 0: np.nansum; a row with nothing left gives base + offset); without it IEEE rules hold as in numpy's matmul.  out: the
+        tensor to write, which may be base itself (accumulate in place).  Within (n_idx + 2) 2^-53 (|base| + |offset| +
+        sum|terms|) of the exact value; repeated calls, and the same rows in a store of fewer iterations or chains, are
+        bit-equal."""
+        torch = _torch()
+        n_iter, size = self._store_shape(store)
+        idx, n = self._store_index(index, size)
+        if (isinstance(W, torch.Tensor) and W.is_cuda and W.dtype is torch.float64 and W.dim() == 2 and W.shape[0] > 1
+                and W.stride(1) == 1 and W.stride(0) >= W.shape[1]):
+            Wt = W  # rows of a wider device matrix are read where they lie (ld_w = the row stride)
+        else:
+            Wt = self.to_device(W)
+        if Wt.dim() == 1:
+            Wt = Wt.reshape(1, -1)
+        if Wt.dim() != 2 or Wt.shape[0] < 1 or Wt.shape[1] != n:
+            raise ValueError(f"W must be (m, {n}): one row per output, one column per selected element, got shape {tuple(Wt.shape)}")
+        m = Wt.shape[0]
+        off = None
+        if offset is not None:
+            off = self.to_device(offset).reshape(-1)
+            if off.numel() != m:
+                raise ValueError(f"offset must hold one value per output ({m})")
+        sizes = {"base": (m,), "prec": (1, m), "z": (m,)}
+        for what, t in (("base", base), ("prec", prec), ("z", z)):
+            if t is None:
+                continue
+            n_it, sz = self._store_shape(t)
+            if n_it != n_iter:
+                raise ValueError(f"{what} holds {n_it} iterations, the store {n_iter}")
+            if sz not in sizes[what]:
+                raise ValueError(f"{what} must hold {' or '.join(str(s) for s in sizes[what])} values per draw, got {sz}")
+        if z is not None and prec is None:
+            raise ValueError("z needs prec")
+        if out is None:
+            out = self.empty(n_iter, self.n_chains, m)
+        elif self._store_shape(out) != (n_iter, m):
+            raise ValueError(f"out must be ({n_iter}, {self.n_chains}, {m})")
+        elif out.data_ptr() == store.data_ptr():
+            raise ValueError("out must not be the store the map reads (other rows of it are still being read)")
+        replicate = int(replicate)
+        if not 0 <= replicate <= 15:
+            raise ValueError("replicate must lie in 0 .. 15")
+        st = lib.omc_store_project(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, m, self._p(Wt), Wt.stride(0), self._p(off),
+                                   self._p(base), int(bool(omit_nan)), self._p(prec), 0 if prec is None else prec.shape[2],
+                                   self._p(z), replicate, self._p(out))
+        if st == _abi.INVALID_ARG:  # the library says which argument
+            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
+        check(st)
+        return out
+
     def store_thin(self, store, every, first=0):
         """store[first::every] of a device store (n_iter, C, ...) as a packed device tensor (one launch)."""
         if store.dim() < 2 or store.shape[1] != self.n_chains or not store.is_contiguous():

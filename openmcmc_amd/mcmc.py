@@ -469,6 +469,142 @@ class MCMC:
             self._derived.add(name)
         return out.cpu().numpy()
 
+    def project(self, key, matrix, index=None, offset=None, base=None, omit_nan=True, name=None, noise_precision=None, replicate=0):
+        """Linear maps of store[key], computed on the device (one read of the store for up to 128 outputs, no gather): every
+        stored state (iteration, chain) gives m numbers, out[it, c, j] = base[it, c, j] + offset[j] + sum_k matrix[j, k] * x[k]
+        with x the elements at the selected positions of its row -- the fitted curve A beta at the observations or on a new grid,
+        a set of contrasts or regional totals, the predictor of a variable-size parameter summed over its live components.  A
+        host array (n_iter, C, m), the store's own layout.  matrix is (m, n_idx), host array or device tensor, a 1-D matrix one
+        output; offset holds m values.  index selects elements (in that order, repeats allowed); a 2-D entry ("log_post")
+        counts as one element.  base and noise_precision are store keys: base an entry of m elements that is added,
+        noise_precision an entry of 1 or m elements tau, with which z / sqrt(tau) is added for z ~ N(0, 1) -- the
+        posterior-predictive replicate y_rep = A beta + eps / sqrt(tau) of every stored draw.  z is element j of the chain's own
+        normal stream under a draw index no sweep uses, one stream per replicate 0 .. 15: the same seed gives the same
+        replicates, also when the chains are sharded over GPUs.  omit_nan: NaN elements (the padding of variable-size
+        parameters: "component absent") are left out, their terms are 0, and a row with nothing left gives base + offset;
+        False follows IEEE as numpy's matmul does (a NaN element makes the row's m outputs NaN).  The linear part is within
+        (n_idx + 2) 2^-53 (|base| + |offset| + sum|terms|) of the exact value.
+        With name the result stays on the device as store[name], shaped (n_iter, C, m), and None is returned (the entry can be
+        as large as the store: no silent transfer): `summary`, `quantiles`, `hdi`, `diagnostics`, `simultaneous_band`,
+        `histogram` ... accept it as a key (pointwise intervals and a simultaneous band of a fitted curve, R-hat and ESS of a
+        prediction), and `collect()` / `gather()` carry it as a vector parameter (C, m, n_iter).  base=name with the same name
+        accumulates in place, the way to add the blocks of one mean: project("beta", A, name="f"); project("gamma", B, base="f",
+        name="f").  A projected entry describes the store AT THE TIME OF THE CALL; a name may be made again, but a name that is
+        a store entry of the run raises ValueError.  Under a sharded multi-GPU run every rank must make the same names before
+        `gather`."""
+        self._whole_store_on_device("project")
+        if name is not None and name in self.store and name not in self._derived:
+            raise ValueError(f"{name!r} is a store entry of the run: choose another name for the projected quantity")
+        if name is not None and base == name and key == name:
+            raise ValueError(f"{name!r} cannot be accumulated into while it is the entry the map reads")
+        t = self._store_3d(key)
+        b = None if base is None else self._store_3d(base)
+        prec = None if noise_precision is None else self._store_3d(noise_precision)
+        out = b if (base is not None and base == name) else None  # accumulate in place
+        out = self.engine.store_project(t, matrix, index=index, offset=offset, base=b, omit_nan=omit_nan, prec=prec,
+                                        replicate=replicate, out=out)
+        if name is None:
+            return out.cpu().numpy()
+        self.store[name] = out
+        self._derived.add(name)
+        return None
+
+    def _predictive_precision(self, dist, m):
+        """store key of the noise precision of a Normal response of m elements: an entry of 1 or m elements"""
+        from openmcmc_amd.parameter import Identity
+
+        prec = dist.precision
+        if isinstance(prec, Identity):
+            scalar, diag = prec.form, None
+        elif isinstance(prec, ScaledMatrix):
+            M = self.state[prec.matrix]
+            M = sparse.csr_matrix(M) if not sparse.issparse(M) else M.tocsr()
+            diag = np.asarray(M.diagonal(), dtype=np.float64)
+            if M.shape != (m, m) or (M - sparse.diags(diag)).count_nonzero():
+                raise NotImplementedError(f"posterior_predictive: the precision matrix {prec.matrix!r} is not diagonal")
+            scalar = prec.scalar
+            if np.all(diag == 1.0):
+                diag = None
+        else:
+            raise NotImplementedError(f"posterior_predictive: a precision of type {type(prec).__name__}")
+        if scalar in self.store:
+            t = self._store_3d(scalar)
+            key = scalar
+        else:  # a constant of the state, broadcast to a device entry once
+            key = f"_precision_{scalar}"
+            if key not in self._derived:
+                v = self.state[scalar]
+                if sparse.issparse(v) or is_chain(v):
+                    raise NotImplementedError(f"posterior_predictive: the precision {scalar!r} is neither stored nor a constant vector")
+                v = np.asarray(v, dtype=np.float64)
+                if v.size != max(v.shape, default=1):
+                    raise NotImplementedError(f"posterior_predictive: the precision {scalar!r} is a matrix")
+                self.store[key] = self.engine.to_device(v.reshape(-1)).expand(self._n_dev, self.n_chains, v.size).contiguous()
+                self._derived.add(key)
+            t = self.store[key]
+        if t.shape[2] not in (1, m):
+            raise NotImplementedError(f"posterior_predictive: the precision {scalar!r} holds {t.shape[2]} values, the response {m}")
+        if diag is None:
+            return key
+        key = f"_precision_of_{dist.response}"  # the scalar times the matrix's diagonal, made anew by every call
+        self.store[key] = (t * self.engine.to_device(diag)).contiguous()
+        self._derived.add(key)
+        return key
+
+    def posterior_predictive(self, response, name=None, replicate=0, noise=True):
+        """Posterior-predictive replicates of a Normal response of the model, one per stored draw, computed on the device:
+        y_rep = mean + eps / sqrt(precision) with the mean and the precision of self.model[response] evaluated at every stored
+        state -- what Normal.rvs of the reference gives in a loop over the store.  noise=False gives the fitted values (the
+        mean alone).  Supported: a mean that is a stored parameter (Identity) or a LinearCombination of stored parameters with
+        shared design matrices in the state (dense or scipy-sparse, densified); a precision that is a stored or constant scalar
+        or vector of the response's length (Identity), or a scalar times a diagonal matrix (ScaledMatrix).  Anything else
+        raises NotImplementedError naming the part: per-chain designs, LinearCombinationWithTransform, precisions that are
+        not diagonal, a term that is not in the store.  name, replicate, the layout (n_iter, C, m), the NaN rule (padding
+        left out) and the sharding remark as `project`, which does the work.  A constant precision is
+        broadcast once to the store entry "_precision_<its name>", a scalar times a diagonal to "_precision_of_<response>"."""
+        from openmcmc_amd.distribution.location_scale import Normal
+        from openmcmc_amd.parameter import Identity, LinearCombinationWithTransform
+
+        self._whole_store_on_device("posterior_predictive")
+        dist = self.model[response]
+        if type(dist) is not Normal:
+            raise NotImplementedError(f"posterior_predictive: a response of type {type(dist).__name__}")
+        mean = dist.mean
+        if isinstance(mean, Identity):
+            if mean.form not in self.store:
+                raise NotImplementedError(f"posterior_predictive: the mean {mean.form!r} is not in the store")
+            blocks = [(mean.form, None)]
+        elif isinstance(mean, LinearCombinationWithTransform):
+            raise NotImplementedError("posterior_predictive: a mean of type LinearCombinationWithTransform")
+        elif isinstance(mean, LinearCombination):
+            blocks = []
+            for prm, prefactor in mean.form.items():
+                if prm not in self.store:
+                    raise NotImplementedError(f"posterior_predictive: the term {prm!r} is not in the store")
+                A = self.state[prefactor]
+                if is_chain(A):
+                    raise NotImplementedError(f"posterior_predictive: the design matrix {prefactor!r} is per chain")
+                blocks.append((prm, A.toarray() if sparse.issparse(A) else np.asarray(A, dtype=np.float64)))
+        else:
+            raise NotImplementedError(f"posterior_predictive: a mean of type {type(mean).__name__}")
+        identity = blocks[0][1] is None
+        m = self._store_3d(blocks[0][0]).shape[2] if identity else blocks[0][1].shape[0]
+        prec_key = self._predictive_precision(dist, m) if noise else None
+        work = name if name is not None else f"_predictive_of_{response}"
+        if work in self.store and work not in self._derived:
+            raise ValueError(f"{work!r} is a store entry of the run: choose another name for the replicates")
+        if identity:  # the entry itself is the mean: it goes in as the base of a map with zero weights on its first element
+            # (NaN padding stays NaN as the base carries it; an infinite first element would make its draw's row NaN by inf * 0)
+            self.project(blocks[0][0], np.zeros((m, 1)), index=[0], base=blocks[0][0], name=work, noise_precision=prec_key,
+                         replicate=replicate)
+        for i, (prm, A) in enumerate(blocks if not identity else []):  # the noise goes in with the last block
+            last = i == len(blocks) - 1
+            self.project(prm, A, base=work if i else None, name=work, noise_precision=prec_key if last else None, replicate=replicate)
+        if name is not None:
+            return None
+        self._derived.discard(work)
+        return self.store.pop(work).cpu().numpy()
+
     def simultaneous_band(self, key, prob=0.95, index=None):
         """A simultaneous credible band of the selected elements of store[key], computed on the device (two reads of the
         store, no gather): a dict of host arrays "lower", "upper", "mean", "sd" of shape (n_idx,) and "critical" (a float).
