@@ -1137,6 +1137,72 @@ omc_status omc_store_autocorr(omc_ctx* ctx, int64_t n_iter, int64_t size, const 
 omc_status omc_store_project(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                              int64_t m, const double* W, int64_t ld_w, const double* offset, const double* base, int32_t omit_nan,
                              const double* prec, int64_t prec_size, const double* z_inject, uint64_t replicate, double* out);
+/* Column summaries of the pointwise Normal log-density of the same store: what WAIC needs of a fitted model, and the pointwise
+ * entry itself -- the loop over MCMC.store[...] of the reference that calls Normal.log_p(..., by_observation=True) per stored draw
+ * (distribution/location_scale.py:145-166), reduced over the draws while the entry is read.
+ *   store is a MEAN entry [n_iter][C][size] (a stored parameter, or what omc_store_project made); idx, n_idx and the NULL
+ *   convention as omc_store_reduce (order kept, repeats allowed); an index outside [0, size) is OMC_INVALID_ARG, found on the
+ *   device before anything reads through it.  Selection position k is element idx[k] of a row (k itself without an index).
+ *   y     (device) [n_idx], aligned with the selection
+ *   prec  (device) [n_iter][C][prec_size], prec_size 1 or n_idx
+ * With S = n_iter C >= 2 rows, c = 0.5 log(2 pi) rounded to fp64, and for row s and position k the element x and precision tau:
+ *     h  = 0.5 log(tau) - c            (one fused multiply-add; with prec_size == 1 one logarithm per ROW, not per element)
+ *     r  = y[k] - x                    (one IEEE subtraction)
+ *     ll = h - (0.5 tau r) r           (0.5 tau exact, one rounded product, one fused multiply-add)
+ *   lse_out  [n_idx]  log sum_s exp(ll)         mean_out [n_idx]  the mean of ll over s
+ *   var_out  [n_idx]  its unbiased variance (divisor S - 1)
+ *   ll_out   [n_iter][C][n_idx]  ll itself, in the store's layout (whatever IEEE gives)
+ *   Any output may be NULL, not all.  A column that holds an ll that is not finite -- a NaN or infinite element, a precision that
+ *   is not positive and finite -- gives NaN in lse, mean and var; no other column is affected.
+ *   OMC_INVALID_ARG, with a text in omc_last_error and every output untouched: ctx, store, y or prec NULL, S < 2, size < 1,
+ *     n_idx < 1 (or no index and n_idx != size), prec_size not 1 or n_idx, every output NULL, an index outside [0, size).
+ * How: one read of the entry, 8 bytes written per element only with ll_out.  A workgroup owns 32 adjacent selection positions
+ * and a slice of the rows (about 2048 workgroups, no slice shorter than 256 rows, at most 1024 slices: omc_store_moments' rule);
+ * lanes run along the row -- 16-byte loads without an index where size is even and store 16-byte aligned, else 8-byte loads -- and
+ * 16 row lanes walk down it.  A lane carries the running maximum M and the rescaled sum s (one exp per element) next to Welford's
+ * update; lanes and slices are joined in a fixed order, (M, s) pairs by M = max and one rescaling, moments by Chan's update.  No
+ * atomics: slices and order are functions of the shape alone, so repeated calls are bit-equal (and the two load forms give the
+ * same bits).  Error of lse: with E = max_s (|0.5 log tau| + c + 0.5 tau r^2) and u = 2^-53, within 4 u E + (K + 4) u + u |lse| of the
+ * exact value, K = 2 ((L - 1) + (min(16, rows) - 1) + (slices - 1)) <= 2 (S - 1) the roundings a term passes through, rows the
+ * rows of a slice and L = ceil(rows / 16).  No scratch.  Workspace (store_ws): 40 n_idx bytes per slice, 8 S bytes with
+ * prec_size == 1, the word of the index check; with an index the host reads that word back.  Runs on the context's stream.     */
+omc_status omc_store_loglik(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                            const double* y, const double* prec, int64_t prec_size, double* lse_out, double* mean_out,
+                            double* var_out, double* ll_out);
+/* Pareto-smoothed importance sampling leave-one-out (PSIS-LOO; Vehtari, Simpson, Gelman, Yao, Gabry 2024 -- what az.loo reports)
+ * per selected column of the same store: the expected log predictive density of the observation with itself left out, and the
+ * Pareto k of its importance ratios.  store, idx, n_idx as omc_store_loglik.  With y == NULL (then prec NULL) store is an entry
+ * of pointwise log-likelihoods read as it lies; else it is a mean entry and ll is computed on load from y, prec, prec_size as
+ * omc_store_loglik computes it (the same inline function: the two routes are bit-equal).
+ *   tail_max (device) int64 [n_idx], 1 <= tail_max[k] <= S - 1, S = n_iter C >= 2; anything else is OMC_INVALID_ARG, found on the
+ *   device before any output is written (as an index outside [0, size)).
+ * Per column, every ll_s finite:
+ *   1. x_s = (-ll_s) - max_s(-ll_s), sorted ascending x_(0) .. x_(S-1); M = tail_max[k].
+ *   2. xc = max(x_(S-M-1), log(DBL_MIN) = -708.3964185322641); the tail is the T draws with x > xc (ties with the cut are not tail;
+ *      T by bisection in the sorted keys, exact).
+ *   3. T <= 4: k = +inf, nothing is smoothed.
+ *   4. Else a_i = exp(x_(S-T+i)) - exp(xc), ascending, and the fit of Zhang and Stephens (2009) with the priors of Vehtari et al.
+ *      (2024): n = T, m = 30 + floor(sqrt(n)), q = floor(n / 4 + 0.5) - 1; for i = 1 .. m:
+ *        b_i = 1 / a_(n-1) + (1 - sqrt(m / (i - 0.5))) / (3 a_q),  k_i = (1/n) sum_j log1p(-b_i a_j),  L_i = n (log(-b_i / k_i) - k_i - 1),
+ *        w_i = 1 / sum_j exp(L_j - L_i)  (an overflowing exp is +inf, the weight 0); candidates with w_i < 10 * 2^-52 are dropped, the
+ *      rest divided by their sum; b = sum b_i w_i, k' = (1/n) sum_j log1p(-b a_j), sigma = -k' / b, k = (n k' + 5) / (n + 10).
+ *   5. k finite: with p_i = (i + 0.5) / T the tail value x_(S-T+i) becomes log(sigma expm1(-k log1p(-p_i)) / k + exp(xc))
+ *      (|k| < 2^-52: log(-sigma log1p(-p_i) + exp(xc)); sigma <= 0: NaN), then every x becomes min(x, 0).
+ *   6. w = x - logsumexp(x), elpd = logsumexp_s(w_s + ll_s), each draw with its own weight: a draw outside the tail has
+ *      w + ll = -max(-ll) - logsumexp(x), and the smoothed values go to the tail draws in ascending order.
+ *   elpd_out [n_idx] fp64;  k_out [n_idx] fp64;  tail_out [n_idx] int64 = T, or NULL.
+ *   A column with an ll that is not finite gives NaN, NaN and -1 and affects nothing else.
+ *   OMC_INVALID_ARG, with a text in omc_last_error: ctx, store, tail_max, elpd_out or k_out NULL, S < 2, size < 1, n_idx < 1 (or no
+ *     index and n_idx != size), y and prec not given together, prec_size not 1 or n_idx (with y), an index or a tail_max out of
+ *     range, S beyond what the fit's 2048 candidate slots take (30 + floor(sqrt(S - 1)) > 2048: about 4 million draws).
+ * How: a chunk of columns at a time -- the gather of omc_store_ranks (keys of -ll), the sort of omc_store_ranks, then one workgroup
+ * per column that reads the sorted tail from the workspace (nothing assumes that a tail fits LDS).  Every sum is taken in an
+ * order that depends on (S, T) alone: repeated calls are bit-equal, and options "rank_tile" and "rank_chunk" apply with the same
+ * results bit for bit.  No scratch.  Workspace as omc_store_ranks (rank_ws: 8 P bytes per column and a few words).  The host reads
+ * two words back (the validation).  Runs on the context's stream.                                                             */
+omc_status omc_store_psis(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                          const double* y, const double* prec, int64_t prec_size, const int64_t* tail_max, double* elpd_out,
+                          double* k_out, int64_t* tail_out);
 /* Thinned copy of the store for a thinned gather: out[j] = store[first + j * every] (slabs of C * size doubles),
  * j = 0 .. ceil((n_iter - first) / every) - 1 (that count is left in *n_out when n_out is not NULL, host).           */
 omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int64_t first, int64_t every,

@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(256) k_hdi_gather(const double* __restrict__ s
                                                     uint64_t* __restrict__ keys, int32_t* __restrict__ flags) {
   const int64_t b = blockIdx.x, rest = b / n_st, c = rest / n_et;
   rank_gather_tile(store, idx, k0, Kc, size, S, P, (rest % n_et) * RANK_G_TE, (b % n_st) * RANK_G_TS, c * Kc,
-                   [=](int64_t s) { return s * rstride + c; }, [](double x) { return x; }, 0, keys, flags);
+                   [=](int64_t s) { return s * rstride + c; }, [](double x, int64_t, int64_t) { return x; }, 0, keys, flags);
 }
 
 // n_valid [n_col]: the keys of each sorted column that are not the all-ones key

@@ -12,6 +12,13 @@ __device__ __forceinline__ void omc_welford(double& n, double& mean, double& m2,
   mean += d / n;
   m2 = fma(d, v - mean, m2);
 }
+// Welford's update by a value that is the n-th of its series, with inv_n = 1 / n supplied by a caller that updates several series of
+// the same length side by side (one division for all of them); exact for equal values like omc_welford
+__device__ __forceinline__ void omc_welford_nth(double inv_n, double& mean, double& m2, double v) {
+  const double d = v - mean;
+  mean = fma(d, inv_n, mean);
+  m2 = fma(d, v - mean, m2);
+}
 __device__ __forceinline__ void omc_chan(double& n, double& mean, double& m2, double nb, double mb, double qb) {
   if (nb == 0.0) return;
   if (n == 0.0) {  // nothing yet: b as it is (d * d * 0 below is NaN once d * d overflows, from |mb| = 1.4e154 on)

@@ -45,7 +45,7 @@ __global__ void __launch_bounds__(256) k_rank_gather(const double* __restrict__ 
     for (int64_t c = threadIdx.x / RANK_G_TE; c < C; c += 256 / RANK_G_TE) bits |= rank_flag_bits(store[(mid_row0 + c) * size + col]);
   }
   rank_gather_tile(store, idx, k0, Kc, size, S, P, e0, (int64_t)blockIdx.x * RANK_G_TS, 0,
-                   [=](int64_t s) { return s < first ? s : s + skip; }, [=](double x) { return fold ? fabs(x - med) : x; }, bits, keys, flags);
+                   [=](int64_t s) { return s < first ? s : s + skip; }, [=](double x, int64_t, int64_t) { return fold ? fabs(x - med) : x; }, bits, keys, flags);
 }
 
 // stats [Kc][3] = median ((a + b) / 2 of the two middle order statistics: S is even), q05, q95 of the S sorted draws

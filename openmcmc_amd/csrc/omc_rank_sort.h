@@ -76,7 +76,7 @@ __device__ __forceinline__ void rank_gather_tile(const double* __restrict__ stor
     const int64_t s = s0 + d_l + 16 * u;
     uint64_t key = ~0ull;
     if (live && s < S) {
-      const double x = value(v[u]);
+      const double x = value(v[u], s, e_l);
       bits |= rank_flag_bits(x);
       key = rank_key(x);
     }

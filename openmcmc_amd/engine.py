@@ -1561,6 +1561,70 @@ class Engine:
         check(st)
         return out
 
+    def _loglik_inputs(self, store, y, prec, index):
+        """(n_iter, size, idx, n, y, prec) of the observation and precision arguments of store_loglik / store_psis"""
+        n_iter, size = self._store_shape(store)
+        idx, n = self._store_index(index, size)
+        yv = self._reduce_vector(y.reshape(-1) if isinstance(y, _torch().Tensor) else np.asarray(y, dtype=np.float64).reshape(-1), n, "y")
+        n_it, sz = self._store_shape(prec)
+        if n_it != n_iter:
+            raise ValueError(f"prec holds {n_it} iterations, the store {n_iter}")
+        if sz not in (1, n):
+            raise ValueError(f"prec must hold 1 or {n} values per draw, got {sz}")
+        return n_iter, size, idx, n, yv, prec
+
+    def store_loglik(self, store, y, prec, index=None, lse=True, mean=True, var=True, ll=False):
+        """Column summaries of the pointwise Normal log-density of a device MEAN entry (n_iter, C, size), on the device
+        (omc_store_loglik): (lse, mean, var, ll) as device tensors, None for what was not asked.  For the element x at selection
+        position k of row (it, c), ll = 0.5 log(tau) - 0.5 log(2 pi) - 0.5 tau (y[k] - x)^2 with tau = prec[it, c, 0 or k]; lse (n_idx,) is
+        log sum exp of ll over all n_iter * C >= 2 draws, mean and var (n_idx,) its mean and unbiased variance, ll the pointwise
+        entry (n_iter, C, n_idx) in the store's layout.  y: host array or device tensor with one value per SELECTED element; prec:
+        a device store (n_iter, C, 1) or (n_iter, C, n_idx).  A column with an ll that is not finite gives NaN in lse, mean and
+        var.  One read of the entry; repeated calls are bit-equal."""
+        n_iter, size, idx, n, yv, prec = self._loglik_inputs(store, y, prec, index)
+        if not (lse or mean or var or ll):
+            raise ValueError("nothing asked for: lse, mean, var and ll are all False")
+        outs = [self.empty(n) if want else None for want in (lse, mean, var)]
+        ll_out = self.empty(n_iter, self.n_chains, n) if ll else None
+        st = lib.omc_store_loglik(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, self._p(yv), self._p(prec), prec.shape[2],
+                                  self._p(outs[0]), self._p(outs[1]), self._p(outs[2]), self._p(ll_out))
+        if st == _abi.INVALID_ARG:  # the library says which argument
+            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
+        check(st)
+        return outs[0], outs[1], outs[2], ll_out
+
+    def store_psis(self, store, tail_max, index=None, y=None, prec=None):
+        """Pareto-smoothed importance sampling leave-one-out of every selected column of a device store (n_iter, C, size), on the
+        device (omc_store_psis): (elpd, k, tail) as device tensors (n_idx,), fp64, fp64 and int64 -- the PSIS-LOO expected log
+        predictive density of the observation, the Pareto k of its importance ratios (+inf where the tail holds 4 draws or
+        fewer) and the tail length used.  store holds pointwise log-likelihoods, or, with y and prec as in store_loglik, the mean
+        entry from which they are computed on load (the same bits).  tail_max: a number or one per selected element, each in
+        1 .. n_iter * C - 1.  A column with an ll that is not finite gives NaN, NaN and -1."""
+        torch = _torch()
+        if (y is None) != (prec is None):
+            raise ValueError("y and prec must be given together")
+        if y is None:
+            n_iter, size = self._store_shape(store)
+            idx, n = self._store_index(index, size)
+            yv = None
+        else:
+            n_iter, size, idx, n, yv, prec = self._loglik_inputs(store, y, prec, index)
+        tm = np.asarray(tail_max.cpu().numpy() if isinstance(tail_max, torch.Tensor) else tail_max)
+        if tm.size and tm.dtype.kind not in "iu":
+            raise ValueError("tail_max must hold integers")
+        tm = np.ascontiguousarray(np.broadcast_to(tm.reshape(-1), (n,)) if tm.size == 1 else tm.reshape(-1), dtype=np.int64)
+        if tm.shape != (n,):
+            raise ValueError(f"tail_max must be a number or hold one value per selected element ({n})")
+        tm = torch.tensor(tm, dtype=torch.int64, device=self.device)
+        elpd, k = self.empty(n), self.empty(n)
+        tail = torch.empty(n, dtype=torch.int64, device=self.device)
+        st = lib.omc_store_psis(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, self._p(yv), self._p(prec),
+                                0 if prec is None else prec.shape[2], tm.data_ptr(), self._p(elpd), self._p(k), tail.data_ptr())
+        if st == _abi.INVALID_ARG:  # the library says which argument
+            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
+        check(st)
+        return elpd, k, tail
+
     def store_thin(self, store, every, first=0):
         """store[first::every] of a device store (n_iter, C, ...) as a packed device tensor (one launch)."""
         if store.dim() < 2 or store.shape[1] != self.n_chains or not store.is_contiguous():
