@@ -1203,6 +1203,59 @@ omc_status omc_store_loglik(omc_ctx* ctx, int64_t n_iter, int64_t size, const do
 omc_status omc_store_psis(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                           const double* y, const double* prec, int64_t prec_size, const int64_t* tail_max, double* elpd_out,
                           double* k_out, int64_t* tail_out);
+/* PSIS-LOO expectations per selected column of the same store: every DRAW gets its own smoothed importance weight, and weighted
+ * sums of a second per-draw quantity f are taken with them -- the leave-one-out predictive mean and variance, the LOO-PIT of
+ * az.loo_pit, the normalised smoothed log weights of az.psislw.  store, idx, n_idx, y, prec, prec_size and tail_max as
+ * omc_store_psis: with y == NULL the entry holds ll, else it is a mean entry and ll comes from the same inline function (the two
+ * routes are bit-equal); the index and tail_max are checked on the device before anything is written.
+ *   f_kind  the quantity f_s of draw s at selection position k:
+ *     0 ENTRY  element vidx[k] (k itself with vidx == NULL, then n_idx == vsize) of values [n_iter][C][vsize] (device); vidx is
+ *              checked like idx.
+ *     1 MEAN   the mean entry's own element x.  Needs y.
+ *     2 CDF    0.5 erfc(-z 2^-1/2), z = sqrt(tau) (y[k] - x) (one rounded product of one IEEE subtraction; 2^-1/2 rounded to fp64):
+ *              the Normal predictive distribution function at the observation.  Needs y.
+ *   thr (device) [n_idx]: required exactly when below_out is given.
+ * Per column, every ll_s finite: steps 1 - 5 of omc_store_psis give vmax = max_s(-ll_s), xc, T, k, sigma and the smoothed sorted
+ * values x'_(p).  Draw s has v = -ll_s and x = v - vmax.
+ *   x <= xc, or nothing was smoothed (T <= 4, or k not finite):  w_s = exp(min(x, 0)).
+ *   Else, with lo the number of sorted keys < key(v) and hi the number <= key(v):  w_s = (sum_{p = lo}^{hi - 1} exp(x'_(p))) / (hi - lo),
+ *     the sum in ascending p.  Tied tail draws share the weight of their positions evenly, a draw that is not tied takes exactly
+ *     exp(x'_(lo)); the rule does not depend on the order of the draws in the store.
+ *   W = sum_s w_s                                 (a draw of weight 0 adds nothing to any sum)
+ *   mean_out    [n_idx]  sum w f / W
+ *   var_out     [n_idx]  sum w (f - mean)^2 / W: the weighted population variance, by West's weighted update per lane
+ *                        (mean += (f - mean) w / W_new, m2 += w (f - mean_old) (f - mean_new)) and Chan's join with weights for counts,
+ *                        never as sum w f^2 - mean^2
+ *   below_out   [n_idx]  sum w [f <= thr[k]] / W   (a NaN f counts as not below)
+ *   ess_out     [n_idx]  W^2 / sum w^2
+ *   invprec_out [n_idx]  sum (w / tau) / W.  Needs y.
+ *   k_out [n_idx], tail_out [n_idx] int64: as omc_store_psis, bit-equal to it.
+ *   lw_out [n_iter][C][n_idx], the store's layout: log(w_s) - L, L = logsumexp_p(x'_(p)) as the fit forms it (omc_store_psis step 6);
+ *     log(w_s) is the exponent itself where w_s is a single exponential, the logarithm of the mean for tied tail draws.
+ *   Any output may be NULL, not all; an accumulator nobody asked for is not updated.  A column with an ll that is not finite gives
+ *   NaN in every fp64 output, -1 in tail_out and NaN down its lw_out column; no other column is affected.  An f that is not finite
+ *   gives whatever IEEE gives in mean and var and leaves ess, k and tail alone.
+ *   OMC_INVALID_ARG, with a text in omc_last_error and nothing written: ctx, store or tail_max NULL, S < 2, size < 1, n_idx < 1 (or
+ *     no index and n_idx != size), y and prec not given together, prec_size not 1 or n_idx (with y), an index or a tail_max out of
+ *     range, S beyond the fit's candidate slots (as omc_store_psis); f_kind outside 0 .. 2; ENTRY without values, with vsize < 1, or
+ *     without vidx and n_idx != vsize; MEAN, CDF or invprec_out without y; below_out and thr not given together; a vidx outside
+ *     [0, vsize); every output NULL.
+ * How: a chunk of columns at a time -- gather, sort and fit as omc_store_psis (the fit is the same inline function; its record per
+ * column goes to the workspace), then one pass laid out like omc_store_loglik: a workgroup owns 32 adjacent selection positions
+ * and a slice of the rows (about 2048 workgroups over the whole selection, no slice shorter than 256 rows, at most 1024 slices:
+ * a function of (S, n_idx) alone, not of the chunk), lanes along the row -- 16-byte loads without an index where the sizes are even
+ * and the entries 16-byte aligned, else 8-byte loads --, 16 row lanes down it.  ll is made on load by the gather's own function, so
+ * a tail draw finds its key in the sorted column bit for bit; only tail draws bisect (at most tail_max of the S draws of a column).
+ * Lanes and slices are joined in a fixed order.  No atomics beyond the gather tile's flag OR; every sum is taken in an order
+ * that depends on the shape and on (S, T) alone: repeated calls are bit-equal, and "rank_tile", "rank_chunk" and both load forms
+ * give the same bits.  No scratch.  Workspace (rank_ws): per column of a chunk 8 P bytes of keys (P = S rounded up to a power of
+ * two), 64 bytes of fit record, 48 bytes per slice and a flag word.  The host reads three words back (the validation).  Runs on
+ * the context's stream.                                                                                                        */
+omc_status omc_store_loo_expect(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                                const double* y, const double* prec, int64_t prec_size, const int64_t* tail_max, int32_t f_kind,
+                                const double* values, int64_t vsize, const int64_t* vidx, const double* thr, double* mean_out,
+                                double* var_out, double* below_out, double* ess_out, double* invprec_out, double* k_out,
+                                int64_t* tail_out, double* lw_out);
 /* Thinned copy of the store for a thinned gather: out[j] = store[first + j * every] (slabs of C * size doubles),
  * j = 0 .. ceil((n_iter - first) / every) - 1 (that count is left in *n_out when n_out is not NULL, host).           */
 omc_status omc_store_thin(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, int64_t first, int64_t every,

@@ -170,6 +170,8 @@ SIGNATURES = {
     "omc_store_project": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i64, c_dp, i64, c_dp, c_dp, i32, c_dp, i64, c_dp, u64, c_dp]),
     "omc_store_loglik": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, c_dp, c_dp, i64, c_dp, c_dp, c_dp, c_dp]),
     "omc_store_psis": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, c_dp, c_dp, i64, c_dp, c_dp, c_dp, c_dp]),
+    "omc_store_loo_expect": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, c_dp, c_dp, i64, c_dp, i32, c_dp, i64, c_dp, c_dp,
+                                   c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "omc_band_sample_canonical": (
         i32, [C.c_void_p, i64, i64, C.POINTER(BandTerms), c_dp, i64, c_dp, i64, u64, c_dp, i64, c_dp, i64, c_dp]),
     "omc_band_quadform": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, c_dp, i64, c_dp]),

@@ -11,30 +11,19 @@
 //                  computed on the way -- the same inline function as omc_store_loglik, so the two routes give the same bits.  It
 //                  notes per column whether a NaN or an infinity was seen.
 //   rank_sort      the key-only bitonic sort of every column (omc_store_shared.hip).
-//   k_psis_fit     one workgroup of 512 per column, everything read from the sorted keys in the workspace (a tail may be S / 5
-//                  long: nothing assumes that it fits LDS).  x_(i) = v_(i) - v_(S-1).  The cut and the tail length T by a bisection
-//                  with the tail's own predicate x > xc, so T is exact.  The m candidate slopes of the fit go round the eight
-//                  waves: a wave sums log1p(-b_i a_j) over the tail, lane l taking j = l, l + 64, .. in ascending order, the 64
-//                  lanes combined by the butterfly 32 .. 1 (a + b == b + a: every lane ends with the same bits); a_j =
-//                  exp(x_j) - exp(xc) is made again from the key each time rather than kept.  The weights, one thread per
-//                  candidate, each a serial sum in ascending j; their normalisation and b serially in thread 0.  The sum for k' and
-//                  the two log-sum-exp over the smoothed column (its normaliser, and the weighted likelihood): thread t takes
-//                  positions t, t + 512, .. in ascending order, and thread 0 joins the 512 partial results in thread order.
-//                  Every order is a function of (S, T) alone: repeated calls, and any "rank_tile" / "rank_chunk", give the same bits.
+//   k_psis_fit     one workgroup of 512 per column: psis_fit_column of omc_psis_fit.h (described there; shared with
+//                  omc_loo_expect.hip, which keeps the fit instead of folding it) and the three stores.  Every order of additions is
+//                  a function of (S, T) alone: repeated calls, and any "rank_tile" / "rank_chunk", give the same bits.
 // No scratch.  The only atomics are the gather tile's flag words (an OR: independent of the order).
 #include <math.h>
 
 #include "omc_common.h"
 #include "omc_loglik.h"
+#include "omc_psis_fit.h"
 #include "omc_rank_sort.h"
 #include "omc_store_view.h"
 
 namespace {
-
-constexpr int PSIS_THREADS = 512;
-constexpr int PSIS_M_MAX = 4 * PSIS_THREADS;            // candidate slopes of the fit at most: 30 + floor(sqrt(T))
-constexpr double PSIS_LOG_MIN = -708.3964185322641;    // log(DBL_MIN)
-constexpr double PSIS_EPS = 2.220446049250313e-16;     // 2^-52
 
 __global__ void __launch_bounds__(256) k_psis_check_tail(const int64_t* __restrict__ tail_max, int64_t n, int64_t S, int32_t* __restrict__ word) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -50,133 +39,29 @@ __global__ void __launch_bounds__(256) k_psis_gather(const double* __restrict__ 
   rank_gather_tile(store, idx, k0, Kc, size, S, P, e0, (int64_t)blockIdx.x * RANK_G_TS, 0,
                    [](int64_t s) { return s; },
                    [=](double x, int64_t s, int64_t e_l) {  // draw s of selection position k0 + e0 + e_l (live: below n_idx)
-                     if (!y) return -x;
-                     const int64_t k = k0 + e0 + e_l;
-                     const double tau = prec[prec_size == 1 ? s : s * n_idx + k];
-                     return -omc_normal_ll(omc_normal_ll_head(tau), tau, y[k], x);
+                     return psis_neg_ll(x, s, k0 + e0 + e_l, y, prec, prec_size, n_idx);
                    },
                    0, keys, flags);
-}
-
-// the sum of the workgroup's 512 values in thread order, in every thread (red: 512 doubles of LDS)
-__device__ __forceinline__ double psis_block_sum(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = red[0];
-    for (int q = 1; q < PSIS_THREADS; ++q) t += red[q];
-    red[0] = t;
-  }
-  __syncthreads();
-  return red[0];
 }
 
 __global__ void __launch_bounds__(PSIS_THREADS) k_psis_fit(int64_t k0, int64_t S, int64_t P, const uint64_t* __restrict__ keys,
                                                             const int32_t* __restrict__ flags, const int64_t* __restrict__ tail_max,
                                                             double* __restrict__ elpd_out, double* __restrict__ k_out,
                                                             int64_t* __restrict__ tail_out) {
-  __shared__ double cand_b[PSIS_M_MAX], cand_l[PSIS_M_MAX];
-  __shared__ double red[4][PSIS_THREADS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t e = blockIdx.x;
-  const double nan = __longlong_as_double(0x7ff8000000000000LL), inf = __longlong_as_double(0x7ff0000000000000LL);
   if (flags[e] != 0) {  // a draw whose log-likelihood is not finite
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
+      const double nan = __longlong_as_double(0x7ff8000000000000LL);
       elpd_out[k0 + e] = nan; k_out[k0 + e] = nan;
       if (tail_out) tail_out[k0 + e] = -1;
     }
     return;
   }
-  const uint64_t* __restrict__ col = keys + e * P;
-  const double vmax = q_val(col[S - 1]);
-  const int64_t Mt = tail_max[k0 + e];  // 1 .. S - 1: checked before the launch
-  const double xcut = q_val(col[S - Mt - 1]) - vmax;
-  const double xc = xcut > PSIS_LOG_MIN ? xcut : PSIS_LOG_MIN;
-  // first position with x > xc: x is non-decreasing along the sorted column (every thread walks the same bisection)
-  int64_t lo = 0, hi = S;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (q_val(col[mid]) - vmax > xc) hi = mid; else lo = mid + 1;
-  }
-  const int64_t t0 = lo, T = S - t0;
-  const double exc = exp(xc);
-  double khat = inf, sigma = 0.0;
-  if (T > 4) {
-    const int64_t n = T;
-    const double dn = (double)n;
-    const int m = 30 + (int)floor(sqrt(dn));  // <= PSIS_M_MAX: checked on the host from S
-    const int64_t q = (int64_t)floor(dn / 4.0 + 0.5) - 1;
-    const double a_last = exp(q_val(col[S - 1]) - vmax) - exc, a_q = exp(q_val(col[t0 + q]) - vmax) - exc;
-    for (int i = wave; i < m; i += PSIS_THREADS / 64) {
-      const double b = 1.0 / a_last + (1.0 - sqrt((double)m / ((double)(i + 1) - 0.5))) / (3.0 * a_q);
-      double sum = 0.0;
-      for (int64_t j = lane; j < n; j += 64) sum += log1p(-b * (exp(q_val(col[t0 + j]) - vmax) - exc));
-      for (int w = 32; w >= 1; w >>= 1) sum += __shfl_xor(sum, w, 64);
-      if (lane == 0) {
-        const double ki = sum / dn;
-        cand_b[i] = b;
-        cand_l[i] = dn * (log(-b / ki) - ki - 1.0);
-      }
-    }
-    __syncthreads();
-    // w_i = 1 / sum_j exp(L_j - L_i): an overflowing exp is +inf and the weight 0
-    double* cand_w = &red[0][0];  // 4 * PSIS_THREADS == PSIS_M_MAX doubles
-    for (int i = tid; i < m; i += PSIS_THREADS) {
-      const double li = cand_l[i];
-      double sum = 0.0;
-      for (int j = 0; j < m; ++j) sum += exp(cand_l[j] - li);
-      cand_w[i] = 1.0 / sum;
-    }
-    __syncthreads();
-    if (tid == 0) {  // the candidates below the cut are dropped, the rest divided by their sum
-      double tot = 0.0;
-      for (int i = 0; i < m; ++i) tot += cand_w[i] >= 10.0 * PSIS_EPS ? cand_w[i] : 0.0;
-      double b = 0.0;
-      for (int i = 0; i < m; ++i)
-        if (cand_w[i] >= 10.0 * PSIS_EPS) b += cand_b[i] * (cand_w[i] / tot);
-      cand_b[0] = b;
-    }
-    __syncthreads();
-    const double b = cand_b[0];
-    double part = 0.0;
-    for (int64_t j = tid; j < n; j += PSIS_THREADS) part += log1p(-b * (exp(q_val(col[t0 + j]) - vmax) - exc));
-    const double kp = psis_block_sum(part, red[0]) / dn;
-    sigma = -kp / b;
-    khat = (dn * kp + 5.0) / (dn + 10.0);
-  }
-  // the smoothed column: its normaliser L = logsumexp(x') and G = logsumexp(x' + ll), ll = -v; elpd = G - L
-  const bool smooth = khat == khat && fabs(khat) < inf;
-  double ML = -inf, sL = 0.0, MG = -inf, sG = 0.0;
-  for (int64_t s = tid; s < S; s += PSIS_THREADS) {
-    const double v = q_val(col[s]);
-    double x = v - vmax;
-    if (s < t0) {
-      omc_lse_add(ML, sL, x, 1.0);
-    } else {
-      if (smooth) {
-        const double p = ((double)(s - t0) + 0.5) / (double)T, lp = log1p(-p);
-        const double g = fabs(khat) < PSIS_EPS ? -sigma * lp : sigma * expm1(-khat * lp) / khat;
-        x = sigma > 0.0 ? log(g + exc) : nan;
-        x = x > 0.0 ? 0.0 : x;  // min(x, 0); a NaN stays
-      }
-      omc_lse_add(ML, sL, x, 1.0);
-      omc_lse_add(MG, sG, x - v, 1.0);
-    }
-  }
-  __syncthreads();
-  red[0][tid] = ML; red[1][tid] = sL; red[2][tid] = MG; red[3][tid] = sG;
-  __syncthreads();
-  if (tid == 0) {
-    for (int q = 1; q < PSIS_THREADS; ++q) {
-      omc_lse_join(ML, sL, red[0][q], red[1][q]);
-      omc_lse_join(MG, sG, red[2][q], red[3][q]);
-    }
-    // a draw outside the tail has x' + ll = -max(-ll): t0 >= 1 of them
-    omc_lse_join(MG, sG, -vmax, (double)t0);
-    elpd_out[k0 + e] = (MG + log(sG)) - (ML + log(sL));
-    k_out[k0 + e] = khat;
-    if (tail_out) tail_out[k0 + e] = T;
+  const PsisFit f = psis_fit_column(keys + e * P, S, tail_max[k0 + e]);  // tail_max 1 .. S - 1: checked before the launch
+  if (threadIdx.x == 0) {
+    elpd_out[k0 + e] = f.elpd;
+    k_out[k0 + e] = f.khat;
+    if (tail_out) tail_out[k0 + e] = f.T;
   }
 }
 

@@ -1609,13 +1609,7 @@ class Engine:
             yv = None
         else:
             n_iter, size, idx, n, yv, prec = self._loglik_inputs(store, y, prec, index)
-        tm = np.asarray(tail_max.cpu().numpy() if isinstance(tail_max, torch.Tensor) else tail_max)
-        if tm.size and tm.dtype.kind not in "iu":
-            raise ValueError("tail_max must hold integers")
-        tm = np.ascontiguousarray(np.broadcast_to(tm.reshape(-1), (n,)) if tm.size == 1 else tm.reshape(-1), dtype=np.int64)
-        if tm.shape != (n,):
-            raise ValueError(f"tail_max must be a number or hold one value per selected element ({n})")
-        tm = torch.tensor(tm, dtype=torch.int64, device=self.device)
+        tm = self._tail_max(tail_max, n)
         elpd, k = self.empty(n), self.empty(n)
         tail = torch.empty(n, dtype=torch.int64, device=self.device)
         st = lib.omc_store_psis(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, self._p(yv), self._p(prec),
@@ -1624,6 +1618,80 @@ class Engine:
             raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
         check(st)
         return elpd, k, tail
+
+    def _tail_max(self, tail_max, n):
+        """tail_max, a number or one per selected element, as a device int64 tensor (n,)"""
+        torch = _torch()
+        tm = np.asarray(tail_max.cpu().numpy() if isinstance(tail_max, torch.Tensor) else tail_max)
+        if tm.size and tm.dtype.kind not in "iu":
+            raise ValueError("tail_max must hold integers")
+        tm = np.ascontiguousarray(np.broadcast_to(tm.reshape(-1), (n,)) if tm.size == 1 else tm.reshape(-1), dtype=np.int64)
+        if tm.shape != (n,):
+            raise ValueError(f"tail_max must be a number or hold one value per selected element ({n})")
+        return torch.tensor(tm, dtype=torch.int64, device=self.device)
+
+    def store_loo_expect(self, store, tail_max, index=None, y=None, prec=None, f="entry", values=None, values_index=None,
+                         threshold=None, want=("mean", "var", "ess", "k", "tail"), lw=False):
+        """PSIS-LOO expectations of every selected column of a device store (n_iter, C, size), on the device
+        (omc_store_loo_expect): a dict of device tensors (n_idx,) for the names in want -- "mean", "var" (the leave-one-out
+        weighted mean and population variance of a per-draw quantity f), "below" (the weighted share of draws with
+        f <= threshold), "ess" (the effective sample size of the weights, W^2 / sum w^2), "invprec" (the weighted mean of
+        1 / precision), "k" and "tail" (as store_psis, the same bits) -- and with lw=True "lw", the normalised smoothed log
+        weights (n_iter, C, n_idx) in the store's layout, what az.psislw returns.  store, tail_max, index, y and prec as
+        store_psis.  f: "entry" takes element values_index[k] (k itself without values_index) of the device entry values
+        (n_iter, C, vsize); "mean" the mean entry's own element; "cdf" the Normal predictive distribution function at the
+        observation (both need y and prec).  threshold: one value per selected element, required exactly with "below".
+        Every draw has the smoothed weight of its position in the sorted column; tied tail draws share theirs evenly.  A
+        column with an ll that is not finite gives NaN, -1 in tail and NaN down its lw column."""
+        torch = _torch()
+        kinds = {"entry": 0, "mean": 1, "cdf": 2}
+        if f not in kinds:
+            raise ValueError(f"unknown f {f!r}: one of {', '.join(kinds)}")
+        names = ("mean", "var", "below", "ess", "invprec", "k", "tail")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for w in want:
+            if w not in names:
+                raise ValueError(f"unknown output {w!r}: one of {', '.join(names)}")
+        if not want and not lw:
+            raise ValueError("nothing asked for: want is empty and lw is False")
+        if (y is None) != (prec is None):
+            raise ValueError("y and prec must be given together")
+        if y is None:
+            n_iter, size = self._store_shape(store)
+            idx, n = self._store_index(index, size)
+            yv = None
+        else:
+            n_iter, size, idx, n, yv, prec = self._loglik_inputs(store, y, prec, index)
+        vidx, vsize = None, 0
+        if f == "entry":
+            if values is None:
+                raise ValueError('f="entry" needs values')
+            n_it, vsize = self._store_shape(values)
+            if n_it != n_iter:
+                raise ValueError(f"values holds {n_it} iterations, the store {n_iter}")
+            vidx, nv = self._store_index(values_index, vsize)
+            if nv != n:
+                raise ValueError(f"values selects {nv} elements, the store {n}")
+        elif values is not None or values_index is not None:
+            raise ValueError('values and values_index apply to f="entry" only')
+        if ("below" in want) != (threshold is not None):
+            raise ValueError('threshold and "below" must be given together')
+        thr = None
+        if threshold is not None:
+            thr = self._reduce_vector(threshold.reshape(-1) if isinstance(threshold, torch.Tensor)
+                                      else np.asarray(threshold, dtype=np.float64).reshape(-1), n, "threshold")
+        tm = self._tail_max(tail_max, n)
+        out = {w: (torch.empty(n, dtype=torch.int64, device=self.device) if w == "tail" else self.empty(n)) for w in want}
+        if lw:
+            out["lw"] = self.empty(n_iter, self.n_chains, n)
+        p = {w: (out[w].data_ptr() if w in out else None) for w in names + ("lw",)}
+        st = lib.omc_store_loo_expect(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, self._p(yv), self._p(prec),
+                                      0 if prec is None else prec.shape[2], tm.data_ptr(), kinds[f], self._p(values), vsize, _ptr(vidx),
+                                      self._p(thr), p["mean"], p["var"], p["below"], p["ess"], p["invprec"], p["k"], p["tail"], p["lw"])
+        if st == _abi.INVALID_ARG:  # the library says which argument
+            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
+        check(st)
+        return out
 
     def store_thin(self, store, every, first=0):
         """store[first::every] of a device store (n_iter, C, ...) as a packed device tensor (one launch)."""

@@ -712,11 +712,7 @@ class MCMC:
         lse = None
         for j0, j1, m, mean, y, prec in self._pointwise_chunks(response, "loo"):
             if lse is None:
-                r = np.asarray(reff, dtype=np.float64).reshape(-1)
-                r = np.broadcast_to(r, (m,)) if r.size == 1 else r
-                if r.shape != (m,) or not np.all(r > 0):
-                    raise ValueError(f"reff must be a positive number or hold one per observation ({m})")
-                tail_max = np.clip(np.ceil(np.minimum(S / 5.0, 3.0 * np.sqrt(S / r))), 1, S - 1).astype(np.int64)
+                tail_max = self._loo_tail_max(reff, m)
                 lse, elpd_i, k, tail = np.empty(m), np.empty(m), np.empty(m), np.empty(m, dtype=np.int64)
             lse[j0:j1] = self.engine.store_loglik(mean, y, prec, lse=True, mean=False, var=False)[0].cpu().numpy()
             e, kk, t = self.engine.store_psis(mean, tail_max[j0:j1], y=y, prec=prec)
@@ -727,6 +723,120 @@ class MCMC:
         if pointwise:
             out.update({"elpd_i": elpd_i, "lppd_i": lppd_i})
         return out
+
+    def _loo_tail_max(self, reff, m):
+        """the longest tail of each of the m observations, ceil(min(S / 5, 3 sqrt(S / reff))) within 1 .. S - 1"""
+        S = self._n_dev * self.n_chains
+        r = np.asarray(reff, dtype=np.float64).reshape(-1)
+        r = np.broadcast_to(r, (m,)) if r.size == 1 else r
+        if r.shape != (m,) or not np.all(r > 0):
+            raise ValueError(f"reff must be a positive number or hold one per observation ({m})")
+        return np.clip(np.ceil(np.minimum(S / 5.0, 3.0 * np.sqrt(S / r))), 1, S - 1).astype(np.int64)
+
+    def _loo_expect(self, what, response, reff, f, want, values=None, index=None, threshold=None, lw=False):
+        """omc_store_loo_expect over the chunks of `_pointwise_chunks`: ({name: host array (m,)}, the observations (m,), the
+        device entry (n_iter, C, m) of the log weights or None).  values is a store key (f = "entry"), index selects m of its
+        elements, threshold is a scalar, holds one value per observation, or is True for the observations themselves."""
+        out = lw_out = ys = None
+        for j0, j1, m, mean, y, prec in self._pointwise_chunks(response, what):
+            if out is None:
+                tail_max = self._loo_tail_max(reff, m)
+                out = {w: np.empty(m, dtype=np.int64 if w == "tail" else np.float64) for w in want}
+                ys = np.empty(m)
+                vt = vi = thr = None
+                if values is not None:
+                    vt = self._store_3d(values)
+                    if index is not None:
+                        vi = np.asarray(index)
+                        if vi.ndim != 1 or (vi.size and vi.dtype.kind not in "iu"):
+                            raise ValueError("index must be a one-dimensional sequence of integers")
+                    if (vt.shape[2] if vi is None else vi.size) != m:
+                        raise ValueError(f"{values!r} holds or selects {vt.shape[2] if vi is None else vi.size} elements, the "
+                                         f"response {response!r} {m} observations")
+                if threshold is not None and threshold is not True:
+                    thr = np.asarray(threshold, dtype=np.float64).reshape(-1)
+                    thr = np.broadcast_to(thr, (m,)) if thr.size == 1 else thr
+                    if thr.shape != (m,):
+                        raise ValueError(f"threshold must be a number or hold one per observation ({m})")
+            whole = (j0, j1) == (0, m)
+            sel = None
+            if vt is not None and not (whole and vi is None):
+                sel = np.arange(j0, j1) if vi is None else vi[j0:j1]
+            got = self.engine.store_loo_expect(mean, tail_max[j0:j1], y=y, prec=prec, f=f, values=vt, values_index=sel,
+                                               threshold=y if threshold is True else None if thr is None else thr[j0:j1], want=want,
+                                               lw=lw)
+            ys[j0:j1] = y
+            for w in want:
+                out[w][j0:j1] = got[w].cpu().numpy()
+            if lw and whole:
+                lw_out = got["lw"]
+            elif lw:
+                if lw_out is None:
+                    lw_out = self.engine.empty(self._n_dev, self.n_chains, m)
+                lw_out[:, :, j0:j1] = got["lw"]
+        return out, ys, lw_out
+
+    def loo_expectation(self, response, values, index=None, threshold=None, reff=1.0):
+        """Leave-one-out expectations of a stored quantity under the PSIS weights of a Normal response of the model, computed on
+        the device (omc_store_loo_expect; neither the pointwise log-likelihood nor the weights are written): a dict of host
+        arrays (m,) -- "mean" and "sd", the weighted mean and population standard deviation of store[values][..., i] over the
+        stored draws with observation i left out, "ess" the effective sample size of the weights (sum w)^2 / sum w^2,
+        "pareto_k" as `loo`, and with a threshold "below", the weighted share of draws with value <= threshold[i].  What a loop of
+        weighted averages over az.psislw(-log_likelihood) gives.  values is a store key whose last dimension matches the m
+        observations, or of which index selects m elements (in that order, repeats allowed); threshold a number or one per
+        observation.  Every draw has the smoothed weight of its position among the sorted importance ratios; tied tail draws
+        share theirs evenly.  reff as `loo`.  The models read and the sharding remark (this rank's chains only) as
+        `log_likelihood`.  An observation with a log-likelihood that is not finite under some draw gives NaN; a value that is
+        not finite gives what IEEE gives in "mean" and "sd" and leaves "ess" and "pareto_k" alone."""
+        want = ("mean", "var", "ess", "k") + (("below",) if threshold is not None else ())
+        got, _, _ = self._loo_expect("loo_expectation", response, reff, "entry", want, values=values, index=index, threshold=threshold)
+        out = {"mean": got["mean"], "sd": np.sqrt(got["var"]), "ess": got["ess"], "pareto_k": got["k"]}
+        if threshold is not None:
+            out["below"] = got["below"]
+        return out
+
+    def loo_predictive(self, response, reff=1.0):
+        """Leave-one-out predictive means and standard deviations of a Normal response of the model, computed on the device
+        (omc_store_loo_expect, one pass): a dict with "mean" (m,), E_loo[mu_i], the PSIS-weighted mean of the fitted mean of
+        observation i with that observation left out; "sd" (m,), sqrt(E_loo[1 / precision_i] + Var_loo[mu_i]), the standard
+        deviation of the leave-one-out predictive distribution; "residual" = y - mean; "z" = residual / sd; "r2", the LOO-R^2
+        1 - np.var(residual) / np.var(y) (a float); and "pareto_k" (m,) as `loo`.  reff as `loo`; the models read and the
+        sharding remark (this rank's chains only) as `log_likelihood`.  An observation with a log-likelihood that is not
+        finite under some draw gives NaN (and a NaN "r2")."""
+        got, y, _ = self._loo_expect("loo_predictive", response, reff, "mean", ("mean", "var", "invprec", "k"))
+        sd = np.sqrt(got["invprec"] + got["var"])
+        res = y - got["mean"]
+        return {"mean": got["mean"], "sd": sd, "residual": res, "z": res / sd, "r2": float(1.0 - np.var(res) / np.var(y)),
+                "pareto_k": got["k"]}
+
+    def loo_pit(self, response, y_rep=None, reff=1.0):
+        """Leave-one-out probability integral transform of a Normal response of the model (az.loo_pit), computed on the
+        device: a host array (m,), uniform on [0, 1] for a calibrated model.  With y_rep=None the analytic value, the
+        PSIS-weighted mean over the stored draws of the Normal distribution function of observation i under the draw's mean
+        and precision; with y_rep a store key made by `posterior_predictive(name=...)` the weighted share of replicates
+        y_rep[..., i] <= y_i, az.loo_pit's own definition.  reff as `loo`; the models read and the sharding remark (this rank's
+        chains only) as `log_likelihood`.  An observation with a log-likelihood that is not finite under some draw gives
+        NaN; a NaN replicate counts as not below."""
+        if y_rep is None:
+            return self._loo_expect("loo_pit", response, reff, "cdf", ("mean",))[0]["mean"]
+        return self._loo_expect("loo_pit", response, reff, "entry", ("below",), values=y_rep, threshold=True)[0]["below"]
+
+    def loo_weights(self, response, name=None, reff=1.0):
+        """The normalised Pareto-smoothed log importance weights of a Normal response of the model (the first result of
+        az.psislw(-log_likelihood)), computed on the device: a host array (n_iter, C, m), the store's own layout, whose
+        exponentials sum to 1 over the draws of every observation -- the weights with which any other stored quantity is
+        averaged leave-one-out.  With name the entry stays on the device as store[name] and None is returned, under the rules
+        of `log_likelihood(name=...)`.  Tied tail draws share the weight of their sorted positions evenly.  reff as `loo`; the
+        models read and the sharding remark (this rank's chains only) as `log_likelihood`.  An observation with a
+        log-likelihood that is not finite under some draw gives a NaN column."""
+        if name is not None and name in self.store and name not in self._derived:
+            raise ValueError(f"{name!r} is a store entry of the run: choose another name for the weights")
+        lw = self._loo_expect("loo_weights", response, reff, "mean", (), lw=True)[2]
+        if name is None:
+            return lw.cpu().numpy()
+        self.store[name] = lw
+        self._derived.add(name)
+        return None
 
     def simultaneous_band(self, key, prob=0.95, index=None):
         """A simultaneous credible band of the selected elements of store[key], computed on the device (two reads of the
