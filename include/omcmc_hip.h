@@ -981,6 +981,53 @@ omc_status omc_store_ranks(omc_ctx* ctx, int64_t n_iter, int64_t size, const dou
  * depends on the size).  Deterministic: repeated calls are bit-equal.                                                       */
 omc_status omc_store_rank_diagnostics(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx,
                                       int64_t n_idx, double* rhat_out, double* ess_bulk_out, double* ess_tail_out);
+/* The effective sample size of indicator series of the same store: ArviZ's ess(method="quantile") and ess(method="local"), the
+ * numbers that say whether a reported quantile or interval end point has converged.  store, idx, n_idx, the NULL convention and the
+ * out-of-range index rule as omc_store_rank_diagnostics; N = n_iter >= 4 (else OMC_INVALID_ARG); M = N / 2, J = 2 C, S = J M, the
+ * split draws those of omc_store_rhat_ess (the middle row of an odd N is dropped, and read only for its NaN / inf).
+ *   prob_lo, prob_hi [n_p] on the HOST, 1 <= n_p <= 32.  prob_lo[i] < 0: no lower end, I = (x <= q_hi) (ArviZ's _ess_quantile);
+ *            otherwise 0 <= lo <= hi <= 1 and I = (q_lo <= x && x <= q_hi) (_ess_local).  Anything else (NaN included) is
+ *            OMC_INVALID_ARG, found before any launch.
+ *   q_p      = np.quantile of the element's S split draws, default "linear" method, read from the sorted column with numpy's
+ *            interpolation operation by operation (bit-equal).  For an even N this is ArviZ's quantile of all draws; for an odd N
+ *            it differs from it by the dropped row.
+ *   With b_j[0..M) the 0/1 series of one (element, interval), all exact in int64:
+ *     n_j = sum_s b_j[s],  Nn = sum_j n_j,  Q = sum_j n_j^2,
+ *     A(t) = sum_j sum_{s < M - t} b_j[s] b_j[s + t],
+ *     H(t) = sum_j n_j (sum_{s < M - t} b_j[s] + sum_{s >= t} b_j[s]),
+ *     Z(t) = M^2 A(t) - M H(t) + (M - t) Q                (Z(0) = M (M Nn - Q)),
+ *   and in omc_store_rhat_ess's notation S(t) = (double)Z(t) / ((double)M (double)M),
+ *   B_M = (double)(J Q - Nn^2) / ((double)M (double)M (double)J (double)(J - 1)); W, var_plus, rho(t), Geyer's initial monotone
+ *   sequence, the floor on tau and every edge rule are those of omc_store_rhat_ess, one copy of the code: a constant series (every
+ *   draw inside, or every draw outside the interval) gives ess = J M with lags 0, and W == 0 < B_M runs to the M - 3 limit.
+ *   Z(t) and J Q - Nn^2 must be exact: J M^3 >= 2^62 or J M >= 2^31 is OMC_UNSUPPORTED.
+ *   ess_out [n_p][n_idx] fp64; lag_out [n_p][n_idx] int32, the lags the sequence used (as omc_store_rhat_ess);
+ *   q_out [n_p][n_idx][2] fp64: the thresholds q_lo, q_hi, [..][0] NaN where there is no lower end;
+ *   counts_out [n_p][n_idx][2 + 2 n_cnt] int64 = Nn, Q, then the pairs A(t), H(t) for t < n_cnt, 0 <= n_cnt <= M (else
+ *            OMC_INVALID_ARG): when given, these lags are evaluated whether or not the sequence needs them (for tests).
+ *   Any output may be NULL.  An element with any non-finite draw (NaN or +-inf) gives NaN, lags 0 and zero counts in every
+ *   interval (its q_out is whatever the interpolation gives) and affects nothing else.
+ *   algo: 0 auto, 1 the bits of a column staged in LDS (8 J ceil(M / 64) + 4 J <= 144 KiB, else OMC_INVALID_ARG; two workgroups
+ *   share a compute unit up to half of that), 2 the bits read from global memory / L2.  0 takes form 1 where it fits.
+ * Per chunk of elements: the gather and the sort of omc_store_ranks with the split geometry, the thresholds, one read of the
+ * chunk's columns that packs 64 draws into a word per interval (bits [Kc][n_p][J][ceil(M / 64)], every series on its own word,
+ * the bits past M zero), and one launch in which a workgroup per (element, interval) walks its own Geyer sequence to the end in
+ * blocks of 64 lags -- popcounts of a word ANDed with its shifted successor -- with no host round trip.  Every sum is an integer
+ * and the fp64 steps follow one fixed sequence from them: repeated calls, any "rank_tile", any "rank_chunk" and both forms are
+ * BIT-EQUAL.  No floating-point atomics.  Workspace from the context's rank workspace: 8 P + n_p (8 J ceil(M / 64) + 4 J + 16)
+ * bytes per element of a chunk.                                                                                          */
+omc_status omc_store_ess_indicator(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                                   const double* prob_lo, const double* prob_hi, int32_t n_p, int32_t algo, double* ess_out,
+                                   int32_t* lag_out, double* q_out, int64_t* counts_out, int64_t n_cnt);
+/* Order statistics of the same store at given positions: out [n_idx][n_pos] fp64 = sorted column of element e at pos[e][k], pos
+ * [n_idx][n_pos] int64 on the DEVICE; store, idx, n_idx as omc_store_ranks.  split != 0: the column is the S split draws (n_iter
+ * >= 4), else all n_iter C draws.  A position outside the column is OMC_INVALID_ARG, found on the device (with the index check,
+ * one read-back) before out is written.  An element with a NaN draw gives NaN.  Equal to np.sort(column)[pos], except that a zero
+ * comes back as +0.0 (the keys merge the two zeros).  The gather and the sort of omc_store_ranks, then a pick; options "rank_tile"
+ * and "rank_chunk" apply: same bits.  What mcse_quantile needs: its positions depend on the ESS through a beta quantile the host
+ * evaluates.                                                                                                              */
+omc_status omc_store_order_stats(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                                 int32_t split, const int64_t* pos, int64_t n_pos, double* out);
 /* [host, no GPU] The launches that sort columns of S keys with tiles of `tile` keys (0 = 8192, or a power of two 64 .. 8192, else
  * OMC_INVALID_ARG; S >= 1): P = the next power of two >= S, T = min(tile, P); out [cap][3] = (kind, k, j) per launch, *n_out their
  * number (set also when cap is too small, which is OMC_INVALID_ARG).  A compare-exchange at stride j of stage k orders the keys at

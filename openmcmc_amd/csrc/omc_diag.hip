@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "omc_common.h"
+#include "omc_geyer.h"
 #include "omc_lag_block.h"
 #include "omc_moments.h"
 
@@ -184,7 +185,7 @@ __global__ void __launch_bounds__(256) k_diag_sum(int64_t size, int nl, int G, d
 }
 
 // One thread per element, one wave per tile: the sums S(t) of lags [t0, t0 + nl) (k_diag_sum's totals), then the
-// element's Geyer state advanced (t0 == 0: W, B_M, rhat and the state set up first).  st [D_STATE][size]:
+// element's Geyer state advanced by the rule of omc_geyer.h (t0 == 0: W, B_M, rhat and the state set up first).  st [D_STATE][size]:
 //   0 W, 1 var_plus, 2 even, 3 odd (the last evaluated pair), 4 sum of the monotone pair sums so far, 5 their running
 //   minimum, 6 index of the last evaluated pair, 7 1 while the sequence goes on.
 // tile_active[tile]: the tile still holds an active element; *any_active set when any tile does.
@@ -197,8 +198,8 @@ __global__ void __launch_bounds__(64) k_diag_step(int64_t size, int64_t M, int64
   if (k < size) {
     const double JM = (double)J * (double)M;
     auto S = [&](int64_t t) { return part[(t - t0) * size + k]; };  // S(t), t in [t0, t0 + nl)
-    double W = 0.0, vp = 0.0, even = 0.0, odd = 0.0, acc = 0.0, minq = 0.0, pp = 0.0;
-    bool go = true, finished = false;
+    GeyerState g = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool go = true;
     if (t0 == 0) {
       double bn = 0.0, bm = 0.0, bq = 0.0;
       for (int gg = 0; gg < G; ++gg) {
@@ -206,56 +207,34 @@ __global__ void __launch_bounds__(64) k_diag_step(int64_t size, int64_t M, int64
         omc_chan(bn, bm, bq, o[k], o[size + k], o[2 * size + k]);
       }
       const double BM = bq / (double)(J - 1);
-      const double S0 = S(0);
-      W = S0 / ((double)J * (double)(M - 1));
-      vp = W * (double)(M - 1) / (double)M + BM;
       const double nan = __longlong_as_double(0x7ff8000000000000LL);
-      if (S0 != S0 || BM != BM) {  // a NaN draw somewhere in the element
+      const int kind = geyer_start(g, S(0), BM, J, M, S);
+      if (kind != GEYER_GO) {  // a NaN draw somewhere in the element, or every draw equal
         if (rhat_out) rhat_out[k] = nan;
-        if (ess_out) ess_out[k] = nan;
+        if (ess_out) ess_out[k] = kind == GEYER_NAN ? nan : JM;
         if (lag_out) lag_out[k] = 0;
         go = false;
-      } else if (W == 0.0 && BM == 0.0) {  // every draw equal
-        if (rhat_out) rhat_out[k] = nan;
-        if (ess_out) ess_out[k] = JM;
-        if (lag_out) lag_out[k] = 0;
-        go = false;
-      } else {
-        if (rhat_out) rhat_out[k] = sqrt(vp / W);  // +inf when W == 0 < B_M
-        even = 1.0;
-        odd = 1.0 - (W - S(1) / JM) / vp;
+      } else if (rhat_out) {
+        rhat_out[k] = sqrt(g.vp / g.W);  // +inf when W == 0 < B_M
       }
     } else {
       go = st[7 * size + k] != 0.0;
-      W = st[k]; vp = st[size + k]; even = st[2 * size + k]; odd = st[3 * size + k];
-      acc = st[4 * size + k]; minq = st[5 * size + k]; pp = st[6 * size + k];
+      g.W = st[k]; g.vp = st[size + k]; g.even = st[2 * size + k]; g.odd = st[3 * size + k];
+      g.acc = st[4 * size + k]; g.minq = st[5 * size + k]; g.pp = st[6 * size + k];
     }
     if (go) {
-      for (;;) {
-        const int64_t p = (int64_t)pp + 1;  // next pair: rho(2p), rho(2p + 1), evaluated while t = 2p - 1 < M - 3 and the last sum > 0
-        if (!(2 * p - 1 < M - 3 && even + odd > 0.0)) { finished = true; break; }
-        if (2 * p + 1 >= t0 + nl) break;  // its lags belong to the next block
-        const double q = pp == 0.0 ? even + odd : fmin(even + odd, minq);  // the monotone step: running minimum of the pair sums
-        acc += q;
-        minq = q;
-        even = 1.0 - (W - S(2 * p) / JM) / vp;
-        odd = 1.0 - (W - S(2 * p + 1) / JM) / vp;
-        pp = (double)p;
-      }
-      if (finished) {
-        // the last evaluated pair enters through r[max_t + 1] = r[2 pp] only: even if it was written (sum >= 0) or positive
-        const double rlast = (even + odd >= 0.0 || even > 0.0) ? even : 0.0;
-        double tau = -1.0 + 2.0 * acc + rlast;
-        const double floor_tau = 1.0 / log10(JM);
-        if (!(tau >= floor_tau)) tau = floor_tau;
-        if (ess_out) ess_out[k] = JM / tau;
-        if (lag_out) lag_out[k] = (int32_t)(2 * (int64_t)pp);
+      if (geyer_advance(g, M, JM, t0 + nl, S)) {
+        double ess;
+        int32_t lags;
+        geyer_finish(g, JM, ess, lags);
+        if (ess_out) ess_out[k] = ess;
+        if (lag_out) lag_out[k] = lags;
       } else {
         active = true;
       }
     }
-    st[k] = W; st[size + k] = vp; st[2 * size + k] = even; st[3 * size + k] = odd;
-    st[4 * size + k] = acc; st[5 * size + k] = minq; st[6 * size + k] = pp; st[7 * size + k] = active ? 1.0 : 0.0;
+    st[k] = g.W; st[size + k] = g.vp; st[2 * size + k] = g.even; st[3 * size + k] = g.odd;
+    st[4 * size + k] = g.acc; st[5 * size + k] = g.minq; st[6 * size + k] = g.pp; st[7 * size + k] = active ? 1.0 : 0.0;
   }
   const bool any = __ballot(active) != 0;
   if (threadIdx.x == 0) {

@@ -1407,6 +1407,65 @@ class Engine:
                                              self._p(rhat), self._p(bulk), self._p(tail)))
         return rhat, bulk, tail
 
+    def store_ess_indicator(self, store, prob_lo, prob_hi, index=None, counts=0, algo=0):
+        """Effective sample size of indicator series of every selected element of a device store (n_iter, C, size), on the
+        device (omc_store_ess_indicator): ArviZ's ess(method="quantile") and ess(method="local").  prob_lo, prob_hi: equally long
+        sequences; prob_lo[i] < 0 (or None for all) means no lower end, I = (x <= q_hi), else 0 <= lo <= hi <= 1 and
+        I = (q_lo <= x <= q_hi), q the np.quantile of the element's split draws.  Returns (ess, lags, q[, counts]) as device
+        tensors: ess fp64 (n_p, n_idx), lags int32 (n_p, n_idx), q fp64 (n_p, n_idx, 2) the thresholds (NaN: no lower end), and
+        with counts = n_cnt > 0 the exact integers int64 (n_p, n_idx, 2 + 2 n_cnt) = Nn, Q, then the pairs A(t), H(t), t < n_cnt
+        <= n_iter // 2 (include/omcmc_hip.h).  Intervals beyond 32 go in groups of 32.  algo: 0 auto, 1 bits in LDS, 2 bits in
+        global memory -- same bits.  n_iter >= 4; an element with a NaN or infinite draw gives NaN."""
+        torch = _torch()
+        n_iter, size = self._store_shape(store)
+        if n_iter < 4:
+            raise ValueError("the ESS of an indicator needs at least 4 stored iterations")
+        hi = np.ascontiguousarray(np.atleast_1d(np.asarray(prob_hi, dtype=np.float64)))
+        lo = np.full(hi.shape, -1.0) if prob_lo is None else np.ascontiguousarray(np.atleast_1d(np.asarray(prob_lo, dtype=np.float64)))
+        if hi.ndim != 1 or hi.size < 1 or lo.shape != hi.shape:
+            raise ValueError("prob_lo and prob_hi must be equally long non-empty one-dimensional sequences")
+        n_cnt = int(counts)
+        idx, n = self._store_index(index, size)
+        n_p = hi.size
+        ess, q = self.empty(n_p, n), self.empty(n_p, n, 2)
+        lags = torch.empty((n_p, n), dtype=torch.int32, device=self.device)
+        cnt = torch.empty((n_p, n, 2 + 2 * n_cnt), dtype=torch.int64, device=self.device) if n_cnt > 0 else None
+        dp = C.POINTER(C.c_double)
+        for i in range(0, n_p, 32):  # at most 32 intervals per call of omc_store_ess_indicator
+            m = min(32, n_p - i)
+            check(lib.omc_store_ess_indicator(self._ctx, n_iter, size, self._p(store), _ptr(idx), n,
+                                              lo[i: i + m].ctypes.data_as(dp), hi[i: i + m].ctypes.data_as(dp), m, int(algo),
+                                              self._p(ess[i: i + m]), lags[i: i + m].data_ptr(), self._p(q[i: i + m]),
+                                              cnt[i: i + m].data_ptr() if cnt is not None else None, n_cnt))
+        return (ess, lags, q, cnt) if cnt is not None else (ess, lags, q)
+
+    def store_order_stats(self, store, pos, index=None, split=True):
+        """Order statistics of every selected element of a device store (n_iter, C, size) at given positions, on the device
+        (omc_store_order_stats): a device tensor (n_idx, n_pos) = np.sort(column)[pos[e]], the column being the element's split
+        draws (split=True: first and last n_iter // 2 iterations of every chain, n_iter >= 4) or all n_iter * C draws.  pos:
+        integers (n_idx, n_pos), a host array or a device tensor; a position outside the column raises ValueError.  An element
+        with a NaN draw gives NaN; a zero comes back as +0.0."""
+        torch = _torch()
+        n_iter, size = self._store_shape(store)
+        if n_iter < (4 if split else 1):
+            raise ValueError("split order statistics need at least 4 stored iterations")
+        idx, n = self._store_index(index, size)
+        if isinstance(pos, torch.Tensor):
+            if pos.is_floating_point() or pos.dtype is torch.bool:
+                raise ValueError("pos must hold integers")
+            p = pos.to(device=self.device, dtype=torch.int64).contiguous()
+        else:
+            arr = np.asarray(pos)
+            if arr.dtype.kind not in "iu":
+                raise ValueError("pos must hold integers")
+            p = torch.tensor(np.ascontiguousarray(arr, dtype=np.int64), dtype=torch.int64, device=self.device)
+        if p.dim() != 2 or p.shape[0] != n or p.shape[1] < 1:
+            raise ValueError(f"pos must be (number of selected elements = {n}, n_pos), got shape {tuple(p.shape)}")
+        out = self.empty(n, p.shape[1])
+        check(lib.omc_store_order_stats(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, int(bool(split)),
+                                        p.data_ptr(), p.shape[1], self._p(out)))
+        return out
+
     def store_hdi(self, store, prob, index=None, pooled=True, omit_nan=True):
         """Highest-density intervals of every selected element of a device store (n_iter, C, size), on the device
         (omc_store_hdi): (hdi, n_valid) as device tensors.  hdi is fp64 (n_prob, n_idx, 2) pooled over chains and iterations,

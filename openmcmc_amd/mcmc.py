@@ -399,6 +399,135 @@ class MCMC:
         rhat, bulk, tail = self.engine.store_rank_diagnostics(self._store_3d(key), index=index)
         return {"rhat": rhat.cpu().numpy(), "ess_bulk": bulk.cpu().numpy(), "ess_tail": tail.cpu().numpy()}
 
+    def _selected_columns(self, key, index):
+        """(store (n_iter, C, size), selection as a host int64 array or None, n_idx); an entry outside [0, size) raises"""
+        t = self._store_3d(key)
+        if index is None:
+            return t, None, t.shape[2]
+        idx, n = self.engine._store_index(index, t.shape[2])
+        cols = idx.cpu().numpy()
+        if cols.min() < 0 or cols.max() >= t.shape[2]:
+            raise ValueError(f"index outside [0, {t.shape[2]})")
+        return t, cols, n
+
+    def _column_chunks(self, t, cols, n):
+        """(first, last, contiguous sub-store (n_iter, C, last - first)) over the selected columns, each at most 1 GiB"""
+        import torch
+
+        step = max(1, (1 << 30) // (8 * t.shape[0] * t.shape[1]))
+        for a in range(0, n, step):
+            b = min(n, a + step)
+            if cols is None:
+                yield a, b, (t if (a, b) == (0, t.shape[2]) else t[:, :, a:b].contiguous())
+            else:
+                yield a, b, t.index_select(2, torch.as_tensor(cols[a:b], device=t.device)).contiguous()
+
+    def _mean_sd_ess(self, key, index, squared):
+        """pooled mean, pooled sd (ddof 1) and E(.) of omc_store_rhat_ess -- of the draws, or with `squared` of (x - pooled mean)^2
+        -- of the selected columns, as host arrays (n_idx,)"""
+        t, cols, n = self._selected_columns(key, index)
+        mean, sd, ess = np.empty(n), np.empty(n), np.empty(n)
+        for a, b, sub in self._column_chunks(t, cols, n):
+            m, v = self.engine.store_moments(sub, pooled=True)
+            if squared:
+                sub = (sub - m).square_()  # the chunk's one temporary
+            mean[a:b], sd[a:b] = m.cpu().numpy(), np.sqrt(v.cpu().numpy())
+            ess[a:b] = self.engine.store_rhat_ess(sub)[1].cpu().numpy()
+        return mean, sd, ess
+
+    @staticmethod
+    def _probs(prob, method):
+        """(prob_lo or None, prob_hi, squeeze) of the `prob` of ess / mcse"""
+        if prob is None:
+            raise ValueError(f'method="{method}" needs prob')
+        p = np.asarray(prob, dtype=np.float64)
+        if method == "local":
+            if p.ndim not in (1, 2) or p.shape[-1] != 2 or p.size < 2:
+                raise ValueError('method="local" takes prob = (lo, hi) or a sequence of such pairs')
+            pairs = p.reshape(-1, 2)
+            if not np.all((pairs[:, 0] >= 0) & (pairs[:, 0] <= pairs[:, 1]) & (pairs[:, 1] <= 1)):
+                raise ValueError("every pair must satisfy 0 <= lo <= hi <= 1")
+            return pairs[:, 0].copy(), pairs[:, 1].copy(), p.ndim == 1
+        if p.ndim > 1 or p.size < 1:
+            raise ValueError("prob must be a number or a non-empty one-dimensional sequence")
+        flat = np.atleast_1d(p)
+        if not np.all((flat >= 0) & (flat <= 1)):
+            raise ValueError("every prob must lie inside [0, 1]")
+        return None, flat, p.ndim == 0
+
+    def ess(self, key, method="bulk", prob=None, index=None):
+        """Effective sample size of store[key], computed on the device (no gather of the store): the family of ArviZ's
+        az.ess(method=...), a host array (n_idx,).  "bulk" and "tail" are those of `rank_diagnostics`; "mean" the ESS of the
+        draws (`diagnostics`); "sd" that of (x - pooled mean)^2; "quantile" the ESS of the indicator x <= q_prob -- whether a
+        reported quantile has converged --, with prob a number or a sequence (then (n_prob, n_idx)); "median" is quantile 0.5;
+        "local" the ESS of q_lo <= x <= q_hi for prob = (lo, hi) or a sequence of pairs (then (n_pairs, n_idx)): np.linspace
+        pairs give the profile of az.plot_ess(kind="local"), twenty probabilities that of kind="quantile".  The quantiles are
+        np.quantile of the split draws (first and last n_iter // 2 iterations of every chain).  index selects elements (in that
+        order, repeats allowed); a 2-D entry ("log_post") counts as one element.  An element with a NaN or infinite draw gives
+        NaN.  "quantile", "median", "local", "bulk" and "tail" sort every element: meant for the elements one inspects.  Under
+        a sharded multi-GPU run these are this rank's chains only."""
+        self._whole_store_on_device("ess")
+        if method in ("bulk", "tail"):
+            return self.rank_diagnostics(key, index=index)["ess_" + method]
+        if method in ("mean", "sd"):
+            return self._mean_sd_ess(key, index, squared=method == "sd")[2]
+        if method == "median":
+            prob = 0.5
+        elif method not in ("quantile", "local"):
+            raise ValueError(f"unknown method {method!r}: one of bulk, tail, mean, sd, quantile, median, local")
+        lo, hi, squeeze = self._probs(prob, method)
+        out = self.engine.store_ess_indicator(self._store_3d(key), lo, hi, index=index)[0].cpu().numpy()
+        return out[0] if squeeze else out
+
+    def mcse(self, key, method="mean", prob=None, index=None):
+        """Monte Carlo standard error of a posterior summary of store[key], computed on the device (no gather of the store): the
+        family of ArviZ's az.mcse(method=...), a host array (n_idx,).  "mean": sd / sqrt(ess_mean), sd the pooled standard
+        deviation (ddof 1); "sd": sd sqrt(e (1 - 1 / ess_sd)^(ess_sd - 1) - 1); "quantile" (prob a number, or a sequence: then
+        (n_prob, n_idx)) and "median": half the distance between the order statistics of the split draws at the 16 % and 84 %
+        points of Beta(ess p + 1, ess (1 - p) + 1), ess = ess(method="quantile", prob=p) -- the beta quantiles on the host, the
+        order statistics on the device.  index as in `ess`.  An element with a NaN or infinite draw gives NaN.  Under a sharded
+        multi-GPU run these are this rank's chains only."""
+        self._whole_store_on_device("mcse")
+        if method in ("mean", "sd"):
+            _, sd, ess = self._mean_sd_ess(key, index, squared=method == "sd")
+            if method == "mean":
+                return sd / np.sqrt(ess)
+            return sd * np.sqrt(np.exp(1.0) * (1.0 - 1.0 / ess) ** (ess - 1.0) - 1.0)
+        if method == "median":
+            prob = 0.5
+        elif method != "quantile":
+            raise ValueError(f"unknown method {method!r}: one of mean, sd, quantile, median")
+        from scipy import stats
+
+        _, p, squeeze = self._probs(prob, method)
+        t = self._store_3d(key)
+        S = 2 * t.shape[1] * (t.shape[0] // 2)
+        ess = self.engine.store_ess_indicator(t, None, p, index=index)[0].cpu().numpy()  # (n_p, n_idx)
+        bad = ~np.isfinite(ess)
+        e = np.where(bad, 1.0, ess)
+        a = stats.beta.ppf(0.1586553, e * p[:, None] + 1, e * (1 - p[:, None]) + 1)
+        b = stats.beta.ppf(0.8413447, e * p[:, None] + 1, e * (1 - p[:, None]) + 1)
+        lower = np.floor(np.maximum(a * S - 1, 0)).astype(np.int64)
+        upper = np.ceil(np.minimum(b * S - 1, S - 1)).astype(np.int64)
+        pos = np.ascontiguousarray(np.concatenate([lower, upper], axis=0).T)  # (n_idx, 2 n_p)
+        x = self.engine.store_order_stats(t, pos, index=index, split=True).cpu().numpy().T  # (2 n_p, n_idx)
+        out = (x[p.size:] - x[:p.size]) / 2
+        out[bad] = np.nan
+        return out[0] if squeeze else out
+
+    def summarize(self, key, index=None, hdi_prob=0.94):
+        """The columns of az.summary for store[key], computed on the device (no gather of the store): a dict of host arrays
+        (n_idx,) -- "mean", "sd" (pooled, ddof 1), "hdi_lo", "hdi_hi" (`hdi` at hdi_prob), "mcse_mean", "mcse_sd" (`mcse`),
+        "ess_bulk", "ess_tail", "r_hat" (`rank_diagnostics`).  index as in `ess`.  Under a sharded multi-GPU run these are this
+        rank's chains only."""
+        self._whole_store_on_device("summarize")
+        mean, sd, ess_mean = self._mean_sd_ess(key, index, squared=False)
+        hdi = self.hdi(key, prob=float(hdi_prob), index=index)
+        rank = self.rank_diagnostics(key, index=index)
+        return {"mean": mean, "sd": sd, "hdi_lo": hdi[:, 0], "hdi_hi": hdi[:, 1], "mcse_mean": sd / np.sqrt(ess_mean),
+                "mcse_sd": self.mcse(key, method="sd", index=index), "ess_bulk": rank["ess_bulk"], "ess_tail": rank["ess_tail"],
+                "r_hat": rank["rhat"]}
+
     def ranks(self, key, index=None, split=False):
         """Average ranks of the stored draws of every selected element of store[key] among all chains and iterations
         (scipy.stats.rankdata(method="average") per element), computed on the device: a host array (n_iter, C, n_idx), the
