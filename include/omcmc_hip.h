@@ -906,6 +906,47 @@ omc_status omc_store_histogram(omc_ctx* ctx, int64_t n_iter, int64_t size, const
  * element's counters (words), byte offsets of the edges, the counters and the outside counts, end of the image = bytes launched,
  * the budget the tile was chosen for, threads of a workgroup}.                                                           */
 omc_status omc_store_histogram_layout(int32_t n_bins, int32_t edges_per_element, int32_t* out);
+/* Kernel density estimate, bandwidth and mode of n_cols columns from their bin counts: what scipy.stats.gaussian_kde / ArviZ's kde
+ * give for a column of MCMC.store[param] on the host (mcmc.py:105-111 of the reference), from counts such as
+ * omc_store_histogram's over evenly spaced edges.  Everything is a function of (counts, lo, hi) alone: counts added over ranks
+ * (same edges) give the estimate of all ranks' chains.  All arrays on the device.
+ *   counts  int64 [n_cols][G], 8 <= G <= 1024 (else OMC_INVALID_ARG); lo, hi [n_cols] the grid [a, b] of every column.
+ *           delta = (b - a) / G, grid points g_j = a + (j + 1/2) delta (the bin centres), N = sum_j c_j, p_j = c_j / N.
+ *   rule    0 given: h = bw_in[col] (bw_in NULL is OMC_INVALID_ARG); else from the binned moments m = sum p_j g_j,
+ *           sd^2 = N / (N - 1) sum p_j (g_j - m)^2 and the binned quantile q(u) = a + delta (j + (u N - C_j) / c_j), C_j the exclusive
+ *           prefix sum of c and j the first bin with C_j + c_j >= u N (exact integers), IQR = q(3/4) - q(1/4):
+ *           1 Scott      h = 1.06 sd N^(-1/5);
+ *           2 Silverman  h = 0.9 min(sd, IQR / 1.34) N^(-1/5), sd alone when IQR == 0;
+ *           3 ISJ, the improved Sheather-Jones rule of Botev, Grotowski and Kroese (2010): a_k = sum_j p_j cos(pi k (2 j + 1) / (2 G)),
+ *             k = 1..G-1, the cosine from a table of cos(pi m / (2 G)) by the exact integer k (2 j + 1) mod 4 G;
+ *             f_s(t) = 2 pi^(2 s) sum_k k^(2 s) a_k^2 exp(-k^2 pi^2 t); from f_7(t), for s = 6..2:
+ *             t_s = (2 c_s kappa_s / (N f_(s+1)))^(2 / (3 + 2 s)), c_s = (1 + 2^-(s + 1/2)) / 3, kappa_s = 1 3 .. (2 s - 1) / sqrt(2 pi),
+ *             f_s(t_s); Phi(t) = t - (2 N sqrt(pi) f_2(t_2))^(-2/5).  The root: Phi at t_i = 2^(-(6 + i) / 2), i = 0..46, from the
+ *             largest t down; the first adjacent pair, both finite, of opposite signs (>= 0 counts as positive); exactly 60
+ *             bisection steps, the midpoint replacing the end whose sign it shares (steps after the ends have met in fp64 change
+ *             nothing and are not run); t* the midpoint of what is left;
+ *             h = sqrt(t*) (b - a).  Without such a pair h is Silverman's and the column's flag is 1;
+ *           4 experimental: the mean of Silverman's and ISJ's (ArviZ's default), flag 1 when ISJ fell back.
+ *           Every rule's h is multiplied by bw_fct (finite and > 0, else OMC_INVALID_ARG).
+ *   density_out [n_cols][G]: f(g_k) = 1 / (N h) sum_j c_j [phi((g_k - g_j) / h) + R_lo + R_hi], phi the standard normal density, no
+ *           truncation; reflect bit 0: the grid starts at a lower bound, R_lo = phi((k + j + 1) delta / h), the image of g_j
+ *           mirrored at a; bit 1: it ends at an upper bound, R_hi = phi((2 G - 1 - k - j) delta / h); else 0.  phi comes from a table
+ *           exp(-(d delta / h)^2 / 2), d = 0..2 G - 1: every distance is an integer multiple of delta.
+ *   bw_out [n_cols] the h used; mode_out [n_cols] the grid point of the largest density, the lowest of equals;
+ *   flag_out int32 [n_cols]: 0 ok; 1 ISJ fell back to Silverman; 2 degenerate -- density, bw and mode NaN, other columns
+ *           unaffected: hi <= lo or an end not finite; under a rule N < 2 or fewer than two non-empty bins; under rule 0 N == 0 or
+ *           a bandwidth that is not finite and positive.  Any output may be NULL.
+ *   A negative count is OMC_INVALID_ARG, found on the device before anything is written (one word read back); the outputs are
+ *   untouched by every OMC_INVALID_ARG.  N is exact below 2^53.
+ * One workgroup per column (one wave up to 128 bins, four above: the choice depends on G alone and both add in the same order);
+ * every sum runs in an order that G alone fixes, no atomics: repeated calls are bit-equal.  Runs on the context's stream.     */
+omc_status omc_kde_binned(omc_ctx* ctx, int64_t n_cols, int32_t G, const int64_t* counts, const double* lo, const double* hi,
+                          int32_t rule, const double* bw_in, double bw_fct, int32_t reflect, double* density_out, double* bw_out,
+                          int32_t* flag_out, double* mode_out);
+/* [host, no GPU] The LDS image of omc_kde_binned's kernel at G bins (8..1024, else OMC_INVALID_ARG): out[8] = {threads of a
+ * workgroup, byte offsets of the counts [G], of A2 [G], of the quarter-wave cosines [G + 1], of the Gaussian table [2 G] and of the
+ * block sums [64] (all doubles), end of the image = bytes launched, the budget}.                                          */
+omc_status omc_kde_layout(int32_t G, int32_t* out);
 /* Joint histogram of pairs of elements of the same store(s): np.histogram2d(x, y, bins=[edges_x, edges_y]) of two rows of the
  * reference's host arrays MCMC.store[param] (mcmc.py:105-111), for all pairs at once; layout conventions of omc_store_histogram.
  *   store_x [n_iter][C][size_x], store_y [n_iter][C][size_y] (device): the same tensor or two; pair k = (element idx_x[k] of

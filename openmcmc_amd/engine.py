@@ -1305,6 +1305,56 @@ class Engine:
                                       int(bool(pooled)), n_bins, e.data_ptr(), int(e.dim() == 2), counts.data_ptr(), outside.data_ptr()))
         return counts, outside
 
+    KDE_RULES = {"given": 0, "scott": 1, "silverman": 2, "isj": 3, "experimental": 4}
+
+    @staticmethod
+    def kde_layout(n_bins):
+        """The eight numbers of omc_kde_layout: threads of a workgroup, byte offsets of the counts, A2, the quarter-wave cosines,
+        the Gaussian table and the block sums, bytes launched, the budget (openmcmc_amd/csrc/omc_kde_layout.h; needs no GPU)."""
+        out = (C.c_int32 * 8)()
+        check(lib.omc_kde_layout(int(n_bins), out))
+        return list(out)
+
+    def kde_binned(self, counts, lo, hi, rule="experimental", bw=None, bw_fct=1.0, reflect=(False, False)):
+        """Kernel density estimates from bin counts, on the device (omc_kde_binned): counts int64 (.., G), 8 <= G <= 1024, over G
+        evenly spaced bins of [lo, hi] (lo, hi fp64 of the leading shape) -> (density (.., G) at the bin centres, bw, mode, flag
+        int32), device tensors.  rule: "scott", "silverman", "isj" (improved Sheather-Jones), "experimental" (the mean of the last
+        two, ArviZ's default) or "given" with bw, a tensor of the leading shape; every bandwidth is multiplied by bw_fct.
+        reflect=(lower, upper): the grid starts / ends at a bound of the support and the mass beyond it is mirrored back.
+        flag: 0 ok, 1 ISJ found no root and Silverman's bandwidth stands in, 2 degenerate (NaN outputs; the other columns are not
+        affected).  The estimate is a function of (counts, lo, hi) alone: under a sharded run all-reduce the counts taken over
+        the same edges and make one call -- that is the KDE of all ranks' chains.  Repeated calls are bit-equal."""
+        torch = _torch()
+        if rule not in self.KDE_RULES:
+            raise ValueError(f"rule must be one of {sorted(self.KDE_RULES)}")
+        if not isinstance(counts, torch.Tensor) or counts.dtype is not torch.int64 or not counts.is_cuda or counts.dim() < 1:
+            raise TypeError("counts must be an int64 ROCm tensor (.., G)")
+        counts = counts.contiguous()
+        lead, G = tuple(counts.shape[:-1]), counts.shape[-1]
+        if not 8 <= G <= 1024:
+            raise ValueError("between 8 and 1024 bins")
+        n_cols = int(np.prod(lead, dtype=np.int64))
+        if n_cols < 1:
+            raise ValueError("no column")
+
+        def column(v, what):
+            v = self.to_device(v)
+            if tuple(v.shape) != lead:
+                raise ValueError(f"{what} must have the leading shape of counts, {lead}")
+            return v
+
+        lo, hi = column(lo, "lo"), column(hi, "hi")
+        if (rule == "given") != (bw is not None):
+            raise ValueError('bw goes with rule="given"')
+        bw_in = None if bw is None else column(bw, "bw")
+        density = torch.empty(lead + (G,), dtype=torch.float64, device=self.device)
+        bw_out, mode = (torch.empty(lead, dtype=torch.float64, device=self.device) for _ in range(2))
+        flag = torch.empty(lead, dtype=torch.int32, device=self.device)
+        check(lib.omc_kde_binned(self._ctx, n_cols, G, counts.data_ptr(), self._p(lo), self._p(hi), self.KDE_RULES[rule],
+                                 self._p(bw_in), float(bw_fct), int(bool(reflect[0])) | 2 * int(bool(reflect[1])),
+                                 self._p(density), self._p(bw_out), flag.data_ptr(), self._p(mode)))
+        return density, bw_out, mode, flag
+
     @staticmethod
     def hist2d_tile(nx, ny, per_pair=False, pool_pairs=False):
         """(TE, RB) of omc_store_histogram2d at an nx x ny grid: a workgroup counts a tile of TE consecutive pairs (1 with

@@ -1084,6 +1084,70 @@ class MCMC:
             hist = hist / np.diff(edges, axis=-1) / hist.sum(axis=-1, keepdims=True)  # (np.histogram's order of operations)
         return hist, edges
 
+    def kde(self, key, index=None, pooled=True, grid_len=512, bw="experimental", bw_fct=1.0, extend=0.1, bounds=None):
+        """Kernel density estimate of the marginal posterior of every selected element of store[key] -- the curve of
+        az.plot_posterior / plot_density -- from one histogram pass over the store and a per-element kernel on the device (no
+        gather): a dict of host arrays "grid" (.., G), "density" (.., G), "bw", "mode", "flag" (int32), "n" (draws counted) and
+        "outside" (draws left out: NaN, or beyond a bound), the leading shape (n_idx,) pooled over chains and iterations, else
+        (C, n_idx).  G = grid_len (8..1024).  The grid of an element spans its minimum and maximum over ALL chains (also with
+        pooled=False, so that its chains share a grid), widened by extend (max - min) either way; an element that never moved
+        is widened by 0.5 as `histogram` does and comes out with flag 2 under a bandwidth rule.  bounds=(L, U), either may be
+        None, are the ends of the parameter's support: the grid is clamped to and starts (ends) exactly at a bound, and the mass
+        a Gaussian kernel would put beyond it is reflected back.  The draws are counted into the G bins with the edges
+        np.linspace(a, b, G + 1) (counts equal np.histogram(x, G, (a, b))); "grid" holds the bin centres, the midpoints of
+        neighbouring edges; the density is the binned Gaussian convolution at those centres.  bw: "experimental" (ArviZ's
+        default: the mean of Silverman's rule and the improved Sheather-Jones rule), "isj", "silverman", "scott", or a
+        bandwidth -- a float or an (n_idx,) array; every bandwidth is multiplied by bw_fct.  "mode" is the grid point of the
+        largest density (the lowest of equal ones).  flag: 0 ok; 1 the Sheather-Jones equation had no root and Silverman's
+        bandwidth stands in; 2 degenerate (fewer than two draws or than two non-empty bins; density, bw and mode are NaN).
+        NaN draws (the padding of variable-size parameters) are left out; an infinite draw raises ValueError as in
+        `histogram`.  index selects elements (in that order, repeats allowed); a 2-D entry ("log_post") counts as one
+        element.  Under a sharded multi-GPU run this covers this rank's chains only; the estimate is a function of the counts
+        and the grid alone, so counts of several ranks over the same edges can be added and handed to `engine.kde_binned`, which
+        gives the estimate of all ranks' chains."""
+        self._whole_store_on_device("kde")
+        t = self._store_3d(key)
+        G = int(grid_len)
+        if G != grid_len or not 8 <= G <= 1024:
+            raise ValueError("grid_len must be an integer between 8 and 1024")
+        if not (np.ndim(extend) == 0 and extend >= 0 and np.isfinite(extend)):
+            raise ValueError("extend must be a finite non-negative number")
+        L, U = (None, None) if bounds is None else bounds
+        mn, mx, cnt = (v.cpu().numpy() for v in self.engine.store_minmax(t, index=index, pooled=True))
+        lo, hi = np.where(cnt > 0, mn, 0.0), np.where(cnt > 0, mx, 1.0)
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+            raise ValueError("autodetected range is not finite")
+        same = lo == hi
+        pad = extend * (hi - lo)
+        a, b = np.where(same, lo - 0.5, lo - pad), np.where(same, hi + 0.5, hi + pad)
+        if L is not None:
+            a = np.full_like(a, float(L))
+        if U is not None:
+            b = np.full_like(b, float(U))
+        if not (np.isfinite(a).all() and np.isfinite(b).all() and (a < b).all()):
+            raise ValueError("bounds leave an element without a range")
+        n_idx = a.shape[0]
+        edges = np.stack([np.linspace(x, y, G + 1) for x, y in zip(a, b)])
+        counts, outside = self.engine.store_histogram(t, edges, index=index, pooled=pooled)
+        lead = tuple(counts.shape[:-1])
+        rule, given = bw, None
+        if not isinstance(bw, str):
+            if np.ndim(bw) > 1 or (np.ndim(bw) == 1 and len(bw) != n_idx):
+                raise ValueError("bw must be a rule's name, a float or an (n_idx,) array")
+            rule, given = "given", np.array(np.broadcast_to(np.asarray(bw, dtype=np.float64), lead))
+        density, h, mode, flag = self.engine.kde_binned(counts, np.array(np.broadcast_to(a, lead)),
+                                                        np.array(np.broadcast_to(b, lead)), rule=rule, bw=given,
+                                                        bw_fct=bw_fct, reflect=(L is not None, U is not None))
+        grid = 0.5 * (edges[:, :-1] + edges[:, 1:])
+        return {"grid": np.ascontiguousarray(np.broadcast_to(grid, lead + (G,))), "density": density.cpu().numpy(),
+                "bw": h.cpu().numpy(), "mode": mode.cpu().numpy(), "flag": flag.cpu().numpy(),
+                "n": counts.sum(dim=-1).cpu().numpy(), "outside": outside.sum(dim=-1).cpu().numpy()}
+
+    def mode(self, key, index=None, pooled=True, **kde_args):
+        """Posterior mode of every selected element of store[key]: the grid point of the largest kernel density estimate,
+        kde(key, index=index, pooled=pooled, **kde_args)["mode"] -- what az.plot_posterior(point_estimate="mode") shows."""
+        return self.kde(key, index=index, pooled=pooled, **kde_args)["mode"]
+
     def exceedance(self, key, thresholds, index=None, pooled=True):
         """P(x > t) of every selected element of store[key] for every threshold t, from one histogram pass on the device:
         (n_t, n_idx) pooled over chains and iterations, else (n_t, C, n_idx).  The numerator counts the draws strictly greater
