@@ -4,7 +4,7 @@
     bash benchmarks/build_rev.sh HEAD~1 before
     python3 benchmarks/store_ab.py [--before build/ab/libomcmc_hip_before.so] [--rounds 5] [--out FILE] [script ...]
 
-Per script (default: the eight benchmarks/store_*.py of the summaries) the two builds run alternately -- before, after, before,
+Per script (default: the fourteen benchmarks/store_*.py of the summaries) the two builds run alternately -- before, after, before,
 after, ... -- one fresh process per run, the other build through OMC_HIP_LIB.  A case is every timing in milliseconds of the
 script's JSON line that the library produces (host, numpy and torch routes are left out).  Per case: the median of either side and
 the spread (max - min over the rounds) of the BEFORE side; the case passes when the median after is not above the median before
@@ -20,7 +20,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCRIPTS = ["store_covariance.py", "store_hdi.py", "store_rank_diagnostics.py", "store_histogram.py", "store_histogram2d.py",
-           "store_derive.py", "store_summaries.py", "store_diagnostics.py"]
+           "store_derive.py", "store_summaries.py", "store_diagnostics.py", "store_autocorr.py", "store_project.py", "store_loo.py",
+           "store_loo_expect.py", "store_ess.py", "store_kde.py"]
 NOT_OURS = re.compile(r"host|numpy|torch|wall|mcmc_|(^|[/_ ])gram|scipy|arviz", re.I)
 
 

@@ -69,7 +69,7 @@ def main():
             for ev in prof.events():
                 name = ev.name
                 us = float(ev.device_time_total if hasattr(ev, "device_time_total") else ev.cuda_time_total)
-                for stage, pieces in (("sort", ("k_essq_gather", "k_rank_sort")), ("thresholds", ("k_essq_thresholds",)),
+                for stage, pieces in (("sort", ("k_rank_gather", "k_rank_sort")), ("thresholds", ("k_essq_thresholds",)),
                                       ("pack", ("k_essq_pack",)), ("lags", ("k_essq_lags",))):
                     if any(p in name for p in pieces):
                         split[stage] += us / 1e3

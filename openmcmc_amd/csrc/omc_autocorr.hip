@@ -188,33 +188,28 @@ __global__ void __launch_bounds__(256) k_acorr_tau(AcArgs a) {
   if (a.window_out) a.window_out[at] = window;
 }
 
-omc_status ac_invalid(const char* text) {
-  omc_set_error_text(text);
-  return OMC_INVALID_ARG;
-}
-
 }  // namespace
 
 extern "C" omc_status omc_store_autocorr(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                                          int64_t max_lag, int32_t per_chain, int32_t normalize, double* acf_out, double* tau_out,
                                          int32_t* window_out, double* mean_out) {
-  if (!ctx) return ac_invalid("omc_store_autocorr: no context");
-  if (n_iter < 2) return ac_invalid("omc_store_autocorr: n_iter < 2");
-  if (size < 1) return ac_invalid("omc_store_autocorr: size < 1");
-  if (!store || !acf_out) return ac_invalid("omc_store_autocorr: store and acf_out must not be NULL");
-  if (n_idx < 1 || (!idx && n_idx != size)) return ac_invalid("omc_store_autocorr: n_idx < 1, or no index and n_idx != size");
-  if (max_lag < 0 || max_lag > n_iter - 1) return ac_invalid("omc_store_autocorr: max_lag outside [0, n_iter - 1]");
+  if (!ctx) return omc_invalid("omc_store_autocorr: no context");
+  if (n_iter < 2) return omc_invalid("omc_store_autocorr: n_iter < 2");
+  if (size < 1) return omc_invalid("omc_store_autocorr: size < 1");
+  if (!store || !acf_out) return omc_invalid("omc_store_autocorr: store and acf_out must not be NULL");
+  if (n_idx < 1 || (!idx && n_idx != size)) return omc_invalid("omc_store_autocorr: n_idx < 1, or no index and n_idx != size");
+  if (max_lag < 0 || max_lag > n_iter - 1) return omc_invalid("omc_store_autocorr: max_lag outside [0, n_iter - 1]");
   const int64_t N = n_iter, C = ctx->n_chains, L = max_lag;
   const int64_t rps = ctx->autocorr_slice > 0 ? ctx->autocorr_slice : A_SLICE;
   const int64_t n_slices = (N + rps - 1) / rps, n_lb = L / A_L + 1;
-  if (n_slices > 65535 || n_lb > 65535) return ac_invalid("omc_store_autocorr: more time slices or blocks of lags than one launch takes (65535)");
+  if (n_slices > 65535 || n_lb > 65535) return omc_invalid("omc_store_autocorr: more time slices or blocks of lags than one launch takes (65535)");
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   int64_t pre_rows = A_PRE;
   if ((N + pre_rows - 1) / pre_rows > 65535) pre_rows = (N + 65534) / 65535;
   const size_t per_col = ((size_t)n_slices * n_lb * A_L + (size_t)(L + 1) + (idx ? (size_t)N : 0)) * sizeof(double) + sizeof(int32_t);
   const int64_t Kc = rank_chunk(ctx, per_col * (size_t)C, n_idx);
   const int64_t W_max = C * Kc;
-  if ((W_max + 31) / 32 > 0x7fffffffLL) return ac_invalid("omc_store_autocorr: more columns than one launch takes");
+  if ((W_max + 31) / 32 > 0x7fffffffLL) return omc_invalid("omc_store_autocorr: more columns than one launch takes");
   const size_t n_mean = mean_out ? 0 : (size_t)C * n_idx, n_part = (size_t)n_slices * n_lb * A_L * W_max, n_g = (size_t)(L + 1) * W_max,
                n_cen = idx ? (size_t)N * W_max : 0;
   omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (n_mean + n_part + n_g + n_cen) * sizeof(double) + (size_t)W_max * sizeof(int32_t));
@@ -226,7 +221,7 @@ extern "C" omc_status omc_store_autocorr(omc_ctx* ctx, int64_t n_iter, int64_t s
   double* cen = g + n_g;
   int32_t* flags = (int32_t*)(cen + n_cen);
   st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size);
-  if (st == OMC_INVALID_ARG) return ac_invalid("omc_store_autocorr: an index outside [0, size)");
+  if (st == OMC_INVALID_ARG) return omc_invalid("omc_store_autocorr: an index outside [0, size)");
   if (st != OMC_OK) return st;
   st = omc_col_moments(ctx, omc_store_view(ctx, N, size, false, store, idx, n_idx), mean, nullptr);
   if (st != OMC_OK) return st;

@@ -7,6 +7,7 @@
 
 void omc_set_error(const char* what, hipError_t e);
 void omc_set_error_text(const char* text);  // any other library failure (RCCL) for omc_last_error()
+omc_status omc_invalid(const char* text);   // sets the text, returns OMC_INVALID_ARG
 
 #define OMC_HIP_CHECK(expr)                  \
   do {                                       \
@@ -152,6 +153,19 @@ omc_status omc_ensure(omc_ctx* ctx, omc_buf<T>& buf, size_t need) {
   buf.bytes = 0;
   OMC_HIP_CHECK(hipMalloc((void**)&buf.p, need));
   buf.bytes = need;
+  return OMC_OK;
+}
+
+// The check words of a validation on the device: zeroed in front of the launches that may set them, and read back behind them --
+// the call's one synchronisation, before anything is written.
+inline omc_status omc_words_zero(omc_ctx* ctx, int32_t* words, int n) {
+  OMC_HIP_CHECK(hipMemsetAsync(words, 0, n * sizeof(int32_t), ctx->stream));
+  return OMC_OK;
+}
+inline omc_status omc_words_read(omc_ctx* ctx, const int32_t* words, int n, int32_t* got) {
+  OMC_HIP_CHECK(hipGetLastError());
+  OMC_HIP_CHECK(hipMemcpyAsync(got, words, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return OMC_OK;
 }
 

@@ -13,6 +13,10 @@ void omc_set_error(const char* what, hipError_t e) {
 }
 
 void omc_set_error_text(const char* text) { g_last_error = text; }
+omc_status omc_invalid(const char* text) {
+  omc_set_error_text(text);
+  return OMC_INVALID_ARG;
+}
 
 omc_status omc_ensure_blas(omc_ctx* ctx) {
   if (!ctx->blas) {

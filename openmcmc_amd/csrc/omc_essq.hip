@@ -15,8 +15,7 @@
 // forms of the lag kernel give the same bits.  No floating-point atomics, no host round trip per block of lags.
 //
 // Per chunk of Kc selected elements:
-//   k_essq_gather      the gather tile of omc_rank_sort.h with the split geometry (the keys k_rank_gather of omc_rank.hip writes),
-//   rank_sort          the key-only bitonic sort of every column (omc_store_shared.hip),
+//   rank_gather_sort   k_rank_gather with the split geometry and the key-only bitonic sort of every column (omc_store_shared.hip),
 //   k_essq_thresholds  q_lo, q_hi of every interval from the sorted column, numpy's interpolation (q_lerp of omc_quantile.h; the
 //                      ranks and the weight come from the host),
 //   k_essq_pack        one read of the chunk's columns: a thread per (word of 64 draws, series, element), the elements on
@@ -56,43 +55,6 @@ void essq_ranks(int64_t nv, double q, int64_t& lo, int64_t& hi, double& frac) {
   hi = lo + 1 < nv ? lo + 1 : nv - 1;
   if (h >= (double)(nv - 1)) lo = hi = nv - 1;
   frac = h < (double)(nv - 1) ? h - (double)lo : 0.0;
-}
-
-// the layout of a column's draws: draw s is row s of the store seen as [N C][size] when s < first, else row s + skip; the middle
-// row of an odd N (rows [mid_row0, mid_row0 + C), mid_row0 < 0: none) is read for its NaN / inf only
-struct EssqGeom { int64_t S, P, first, skip, mid_row0; };
-EssqGeom essq_geom(int64_t N, int64_t C, bool split) {
-  EssqGeom g;
-  const int64_t M = N / 2;
-  g.S = split ? 2 * C * M : N * C;
-  g.P = rank_pow2(g.S);
-  g.first = split ? M * C : g.S;
-  g.skip = split ? (N - 2 * M) * C : 0;
-  g.mid_row0 = (split && (N & 1)) ? M * C : -1;
-  return g;
-}
-
-__global__ void __launch_bounds__(256) k_essq_gather(const double* __restrict__ store, const int64_t* __restrict__ idx, int64_t k0, int64_t Kc,
-                                                     int64_t size, int64_t C, int64_t S, int64_t P, int64_t first, int64_t skip,
-                                                     int64_t mid_row0, uint64_t* __restrict__ keys, int32_t* __restrict__ flags) {
-  const int64_t e0 = (int64_t)blockIdx.y * RANK_G_TE, e = e0 + (threadIdx.x & (RANK_G_TE - 1));
-  int32_t bits = 0;
-  if (mid_row0 >= 0 && blockIdx.x == 0 && e < Kc) {
-    const int64_t col = idx ? idx[k0 + e] : k0 + e;
-    for (int64_t c = threadIdx.x / RANK_G_TE; c < C; c += 256 / RANK_G_TE) bits |= rank_flag_bits(store[(mid_row0 + c) * size + col]);
-  }
-  rank_gather_tile(store, idx, k0, Kc, size, S, P, e0, (int64_t)blockIdx.x * RANK_G_TS, 0,
-                   [=](int64_t s) { return s < first ? s : s + skip; }, [=](double x, int64_t, int64_t) { return x; }, bits, keys, flags);
-}
-
-omc_status essq_gather_sort(omc_ctx* ctx, const double* store, const int64_t* idx, int64_t k0, int64_t kc, int64_t size, const EssqGeom& g,
-                            uint64_t* keys, int32_t* flags) {
-  OMC_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)kc * sizeof(int32_t), ctx->stream));
-  const dim3 grid((unsigned)((g.P + RANK_G_TS - 1) / RANK_G_TS), (unsigned)((kc + RANK_G_TE - 1) / RANK_G_TE));
-  hipLaunchKernelGGL(k_essq_gather, grid, dim3(256), 0, ctx->stream, store, idx, k0, kc, size, ctx->n_chains, g.S, g.P, g.first, g.skip,
-                     g.mid_row0, keys, flags);
-  OMC_HIP_CHECK(hipGetLastError());
-  return rank_sort(ctx, keys, kc, g.P);
 }
 
 // One thread per element of the chunk: thr [Kc][n_p][2] = q_lo (NaN: no lower end), q_hi of every interval; q_out [n_p][n_idx][2]
@@ -319,12 +281,12 @@ __global__ void __launch_bounds__(256) k_essq_pick(int64_t Kc, int64_t k0, int64
 extern "C" omc_status omc_store_ess_indicator(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx,
                                               int64_t n_idx, const double* prob_lo, const double* prob_hi, int32_t n_p, int32_t algo,
                                               double* ess_out, int32_t* lag_out, double* q_out, int64_t* counts_out, int64_t n_cnt) {
-  if (!ctx || n_iter < 4 || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size) || !prob_lo || !prob_hi || n_p < 1 ||
-      n_p > EQ_MAXP || algo < 0 || algo > 2 || n_cnt < 0)
+  if (!omc_selection_ok(ctx, n_iter, 4, size, store, idx, n_idx) || !prob_lo || !prob_hi || n_p < 1 || n_p > EQ_MAXP || algo < 0 || algo > 2 ||
+      n_cnt < 0)
     return OMC_INVALID_ARG;
   const int64_t N = n_iter, C = ctx->n_chains, M = N / 2, J = 2 * C, Wd = (M + 63) / 64;
   if (n_cnt > M) return OMC_INVALID_ARG;
-  const EssqGeom g = essq_geom(N, C, true);
+  const RankGeom g = rank_geom(N, C, true);
   EssqProbs pr;
   for (int p = 0; p < EQ_MAXP; ++p) {
     pr.r0[0][p] = -1;
@@ -345,19 +307,17 @@ extern "C" omc_status omc_store_ess_indicator(omc_ctx* ctx, int64_t n_iter, int6
   const bool in_lds = algo == 1 || (algo == 0 && lds <= EQ_LDS_MAX);
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   // per element: keys [P], the thresholds [n_p][2], the bits [n_p][J][Wd], the series counts [n_p][J], the flag word
-  const size_t per_elem = (size_t)g.P * sizeof(uint64_t) + (size_t)n_p * (2 * sizeof(double) + lds) + sizeof(int32_t);
-  int64_t Kc = rank_chunk(ctx, per_elem, n_idx);
-  while (Kc > 1 && Kc * (int64_t)n_p > 0x7fffffffLL) Kc /= 2;
+  RankCarve ws(ctx, (size_t)g.P * sizeof(uint64_t) + (size_t)n_p * (2 * sizeof(double) + lds) + sizeof(int32_t), n_idx);
+  while (ws.Kc > 1 && ws.Kc * (int64_t)n_p > 0x7fffffffLL) ws.Kc /= 2;
+  const int64_t Kc = ws.Kc;
   if (Kc * Wd * J / 256 > 0x7fffffffLL) return OMC_INVALID_ARG;
-  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (size_t)Kc * per_elem + 64);
-  if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws.p;
-  uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
-  uint64_t* bits = keys + (size_t)Kc * g.P;
-  double* thr = (double*)(bits + (size_t)Kc * n_p * J * Wd);
-  int32_t* nj = (int32_t*)(thr + (size_t)Kc * n_p * 2);
-  int32_t* flags = nj + (size_t)Kc * n_p * J;
-  st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size);
+  uint64_t* keys = ws.take<uint64_t>((size_t)Kc * g.P);
+  uint64_t* bits = ws.take<uint64_t>((size_t)Kc * n_p * J * Wd);
+  double* thr = ws.take<double>((size_t)Kc * n_p * 2);
+  int32_t* nj = ws.take<int32_t>((size_t)Kc * n_p * J);
+  int32_t* flags = ws.take<int32_t>(Kc);
+  omc_status st = ws.done();
+  if (st == OMC_OK) st = omc_store_check_index(ctx, ws.head(), idx, n_idx, size);
   if (st != OMC_OK) return st;
   hipStream_t s = ctx->stream;
   if (in_lds) OMC_HIP_CHECK(hipFuncSetAttribute((const void*)k_essq_lags<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EQ_LDS_MAX));
@@ -366,7 +326,7 @@ extern "C" omc_status omc_store_ess_indicator(omc_ctx* ctx, int64_t n_iter, int6
   a.ess_out = ess_out; a.lag_out = lag_out; a.counts_out = counts_out;
   for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {
     const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc;
-    st = essq_gather_sort(ctx, store, idx, k0, kc, size, g, keys, flags);
+    st = rank_gather_sort(ctx, store, idx, k0, kc, size, g, nullptr, keys, flags);
     if (st != OMC_OK) return st;
     hipLaunchKernelGGL(k_essq_thresholds, dim3((unsigned)((kc + 63) / 64)), dim3(64), 0, s, kc, k0, n_idx, g.P, (int)n_p, pr, keys, thr,
                        q_out);
@@ -382,26 +342,23 @@ extern "C" omc_status omc_store_ess_indicator(omc_ctx* ctx, int64_t n_iter, int6
 
 extern "C" omc_status omc_store_order_stats(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx,
                                             int64_t n_idx, int32_t split, const int64_t* pos, int64_t n_pos, double* out) {
-  if (!ctx || n_iter < (split ? 4 : 1) || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size) || !pos || n_pos < 1 || !out)
-    return OMC_INVALID_ARG;
+  if (!omc_selection_ok(ctx, n_iter, split ? 4 : 1, size, store, idx, n_idx) || !pos || n_pos < 1 || !out) return OMC_INVALID_ARG;
   const int64_t N = n_iter, C = ctx->n_chains;
-  const EssqGeom g = essq_geom(N, C, split != 0);
+  const RankGeom g = rank_geom(N, C, split != 0);
   if ((N * C + 63) / 64 > 0x7fffffffLL) return OMC_INVALID_ARG;
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  const size_t per_elem = (size_t)g.P * sizeof(uint64_t) + sizeof(int32_t);
-  const int64_t Kc = rank_chunk(ctx, per_elem, n_idx);
+  RankCarve ws(ctx, (size_t)g.P * sizeof(uint64_t) + sizeof(int32_t), n_idx);
+  const int64_t Kc = ws.Kc;
   if (Kc * n_pos / 256 > 0x7fffffffLL) return OMC_INVALID_ARG;
-  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (size_t)Kc * per_elem + 64);
-  if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws.p;
-  uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
-  int32_t* flags = (int32_t*)(keys + (size_t)Kc * g.P);
+  uint64_t* keys = ws.take<uint64_t>((size_t)Kc * g.P);
+  int32_t* flags = ws.take<int32_t>(Kc);
+  omc_status st = ws.done();
   // the selection against [0, size) and the positions against [0, S): one read-back, before out is written
-  st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size, pos, n_idx * n_pos, g.S);
+  if (st == OMC_OK) st = omc_store_check_index(ctx, ws.head(), idx, n_idx, size, pos, n_idx * n_pos, g.S);
   if (st != OMC_OK) return st;
   for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {
     const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc;
-    st = essq_gather_sort(ctx, store, idx, k0, kc, size, g, keys, flags);
+    st = rank_gather_sort(ctx, store, idx, k0, kc, size, g, nullptr, keys, flags);
     if (st != OMC_OK) return st;
     hipLaunchKernelGGL(k_essq_pick, dim3((unsigned)((kc * n_pos + 255) / 256)), dim3(256), 0, ctx->stream, kc, k0, g.P, n_pos, keys, flags, pos,
                        out);

@@ -168,9 +168,7 @@ __global__ void __launch_bounds__(64) k_hdi_window_final(HdiArgs a) {
 extern "C" omc_status omc_store_hdi(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                                     const double* probs, int32_t n_probs, int32_t per_chain, int32_t omit_nan, double* out,
                                     int64_t* n_valid_out) {
-  if (!ctx || n_iter < 1 || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size) || !probs || n_probs < 1 || n_probs > HDI_PROBS ||
-      !out)
-    return OMC_INVALID_ARG;
+  if (!omc_selection_ok(ctx, n_iter, 1, size, store, idx, n_idx) || !probs || n_probs < 1 || n_probs > HDI_PROBS || !out) return OMC_INVALID_ARG;
   for (int p = 0; p < n_probs; ++p)
     if (!(probs[p] > 0.0 && probs[p] < 1.0)) return OMC_INVALID_ARG;
   const int64_t N = n_iter, C = ctx->n_chains;
@@ -179,18 +177,16 @@ extern "C" omc_status omc_store_hdi(omc_ctx* ctx, int64_t n_iter, int64_t size, 
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   // per column: keys [P], n, the pairs of every slice and probability, the flag word
   const size_t per_col = (size_t)P * sizeof(uint64_t) + sizeof(int64_t) + (n_slices > 1 ? (size_t)n_slices * HDI_PROBS * 16 : 0) + sizeof(int32_t);
-  const int64_t Kc = rank_chunk(ctx, per_col * (size_t)CC, n_idx);
-  const int64_t n_col_max = Kc * CC;
+  RankCarve ws(ctx, per_col * (size_t)CC, n_idx);
+  const int64_t Kc = ws.Kc, n_col_max = Kc * CC;
   const int64_t n_st = (P + RANK_G_TS - 1) / RANK_G_TS, n_et_max = (Kc + RANK_G_TE - 1) / RANK_G_TE;
   if (n_st * n_et_max * CC > 0x7fffffffLL || n_col_max * n_slices > 0x7fffffffLL) return OMC_INVALID_ARG;
-  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (size_t)n_col_max * per_col + 64);
-  if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws.p;
-  uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
-  int64_t* n_valid = (int64_t*)(keys + (size_t)n_col_max * P);
-  uint64_t* part = (uint64_t*)(n_valid + n_col_max);
-  int32_t* flags = (int32_t*)(part + (n_slices > 1 ? (size_t)n_col_max * n_slices * HDI_PROBS * 2 : 0));
-  st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size);
+  uint64_t* keys = ws.take<uint64_t>((size_t)n_col_max * P);
+  int64_t* n_valid = ws.take<int64_t>(n_col_max);
+  uint64_t* part = ws.take<uint64_t>(n_slices > 1 ? (size_t)n_col_max * n_slices * HDI_PROBS * 2 : 0);
+  int32_t* flags = ws.take<int32_t>(n_col_max);
+  omc_status st = ws.done();
+  if (st == OMC_OK) st = omc_store_check_index(ctx, ws.head(), idx, n_idx, size);
   if (st != OMC_OK) return st;
   hipStream_t s = ctx->stream;
   HdiArgs a;

@@ -201,14 +201,12 @@ omc_status omc_hist_check(omc_ctx* ctx, const int64_t* idx, int64_t n_idx, int64
   omc_status st = omc_ensure(ctx, ctx->store_ws, 64);
   if (st != OMC_OK) return st;
   int32_t* words = (int32_t*)ctx->store_ws.p;
-  OMC_HIP_CHECK(hipMemsetAsync(words, 0, 2 * sizeof(int32_t), ctx->stream));
+  st = omc_words_zero(ctx, words, 2);
+  if (st != OMC_OK) return st;
   omc_store_check_index_launch(ctx, idx, n_idx, size, nullptr, 0, 0, words);
   const int64_t n = edge_rows * (n_bins + 1);
   hipLaunchKernelGGL(k_hist_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, edges, edge_rows, n_bins, words);
-  OMC_HIP_CHECK(hipGetLastError());
-  OMC_HIP_CHECK(hipMemcpyAsync(got, words, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return OMC_OK;
+  return omc_words_read(ctx, words, 2, got);
 }
 
 extern "C" omc_status omc_store_histogram_layout(int32_t n_bins, int32_t edges_per_element, int32_t* out) {
@@ -221,7 +219,7 @@ extern "C" omc_status omc_store_histogram_layout(int32_t n_bins, int32_t edges_p
 
 extern "C" omc_status omc_store_minmax(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                                        int32_t pooled, double* min_out, double* max_out, int64_t* count_out) {
-  if (!ctx || n_iter < 1 || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size)) return OMC_INVALID_ARG;
+  if (!omc_selection_ok(ctx, n_iter, 1, size, store, idx, n_idx)) return OMC_INVALID_ARG;
   const StoreView v = omc_store_view(ctx, n_iter, size, pooled != 0, store, idx, n_idx);
   const int64_t R = v.R, batches = v.batches;
   const int64_t tiles = (n_idx + HIST_TE_MAX - 1) / HIST_TE_MAX;
@@ -253,8 +251,7 @@ extern "C" omc_status omc_store_minmax(omc_ctx* ctx, int64_t n_iter, int64_t siz
 extern "C" omc_status omc_store_histogram(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx,
                                           int64_t n_idx, int32_t pooled, int32_t n_bins, const double* edges, int32_t edges_per_element,
                                           int64_t* counts_out, int64_t* outside_out) {
-  if (!ctx || n_iter < 1 || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size) || n_bins < 1 || n_bins > HIST_MAX_BINS || !edges ||
-      !counts_out)
+  if (!omc_selection_ok(ctx, n_iter, 1, size, store, idx, n_idx) || n_bins < 1 || n_bins > HIST_MAX_BINS || !edges || !counts_out)
     return OMC_INVALID_ARG;
   const StoreView v = omc_store_view(ctx, n_iter, size, pooled != 0, store, idx, n_idx);
   const int64_t R = v.R, batches = v.batches;

@@ -279,8 +279,8 @@ extern "C" omc_status omc_store_histogram2d(omc_ctx* ctx, int64_t n_iter, int64_
                                             int64_t size_y, const double* store_y, const int64_t* idx_y, int64_t n_pairs, int32_t pooled,
                                             int32_t pool_pairs, int32_t nx, const double* edges_x, int32_t ny, const double* edges_y,
                                             int32_t edges_per_pair, int64_t* counts_out, int64_t* outside_out, int64_t* occupied_out) {
-  if (!ctx || n_iter < 1 || size_x < 1 || size_y < 1 || !store_x || !store_y || n_pairs < 1 || (!idx_x && n_pairs != size_x) ||
-      (!idx_y && n_pairs != size_y) || nx < 1 || nx > HIST_MAX_BINS || ny < 1 || ny > HIST_MAX_BINS || !edges_x || !edges_y || !counts_out ||
+  if (!omc_selection_ok(ctx, n_iter, 1, size_x, store_x, idx_x, n_pairs) || !omc_selection_ok(ctx, n_iter, 1, size_y, store_y, idx_y, n_pairs) ||
+      nx < 1 || nx > HIST_MAX_BINS || ny < 1 || ny > HIST_MAX_BINS || !edges_x || !edges_y || !counts_out ||
       (edges_per_pair && pool_pairs) || (occupied_out && !pool_pairs))
     return OMC_INVALID_ARG;
   if (occupied_out && n_pairs > HIST2D_OCC_PAIRS) return OMC_UNSUPPORTED;  // a row's cells must stay in one wave

@@ -295,11 +295,11 @@ extern "C" omc_status omc_kde_binned(omc_ctx* ctx, int64_t n_cols, int32_t G, co
   int32_t got = 0;
   const int64_t n = n_cols * G;
   if ((n + 255) / 256 > 0x7fffffffLL) return OMC_INVALID_ARG;
-  OMC_HIP_CHECK(hipMemsetAsync(word, 0, sizeof(int32_t), s));
+  st = omc_words_zero(ctx, word, 1);
+  if (st != OMC_OK) return st;
   hipLaunchKernelGGL(k_kde_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, counts, n, word);
-  OMC_HIP_CHECK(hipGetLastError());
-  OMC_HIP_CHECK(hipMemcpyAsync(&got, word, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  OMC_HIP_CHECK(hipStreamSynchronize(s));
+  st = omc_words_read(ctx, word, 1, &got);
+  if (st != OMC_OK) return st;
   if (got) return OMC_INVALID_ARG;
   KdeArgs a;
   a.counts = counts; a.lo = lo; a.hi = hi; a.bw_in = bw_in; a.density = density_out; a.bw = bw_out; a.flag = flag_out; a.mode = mode_out;

@@ -163,40 +163,31 @@ __global__ void __launch_bounds__(256) k_loglik_join(int64_t n, int slices, cons
   if (var_out) var_out[k] = bad ? nan : m2 / (cnt - 1.0);
 }
 
-omc_status ll_invalid(const char* text) {
-  omc_set_error_text(text);
-  return OMC_INVALID_ARG;
-}
-
 }  // namespace
 
 extern "C" omc_status omc_store_loglik(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                                        const double* y, const double* prec, int64_t prec_size, double* lse_out, double* mean_out,
                                        double* var_out, double* ll_out) {
-  if (!ctx) return ll_invalid("omc_store_loglik: no context");
-  if (n_iter < 1 || n_iter * ctx->n_chains < 2) return ll_invalid("omc_store_loglik: fewer than 2 stored draws (n_iter * C < 2)");
-  if (size < 1) return ll_invalid("omc_store_loglik: size < 1");
-  if (!store || !y || !prec) return ll_invalid("omc_store_loglik: store, y and prec must not be NULL");
-  if (n_idx < 1 || (!idx && n_idx != size)) return ll_invalid("omc_store_loglik: n_idx < 1, or no index and n_idx != size");
-  if (prec_size != 1 && prec_size != n_idx) return ll_invalid("omc_store_loglik: prec_size must be 1 or n_idx");
-  if (!lse_out && !mean_out && !var_out && !ll_out) return ll_invalid("omc_store_loglik: every output is NULL");
+  if (!ctx) return omc_invalid("omc_store_loglik: no context");
+  if (n_iter < 1 || n_iter * ctx->n_chains < 2) return omc_invalid("omc_store_loglik: fewer than 2 stored draws (n_iter * C < 2)");
+  if (size < 1) return omc_invalid("omc_store_loglik: size < 1");
+  if (!store || !y || !prec) return omc_invalid("omc_store_loglik: store, y and prec must not be NULL");
+  if (n_idx < 1 || (!idx && n_idx != size)) return omc_invalid("omc_store_loglik: n_idx < 1, or no index and n_idx != size");
+  if (prec_size != 1 && prec_size != n_idx) return omc_invalid("omc_store_loglik: prec_size must be 1 or n_idx");
+  if (!lse_out && !mean_out && !var_out && !ll_out) return omc_invalid("omc_store_loglik: every output is NULL");
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const StoreView v = omc_store_view(ctx, n_iter, size, true, store, idx, n_idx);  // pooled: S rows of row_stride = size doubles
   const int64_t S = v.R;
-  // row slices: about 2048 workgroups, no slice shorter than 256 rows (a function of the shape only)
   const int64_t tiles = (n_idx + LL_COLS - 1) / LL_COLS;
-  int64_t slices = (2048 + tiles - 1) / tiles;
-  if (slices > (S + 255) / 256) slices = (S + 255) / 256;
-  if (slices < 1) slices = 1;
-  if (slices > 1024) slices = 1024;
-  const int64_t rpb = (S + slices - 1) / slices;
-  if (tiles > 0x7fffffffLL || (S + 255) / 256 > 0x7fffffffLL) return ll_invalid("omc_store_loglik: more columns or rows than one launch takes");
+  int64_t rpb;
+  const int64_t slices = omc_row_slices(tiles, S, &rpb);
+  if (tiles > 0x7fffffffLL || (S + 255) / 256 > 0x7fffffffLL) return omc_invalid("omc_store_loglik: more columns or rows than one launch takes");
   const size_t head_bytes = prec_size == 1 ? (size_t)S * sizeof(double) : 0;
   omc_status st = omc_ensure(ctx, ctx->store_ws, LL_HEAD + head_bytes + (size_t)slices * 5 * n_idx * sizeof(double));
   if (st != OMC_OK) return st;
   char* ws = (char*)ctx->store_ws.p;
   st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size);
-  if (st == OMC_INVALID_ARG) return ll_invalid("omc_store_loglik: an index outside [0, size)");  // (the helper's only use of that status)
+  if (st == OMC_INVALID_ARG) return omc_invalid("omc_store_loglik: an index outside [0, size)");  // (the helper's only use of that status)
   if (st != OMC_OK) return st;
   LlArgs g;
   g.store = v.data; g.idx = v.idx; g.y = y; g.prec = prec; g.head = (const double*)(ws + LL_HEAD);

@@ -8,8 +8,7 @@
 //
 // The sort of omc_rank_sort.h is key-only: after it a smoothed weight belongs to a sorted position, not to a draw, and f still lies
 // in the store in draw order.  A chunk of Kc selected columns at a time:
-//   k_loo_gather   the gather tile of omc_rank_sort.h with psis_neg_ll of omc_psis_fit.h: the keys k_psis_gather writes.
-//   rank_sort      the key-only bitonic sort of every column (omc_store_shared.hip).
+//   psis_gather_sort  omc_psis.hip's k_psis_gather and the key-only bitonic sort of every column (omc_store_shared.hip).
 //   k_loo_fit      psis_fit_column of omc_psis_fit.h, one workgroup of 512 per column: the fit record (vmax, xc, exp(xc), k, sigma,
 //                  L, t0, T; T = -1 for a column with an ll that is not finite) into the workspace.
 //   k_loo_expect   laid out like k_loglik_part: a workgroup owns LE_COLS = 32 adjacent selection positions and a slice of the rows;
@@ -26,9 +25,8 @@
 //                  LDS -- the moments by Chan's update with weights for counts, the rest by addition -- into part [slices][6][Kc].
 //                  lw_out is written on the way.  The sorted keys stay in rank_ws until the pass over the chunk has run.
 //   k_loo_join     thread = column: the slices in slice order, the divisions by W, k and T from the fit record.
-// Slices: about 2048 workgroups over the whole selection, no slice shorter than 256 rows, at most 1024 -- omc_store_loglik's rule,
-// a function of (S, n_idx) alone and not of the chunk.  No scratch.  The only atomics are the gather tile's flag words (an OR:
-// independent of the order).
+// Slices: omc_row_slices (omc_store_view.h) over the whole selection, a function of (S, n_idx) alone and not of the chunk.  No
+// scratch.  The only atomics are the gather tile's flag words (an OR: independent of the order).
 #include <math.h>
 
 #include "omc_common.h"
@@ -56,22 +54,6 @@ struct LooArgs {
   int64_t S, P, size, vsize, n_idx, prec_size, rows_per_block, k0, kc;
   int32_t want;
 };
-
-__global__ void __launch_bounds__(256) k_loo_check_tail(const int64_t* __restrict__ tail_max, int64_t n, int64_t S, int32_t* __restrict__ word) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k < n && (tail_max[k] < 1 || tail_max[k] > S - 1)) *word = 1;
-}
-
-__global__ void __launch_bounds__(256) k_loo_gather(const double* __restrict__ store, const int64_t* __restrict__ idx, int64_t k0, int64_t Kc,
-                                                    int64_t size, int64_t S, int64_t P, const double* __restrict__ y,
-                                                    const double* __restrict__ prec, int64_t prec_size, int64_t n_idx,
-                                                    uint64_t* __restrict__ keys, int32_t* __restrict__ flags) {
-  const int64_t e0 = (int64_t)blockIdx.y * RANK_G_TE;
-  rank_gather_tile(store, idx, k0, Kc, size, S, P, e0, (int64_t)blockIdx.x * RANK_G_TS, 0,
-                   [](int64_t s) { return s; },
-                   [=](double x, int64_t s, int64_t e_l) { return psis_neg_ll(x, s, k0 + e0 + e_l, y, prec, prec_size, n_idx); },
-                   0, keys, flags);
-}
 
 __global__ void __launch_bounds__(PSIS_THREADS) k_loo_fit(int64_t k0, int64_t S, int64_t P, const uint64_t* __restrict__ keys,
                                                            const int32_t* __restrict__ flags, const int64_t* __restrict__ tail_max,
@@ -265,11 +247,6 @@ __global__ void __launch_bounds__(256) k_loo_join(int64_t k0, int64_t kc, int sl
   if (invprec_out) invprec_out[k0 + e] = bad ? nan : ip / W;
 }
 
-omc_status le_invalid(const char* text) {
-  omc_set_error_text(text);
-  return OMC_INVALID_ARG;
-}
-
 template <int F>
 void le_launch(omc_ctx* ctx, const dim3& grid, bool vec, const LooArgs& g) {
   if (vec) hipLaunchKernelGGL((k_loo_expect<true, F>), grid, dim3(256), 0, ctx->stream, g);
@@ -283,54 +260,29 @@ extern "C" omc_status omc_store_loo_expect(omc_ctx* ctx, int64_t n_iter, int64_t
                                            const double* values, int64_t vsize, const int64_t* vidx, const double* thr, double* mean_out,
                                            double* var_out, double* below_out, double* ess_out, double* invprec_out, double* k_out,
                                            int64_t* tail_out, double* lw_out) {
-  if (!ctx) return le_invalid("omc_store_loo_expect: no context");
-  if (n_iter < 1 || n_iter * ctx->n_chains < 2) return le_invalid("omc_store_loo_expect: fewer than 2 stored draws (n_iter * C < 2)");
-  if (size < 1) return le_invalid("omc_store_loo_expect: size < 1");
-  if (!store || !tail_max) return le_invalid("omc_store_loo_expect: store and tail_max must not be NULL");
-  if (n_idx < 1 || (!idx && n_idx != size)) return le_invalid("omc_store_loo_expect: n_idx < 1, or no index and n_idx != size");
-  if ((y != nullptr) != (prec != nullptr)) return le_invalid("omc_store_loo_expect: y and prec must be given together");
-  if (y && prec_size != 1 && prec_size != n_idx) return le_invalid("omc_store_loo_expect: prec_size must be 1 or n_idx");
-  if (f_kind < F_ENTRY || f_kind > F_CDF) return le_invalid("omc_store_loo_expect: f_kind must be 0 (entry), 1 (mean) or 2 (cdf)");
-  if (f_kind == F_ENTRY && (!values || vsize < 1)) return le_invalid("omc_store_loo_expect: f_kind entry needs values and vsize >= 1");
-  if (f_kind == F_ENTRY && !vidx && n_idx != vsize) return le_invalid("omc_store_loo_expect: f_kind entry without vidx needs n_idx == vsize");
-  if (f_kind != F_ENTRY && !y) return le_invalid("omc_store_loo_expect: f_kind mean and cdf need y and prec (a mean entry)");
-  if (invprec_out && !y) return le_invalid("omc_store_loo_expect: invprec_out needs y and prec (a mean entry)");
-  if ((below_out != nullptr) != (thr != nullptr)) return le_invalid("omc_store_loo_expect: below_out and thr must be given together");
-  if (!mean_out && !var_out && !below_out && !ess_out && !invprec_out && !k_out && !tail_out && !lw_out)
-    return le_invalid("omc_store_loo_expect: every output is NULL");
-  const int64_t S = n_iter * ctx->n_chains, P = rank_pow2(S);
-  if (30 + (int64_t)floor(sqrt((double)(S - 1))) > PSIS_M_MAX)
-    return le_invalid("omc_store_loo_expect: more stored draws than the fit takes (about 4 million)");
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  // row slices: about 2048 workgroups over the whole selection, no slice shorter than 256 rows (a function of the shape only)
-  const int64_t tiles_all = (n_idx + LE_COLS - 1) / LE_COLS;
-  int64_t slices = (2048 + tiles_all - 1) / tiles_all;
-  if (slices > (S + 255) / 256) slices = (S + 255) / 256;
-  if (slices < 1) slices = 1;
-  if (slices > 1024) slices = 1024;
-  const int64_t rpb = (S + slices - 1) / slices;
-  const size_t per_elem = (size_t)P * sizeof(uint64_t) + sizeof(LooFit) + (size_t)slices * LE_PART * sizeof(double) + sizeof(int32_t);
-  const int64_t Kc = rank_chunk(ctx, per_elem, n_idx);
-  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (size_t)Kc * per_elem + 64);
+  const char* own = nullptr;  // what this entry point alone asks of its arguments
+  if (f_kind < F_ENTRY || f_kind > F_CDF) own = "f_kind must be 0 (entry), 1 (mean) or 2 (cdf)";
+  else if (f_kind == F_ENTRY && (!values || vsize < 1)) own = "f_kind entry needs values and vsize >= 1";
+  else if (f_kind == F_ENTRY && !vidx && n_idx != vsize) own = "f_kind entry without vidx needs n_idx == vsize";
+  else if (f_kind != F_ENTRY && !y) own = "f_kind mean and cdf need y and prec (a mean entry)";
+  else if (invprec_out && !y) own = "invprec_out needs y and prec (a mean entry)";
+  else if ((below_out != nullptr) != (thr != nullptr)) own = "below_out and thr must be given together";
+  else if (!mean_out && !var_out && !below_out && !ess_out && !invprec_out && !k_out && !tail_out && !lw_out) own = "every output is NULL";
+  const PsisCall c = {n_iter, size, store, idx, n_idx, y, prec, prec_size, tail_max};
+  omc_status st = psis_prelude(ctx, "omc_store_loo_expect", c, store && tail_max ? nullptr : "store and tail_max must not be NULL", own,
+                               f_kind == F_ENTRY ? vidx : nullptr, vsize);
   if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws.p;
-  uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
-  LooFit* fit = (LooFit*)(keys + (size_t)Kc * P);
-  double* part = (double*)(fit + Kc);
-  int32_t* flags = (int32_t*)(part + (size_t)Kc * slices * LE_PART);
-  // one read-back for the two indices and the tail lengths, before anything is written: words 0 .. 2 of the head
-  int32_t* words = (int32_t*)ws;
-  OMC_HIP_CHECK(hipMemsetAsync(words, 0, 3 * sizeof(int32_t), ctx->stream));
-  omc_store_check_index_launch(ctx, idx, n_idx, size, nullptr, 0, 0, words);
-  hipLaunchKernelGGL(k_loo_check_tail, dim3((unsigned)((n_idx + 255) / 256)), dim3(256), 0, ctx->stream, tail_max, n_idx, S, words + 1);
-  if (f_kind == F_ENTRY) omc_store_check_index_launch(ctx, vidx, n_idx, vsize, nullptr, 0, 0, words + 2);
-  OMC_HIP_CHECK(hipGetLastError());
-  int32_t got[3] = {0, 0, 0};
-  OMC_HIP_CHECK(hipMemcpyAsync(got, words, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (got[0]) return le_invalid("omc_store_loo_expect: an index outside [0, size)");
-  if (got[1]) return le_invalid("omc_store_loo_expect: a tail_max outside [1, n_iter * C - 1]");
-  if (got[2]) return le_invalid("omc_store_loo_expect: a vidx outside [0, vsize)");
+  const int64_t S = n_iter * ctx->n_chains, P = rank_pow2(S);
+  int64_t rpb;  // slices over the whole selection: a function of (S, n_idx) alone and not of the chunk
+  const int64_t slices = omc_row_slices((n_idx + LE_COLS - 1) / LE_COLS, S, &rpb);
+  RankCarve ws(ctx, (size_t)P * sizeof(uint64_t) + sizeof(LooFit) + (size_t)slices * LE_PART * sizeof(double) + sizeof(int32_t), n_idx);
+  const int64_t Kc = ws.Kc;
+  uint64_t* keys = ws.take<uint64_t>((size_t)Kc * P);
+  LooFit* fit = ws.take<LooFit>(Kc);
+  double* part = ws.take<double>((size_t)Kc * slices * LE_PART);
+  int32_t* flags = ws.take<int32_t>(Kc);
+  st = ws.done();
+  if (st != OMC_OK) return st;
   LooArgs g;
   g.store = store; g.idx = idx; g.y = y; g.prec = prec; g.values = f_kind == F_ENTRY ? values : nullptr;
   g.vidx = f_kind == F_ENTRY ? vidx : nullptr; g.thr = thr; g.keys = keys; g.fit = fit; g.part = part; g.lw_out = lw_out;
@@ -342,11 +294,7 @@ extern "C" omc_status omc_store_loo_expect(omc_ctx* ctx, int64_t n_iter, int64_t
   if (f_kind == F_ENTRY) vec_ok = vec_ok && !vidx && vsize % 2 == 0 && ((uintptr_t)values & 15) == 0;
   for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {
     const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc;
-    OMC_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)kc * sizeof(int32_t), ctx->stream));
-    const dim3 grid((unsigned)((P + RANK_G_TS - 1) / RANK_G_TS), (unsigned)((kc + RANK_G_TE - 1) / RANK_G_TE));
-    hipLaunchKernelGGL(k_loo_gather, grid, dim3(256), 0, ctx->stream, store, idx, k0, kc, size, S, P, y, prec, prec_size, n_idx, keys, flags);
-    OMC_HIP_CHECK(hipGetLastError());
-    st = rank_sort(ctx, keys, kc, P);
+    st = psis_gather_sort(ctx, c, k0, kc, S, P, keys, flags);
     if (st != OMC_OK) return st;
     hipLaunchKernelGGL(k_loo_fit, dim3((unsigned)kc), dim3(PSIS_THREADS), 0, ctx->stream, k0, S, P, keys, flags, tail_max, fit);
     OMC_HIP_CHECK(hipGetLastError());

@@ -178,36 +178,31 @@ __global__ void __launch_bounds__(256) k_project_mfma(ProjArgs g) {
   }
 }
 
-omc_status proj_invalid(const char* text) {
-  omc_set_error_text(text);
-  return OMC_INVALID_ARG;
-}
-
 }  // namespace
 
 extern "C" omc_status omc_store_project(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx,
                                         int64_t n_idx, int64_t m, const double* W, int64_t ld_w, const double* offset,
                                         const double* base, int32_t omit_nan, const double* prec, int64_t prec_size,
                                         const double* z_inject, uint64_t replicate, double* out) {
-  if (!ctx) return proj_invalid("omc_store_project: no context");
-  if (n_iter < 1) return proj_invalid("omc_store_project: n_iter < 1");
-  if (size < 1) return proj_invalid("omc_store_project: size < 1");
-  if (m < 1) return proj_invalid("omc_store_project: m < 1");
-  if (!store || !W || !out) return proj_invalid("omc_store_project: store, W and out must not be NULL");
-  if (n_idx < 1 || (!idx && n_idx != size)) return proj_invalid("omc_store_project: n_idx < 1, or no index and n_idx != size");
-  if (ld_w < n_idx) return proj_invalid("omc_store_project: ld_w < n_idx");
-  if (prec_size != 0 && prec_size != 1 && prec_size != m) return proj_invalid("omc_store_project: prec_size must be 0, 1 or m");
-  if ((prec_size != 0) != (prec != nullptr)) return proj_invalid("omc_store_project: prec and prec_size must be given together");
-  if (z_inject && !prec) return proj_invalid("omc_store_project: z_inject without prec");
-  if (replicate > 15) return proj_invalid("omc_store_project: replicate > 15");
+  if (!ctx) return omc_invalid("omc_store_project: no context");
+  if (n_iter < 1) return omc_invalid("omc_store_project: n_iter < 1");
+  if (size < 1) return omc_invalid("omc_store_project: size < 1");
+  if (m < 1) return omc_invalid("omc_store_project: m < 1");
+  if (!store || !W || !out) return omc_invalid("omc_store_project: store, W and out must not be NULL");
+  if (n_idx < 1 || (!idx && n_idx != size)) return omc_invalid("omc_store_project: n_idx < 1, or no index and n_idx != size");
+  if (ld_w < n_idx) return omc_invalid("omc_store_project: ld_w < n_idx");
+  if (prec_size != 0 && prec_size != 1 && prec_size != m) return omc_invalid("omc_store_project: prec_size must be 0, 1 or m");
+  if ((prec_size != 0) != (prec != nullptr)) return omc_invalid("omc_store_project: prec and prec_size must be given together");
+  if (z_inject && !prec) return omc_invalid("omc_store_project: z_inject without prec");
+  if (replicate > 15) return omc_invalid("omc_store_project: replicate > 15");
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const omc_status st = omc_store_check_index(ctx, nullptr, idx, n_idx, size);
-  if (st == OMC_INVALID_ARG) return proj_invalid("omc_store_project: an index outside [0, size)");  // (the helper's only use of that status)
+  if (st == OMC_INVALID_ARG) return omc_invalid("omc_store_project: an index outside [0, size)");  // (the helper's only use of that status)
   if (st != OMC_OK) return st;
   const StoreView v = omc_store_view(ctx, n_iter, size, true, store, idx, n_idx);  // pooled: R rows of row_stride = size doubles
   const bool tall = m <= PJ_TM / 2;  // 128 rows x 64 columns
   const int64_t row_tiles = tall ? (v.R + 2 * PJ_TR - 1) / (2 * PJ_TR) : (v.R + PJ_TR - 1) / PJ_TR, col_tiles = tall ? 1 : (m + PJ_TM - 1) / PJ_TM;
-  if (row_tiles > 0x7fffffffLL || col_tiles > 65535) return proj_invalid("omc_store_project: more rows or outputs than one launch takes");
+  if (row_tiles > 0x7fffffffLL || col_tiles > 65535) return omc_invalid("omc_store_project: more rows or outputs than one launch takes");
   ProjArgs g;
   g.store = v.data; g.idx = v.idx; g.W = W; g.offset = offset; g.base = base; g.prec = prec; g.z = z_inject; g.out = out;
   g.R = v.R; g.size = v.row_stride; g.n_idx = v.n; g.m = m; g.ld_w = ld_w; g.prec_size = prec_size;

@@ -6,8 +6,8 @@
 // Normal.log_p(..., by_observation=True) of the reference per stored draw (distribution/location_scale.py:145-166).
 //
 // A chunk of Kc selected columns at a time:
-//   k_psis_gather  the gather tile of omc_rank_sort.h: the S draws of a column as order-preserving keys of v = -ll, the log
-//                  importance ratio up to a constant; ll is the entry as it lies, or omc_normal_ll (omc_loglik.h) of a mean entry
+//   k_psis_gather  (shared with omc_loo_expect.hip through psis_gather_sort) the gather tile of omc_rank_sort.h: the S draws of
+//                  a column as order-preserving keys of v = -ll, the log importance ratio up to a constant; ll is the entry as it lies, or omc_normal_ll (omc_loglik.h) of a mean entry
 //                  computed on the way -- the same inline function as omc_store_loglik, so the two routes give the same bits.  It
 //                  notes per column whether a NaN or an infinity was seen.
 //   rank_sort      the key-only bitonic sort of every column (omc_store_shared.hip).
@@ -16,6 +16,8 @@
 //                  a function of (S, T) alone: repeated calls, and any "rank_tile" / "rank_chunk", give the same bits.
 // No scratch.  The only atomics are the gather tile's flag words (an OR: independent of the order).
 #include <math.h>
+
+#include <string>
 
 #include "omc_common.h"
 #include "omc_loglik.h"
@@ -65,51 +67,65 @@ __global__ void __launch_bounds__(PSIS_THREADS) k_psis_fit(int64_t k0, int64_t S
   }
 }
 
-omc_status psis_invalid(const char* text) {
-  omc_set_error_text(text);
-  return OMC_INVALID_ARG;
+}  // namespace
+
+omc_status psis_prelude(omc_ctx* ctx, const char* who, const PsisCall& c, const char* null_text, const char* own_text, const int64_t* vidx,
+                        int64_t vsize) {
+  const auto no = [who](const char* text) { return omc_invalid((std::string(who) + ": " + text).c_str()); };
+  if (!ctx) return no("no context");
+  if (c.n_iter < 1 || c.n_iter * ctx->n_chains < 2) return no("fewer than 2 stored draws (n_iter * C < 2)");
+  if (c.size < 1) return no("size < 1");
+  if (null_text) return no(null_text);
+  if (c.n_idx < 1 || (!c.idx && c.n_idx != c.size)) return no("n_idx < 1, or no index and n_idx != size");
+  if ((c.y != nullptr) != (c.prec != nullptr)) return no("y and prec must be given together");
+  if (c.y && c.prec_size != 1 && c.prec_size != c.n_idx) return no("prec_size must be 1 or n_idx");
+  if (own_text) return no(own_text);
+  const int64_t S = c.n_iter * ctx->n_chains;
+  if (30 + (int64_t)floor(sqrt((double)(S - 1))) > PSIS_M_MAX) return no("more stored draws than the fit takes (about 4 million)");
+  OMC_HIP_CHECK(hipSetDevice(ctx->device));
+  omc_status st = omc_ensure(ctx, ctx->store_ws, 64);
+  if (st != OMC_OK) return st;
+  int32_t* words = (int32_t*)ctx->store_ws.p;
+  st = omc_words_zero(ctx, words, 3);
+  if (st != OMC_OK) return st;
+  omc_store_check_index_launch(ctx, c.idx, c.n_idx, c.size, nullptr, 0, 0, words);
+  hipLaunchKernelGGL(k_psis_check_tail, dim3((unsigned)((c.n_idx + 255) / 256)), dim3(256), 0, ctx->stream, c.tail_max, c.n_idx, S, words + 1);
+  omc_store_check_index_launch(ctx, vidx, c.n_idx, vsize, nullptr, 0, 0, words + 2);
+  int32_t got[3] = {0, 0, 0};
+  st = omc_words_read(ctx, words, 3, got);
+  if (st != OMC_OK) return st;
+  if (got[0]) return no("an index outside [0, size)");
+  if (got[1]) return no("a tail_max outside [1, n_iter * C - 1]");
+  if (got[2]) return no("a vidx outside [0, vsize)");
+  return OMC_OK;
 }
 
-}  // namespace
+omc_status psis_gather_sort(omc_ctx* ctx, const PsisCall& c, int64_t k0, int64_t kc, int64_t S, int64_t P, uint64_t* keys, int32_t* flags) {
+  OMC_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)kc * sizeof(int32_t), ctx->stream));
+  const dim3 grid((unsigned)((P + RANK_G_TS - 1) / RANK_G_TS), (unsigned)((kc + RANK_G_TE - 1) / RANK_G_TE));
+  hipLaunchKernelGGL(k_psis_gather, grid, dim3(256), 0, ctx->stream, c.store, c.idx, k0, kc, c.size, S, P, c.y, c.prec, c.prec_size, c.n_idx, keys,
+                     flags);
+  OMC_HIP_CHECK(hipGetLastError());
+  return rank_sort(ctx, keys, kc, P);
+}
 
 extern "C" omc_status omc_store_psis(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                                      const double* y, const double* prec, int64_t prec_size, const int64_t* tail_max, double* elpd_out,
                                      double* k_out, int64_t* tail_out) {
-  if (!ctx) return psis_invalid("omc_store_psis: no context");
-  if (n_iter < 1 || n_iter * ctx->n_chains < 2) return psis_invalid("omc_store_psis: fewer than 2 stored draws (n_iter * C < 2)");
-  if (size < 1) return psis_invalid("omc_store_psis: size < 1");
-  if (!store || !tail_max || !elpd_out || !k_out) return psis_invalid("omc_store_psis: store, tail_max, elpd_out and k_out must not be NULL");
-  if (n_idx < 1 || (!idx && n_idx != size)) return psis_invalid("omc_store_psis: n_idx < 1, or no index and n_idx != size");
-  if ((y != nullptr) != (prec != nullptr)) return psis_invalid("omc_store_psis: y and prec must be given together");
-  if (y && prec_size != 1 && prec_size != n_idx) return psis_invalid("omc_store_psis: prec_size must be 1 or n_idx");
-  const int64_t S = n_iter * ctx->n_chains, P = rank_pow2(S);
-  if (30 + (int64_t)floor(sqrt((double)(S - 1))) > PSIS_M_MAX) return psis_invalid("omc_store_psis: more stored draws than the fit takes (about 4 million)");
-  OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  const size_t per_elem = (size_t)P * sizeof(uint64_t) + sizeof(int32_t);
-  const int64_t Kc = rank_chunk(ctx, per_elem, n_idx);
-  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (size_t)Kc * per_elem + 64);
+  const PsisCall c = {n_iter, size, store, idx, n_idx, y, prec, prec_size, tail_max};
+  const char* null_text = store && tail_max && elpd_out && k_out ? nullptr : "store, tail_max, elpd_out and k_out must not be NULL";
+  omc_status st = psis_prelude(ctx, "omc_store_psis", c, null_text, nullptr, nullptr, 0);
   if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws.p;
-  uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
-  int32_t* flags = (int32_t*)(ws + RANK_HEAD + (size_t)Kc * P * sizeof(uint64_t));
-  // one read-back for the index and the tail lengths, before anything is written: words 0 and 1 of the head
-  int32_t* words = (int32_t*)ws;
-  OMC_HIP_CHECK(hipMemsetAsync(words, 0, 2 * sizeof(int32_t), ctx->stream));
-  omc_store_check_index_launch(ctx, idx, n_idx, size, nullptr, 0, 0, words);
-  hipLaunchKernelGGL(k_psis_check_tail, dim3((unsigned)((n_idx + 255) / 256)), dim3(256), 0, ctx->stream, tail_max, n_idx, S, words + 1);
-  OMC_HIP_CHECK(hipGetLastError());
-  int32_t got[2] = {0, 0};
-  OMC_HIP_CHECK(hipMemcpyAsync(got, words, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (got[0]) return psis_invalid("omc_store_psis: an index outside [0, size)");
-  if (got[1]) return psis_invalid("omc_store_psis: a tail_max outside [1, n_iter * C - 1]");
+  const int64_t S = n_iter * ctx->n_chains, P = rank_pow2(S);
+  RankCarve ws(ctx, (size_t)P * sizeof(uint64_t) + sizeof(int32_t), n_idx);
+  const int64_t Kc = ws.Kc;
+  uint64_t* keys = ws.take<uint64_t>((size_t)Kc * P);
+  int32_t* flags = ws.take<int32_t>(Kc);
+  st = ws.done();
+  if (st != OMC_OK) return st;
   for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {
     const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc;
-    OMC_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)kc * sizeof(int32_t), ctx->stream));
-    const dim3 grid((unsigned)((P + RANK_G_TS - 1) / RANK_G_TS), (unsigned)((kc + RANK_G_TE - 1) / RANK_G_TE));
-    hipLaunchKernelGGL(k_psis_gather, grid, dim3(256), 0, ctx->stream, store, idx, k0, kc, size, S, P, y, prec, prec_size, n_idx, keys, flags);
-    OMC_HIP_CHECK(hipGetLastError());
-    st = rank_sort(ctx, keys, kc, P);
+    st = psis_gather_sort(ctx, c, k0, kc, S, P, keys, flags);
     if (st != OMC_OK) return st;
     hipLaunchKernelGGL(k_psis_fit, dim3((unsigned)kc), dim3(PSIS_THREADS), 0, ctx->stream, k0, S, P, keys, flags, tail_max, elpd_out, k_out,
                        tail_out);

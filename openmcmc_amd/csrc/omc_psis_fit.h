@@ -34,6 +34,22 @@ struct PsisFit {
   bool smooth;           // khat is finite: the tail positions hold the fit's expected order statistics
 };
 
+// omc_psis.hip: what omc_store_psis and omc_store_loo_expect do alike on the host, on the arguments they have in common
+struct PsisCall {
+  int64_t n_iter, size;
+  const double* store; const int64_t* idx; int64_t n_idx;
+  const double *y, *prec; int64_t prec_size;
+  const int64_t* tail_max;
+};
+// Everything that can refuse the call, in one place and before anything is written: the argument checks, with the caller's two
+// complaints of its own (or NULL) -- null_text where the check of the pointers stands, own_text behind the shared checks --, the bound
+// on the draws, and ONE read-back of the check words (head of ctx->store_ws): idx against [0, size), tail_max against [1, S - 1],
+// vidx (or NULL) against [0, vsize).  Every text is "<who>: ..." through omc_invalid.
+omc_status psis_prelude(omc_ctx* ctx, const char* who, const PsisCall& c, const char* null_text, const char* own_text, const int64_t* vidx,
+                        int64_t vsize);
+// flags zeroed, the draws of selection positions [k0, k0 + kc) as keys of psis_neg_ll (k_psis_gather), rank_sort
+omc_status psis_gather_sort(omc_ctx* ctx, const PsisCall& c, int64_t k0, int64_t kc, int64_t S, int64_t P, uint64_t* keys, int32_t* flags);
+
 // v = -ll of draw s at selection position k: the entry as it lies (y == NULL), or omc_normal_ll of a mean entry
 __device__ __forceinline__ double psis_neg_ll(double x, int64_t s, int64_t k, const double* __restrict__ y, const double* __restrict__ prec,
                                               int64_t prec_size, int64_t n_idx) {

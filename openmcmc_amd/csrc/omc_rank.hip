@@ -3,8 +3,8 @@
 // The contract is in include/omcmc_hip.h (omc_store_ranks, omc_store_rank_diagnostics, omc_store_rank_schedule).
 //
 // store is [N][C][size].  A chunk of Kc selected elements is worked on at a time:
-//   k_rank_gather  the gather tile of omc_rank_sort.h: the draws of the chunk, read where they lie, as order-preserving 64-bit
-//                  keys (-0.0 first made +0.0) in columns keys [Kc][P], P the next power of two >= the S draws of a column, the
+//   k_rank_gather  (omc_store_shared.hip, through rank_gather_sort) the gather tile of omc_rank_sort.h: the draws of the chunk,
+//                  read where they lie, as order-preserving 64-bit keys (-0.0 first made +0.0) in columns keys [Kc][P], P the next power of two >= the S draws of a column, the
 //                  rest of a column the all-ones key; it notes per element whether a NaN (bit 0) or an infinity (bit 1) was
 //                  seen.  With `fold` the value is |x - med|, med the element's median from k_rank_stats.
 //   rank_sort      the key-only bitonic sort of every column (omc_store_shared.hip, shared with omc_hdi.hip).
@@ -28,25 +28,6 @@
 #include "omc_truncnorm.h"
 
 namespace {
-
-// Draw s of a column (s < S) is row s of the store seen as [N C][size] when s < first, else row s + skip: the two halves of a
-// split store, with the middle row of an odd N (rows [mid_row0, mid_row0 + C), mid_row0 < 0: none) read for its NaN / inf only.
-// stats (or NULL): fold the draws, |x - stats[3 e]|.
-__global__ void __launch_bounds__(256) k_rank_gather(const double* __restrict__ store, const int64_t* __restrict__ idx, int64_t k0, int64_t Kc,
-                                                     int64_t size, int64_t C, int64_t S, int64_t P, int64_t first, int64_t skip,
-                                                     int64_t mid_row0, const double* __restrict__ stats, uint64_t* __restrict__ keys,
-                                                     int32_t* __restrict__ flags) {
-  const int64_t e0 = (int64_t)blockIdx.y * RANK_G_TE, e = e0 + (threadIdx.x & (RANK_G_TE - 1));
-  const bool fold = stats != nullptr;
-  const double med = (fold && e < Kc) ? stats[3 * e] : 0.0;
-  int32_t bits = 0;
-  if (mid_row0 >= 0 && blockIdx.x == 0 && e < Kc) {
-    const int64_t col = idx ? idx[k0 + e] : k0 + e;
-    for (int64_t c = threadIdx.x / RANK_G_TE; c < C; c += 256 / RANK_G_TE) bits |= rank_flag_bits(store[(mid_row0 + c) * size + col]);
-  }
-  rank_gather_tile(store, idx, k0, Kc, size, S, P, e0, (int64_t)blockIdx.x * RANK_G_TS, 0,
-                   [=](int64_t s) { return s < first ? s : s + skip; }, [=](double x, int64_t, int64_t) { return fold ? fabs(x - med) : x; }, bits, keys, flags);
-}
 
 // stats [Kc][3] = median ((a + b) / 2 of the two middle order statistics: S is even), q05, q95 of the S sorted draws
 __global__ void k_rank_stats(int64_t Kc, int64_t S, int64_t P, const uint64_t* __restrict__ keys, double* __restrict__ stats) {
@@ -128,28 +109,6 @@ __global__ void k_rank_combine(int64_t Kc, int64_t k0, const int32_t* __restrict
 
 dim3 rank_emit_grid(const RankEmit& a) { return dim3((unsigned)((a.n_rows + 63) / 64), (unsigned)((a.Kc + 3) / 4)); }
 
-// the layout of a column's draws (k_rank_gather)
-struct RankGeom { int64_t S, P, first, skip, mid_row0; };
-RankGeom rank_geom(int64_t N, int64_t C, bool split) {
-  RankGeom g;
-  const int64_t M = N / 2;
-  g.S = split ? 2 * C * M : N * C;
-  g.P = rank_pow2(g.S);
-  g.first = split ? M * C : g.S;
-  g.skip = split ? (N - 2 * M) * C : 0;
-  g.mid_row0 = (split && (N & 1)) ? M * C : -1;
-  return g;
-}
-
-omc_status rank_gather(omc_ctx* ctx, const double* store, const int64_t* idx, int64_t k0, int64_t kc, int64_t size, const RankGeom& g,
-                       const double* stats, uint64_t* keys, int32_t* flags) {
-  const dim3 grid((unsigned)((g.P + RANK_G_TS - 1) / RANK_G_TS), (unsigned)((kc + RANK_G_TE - 1) / RANK_G_TE));
-  hipLaunchKernelGGL(k_rank_gather, grid, dim3(256), 0, ctx->stream, store, idx, k0, kc, size, ctx->n_chains, g.S, g.P, g.first, g.skip,
-                     g.mid_row0, stats, keys, flags);
-  OMC_HIP_CHECK(hipGetLastError());
-  return OMC_OK;
-}
-
 }  // namespace
 
 extern "C" omc_status omc_store_rank_schedule(int64_t S, int32_t tile, int64_t* out, int64_t cap, int64_t* n_out) {
@@ -166,26 +125,21 @@ extern "C" omc_status omc_store_rank_schedule(int64_t S, int32_t tile, int64_t* 
 
 extern "C" omc_status omc_store_ranks(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                                       int32_t split, double* rank_out) {
-  if (!ctx || n_iter < (split ? 4 : 1) || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size) || !rank_out) return OMC_INVALID_ARG;
+  if (!omc_selection_ok(ctx, n_iter, split ? 4 : 1, size, store, idx, n_idx) || !rank_out) return OMC_INVALID_ARG;
   const int64_t N = n_iter, C = ctx->n_chains;
   const RankGeom g = rank_geom(N, C, split != 0);
   if ((N * C + 63) / 64 > 0x7fffffffLL) return OMC_INVALID_ARG;
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
-  const size_t per_elem = (size_t)g.P * sizeof(uint64_t) + sizeof(int32_t);
-  const int64_t Kc = rank_chunk(ctx, per_elem, n_idx);
-  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (size_t)Kc * per_elem + 64);
-  if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws.p;
-  uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
-  int32_t* flags = (int32_t*)(ws + RANK_HEAD + (size_t)Kc * g.P * sizeof(uint64_t));
-  st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size);
+  RankCarve ws(ctx, (size_t)g.P * sizeof(uint64_t) + sizeof(int32_t), n_idx);
+  const int64_t Kc = ws.Kc;
+  uint64_t* keys = ws.take<uint64_t>((size_t)Kc * g.P);
+  int32_t* flags = ws.take<int32_t>(Kc);
+  omc_status st = ws.done();
+  if (st == OMC_OK) st = omc_store_check_index(ctx, ws.head(), idx, n_idx, size);
   if (st != OMC_OK) return st;
   for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {
     const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc;
-    OMC_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)kc * sizeof(int32_t), ctx->stream));
-    st = rank_gather(ctx, store, idx, k0, kc, size, g, nullptr, keys, flags);
-    if (st != OMC_OK) return st;
-    st = rank_sort(ctx, keys, kc, g.P);
+    st = rank_gather_sort(ctx, store, idx, k0, kc, size, g, nullptr, keys, flags);
     if (st != OMC_OK) return st;
     RankEmit a;
     a.store = store; a.idx = idx; a.keys = keys; a.flags = flags; a.stats = nullptr; a.out = rank_out;
@@ -199,44 +153,37 @@ extern "C" omc_status omc_store_ranks(omc_ctx* ctx, int64_t n_iter, int64_t size
 
 extern "C" omc_status omc_store_rank_diagnostics(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx,
                                                  int64_t n_idx, double* rhat_out, double* ess_bulk_out, double* ess_tail_out) {
-  if (!ctx || n_iter < 4 || size < 1 || !store || n_idx < 1 || (!idx && n_idx != size)) return OMC_INVALID_ARG;
+  if (!omc_selection_ok(ctx, n_iter, 4, size, store, idx, n_idx)) return OMC_INVALID_ARG;
   const int64_t N = n_iter, C = ctx->n_chains;
   const RankGeom g = rank_geom(N, C, true);
   if ((N * C + 63) / 64 > 0x7fffffffLL) return OMC_INVALID_ARG;
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   // per element: keys [P], the four series [N C][4], median and two quantiles, R-hat and ESS of the four series, the flag word
-  const size_t per_elem = (size_t)g.P * sizeof(uint64_t) + (size_t)N * C * 4 * sizeof(double) + (3 + 8) * sizeof(double) + sizeof(int32_t);
-  const int64_t Kc = rank_chunk(ctx, per_elem, n_idx);
-  omc_status st = omc_ensure(ctx, ctx->rank_ws, RANK_HEAD + (size_t)Kc * per_elem + 64);
-  if (st != OMC_OK) return st;
-  char* ws = (char*)ctx->rank_ws.p;
-  uint64_t* keys = (uint64_t*)(ws + RANK_HEAD);
-  double* series = (double*)(keys + (size_t)Kc * g.P);
-  double* stats = series + (size_t)N * C * 4 * Kc;
-  double* rh4 = stats + 3 * Kc;
-  double* es4 = rh4 + 4 * Kc;
-  int32_t* flags = (int32_t*)(es4 + 4 * Kc);
-  st = omc_store_check_index(ctx, (int32_t*)ws, idx, n_idx, size);
+  RankCarve ws(ctx, (size_t)g.P * sizeof(uint64_t) + (size_t)N * C * 4 * sizeof(double) + (3 + 8) * sizeof(double) + sizeof(int32_t), n_idx);
+  const int64_t Kc = ws.Kc;
+  uint64_t* keys = ws.take<uint64_t>((size_t)Kc * g.P);
+  double* series = ws.take<double>((size_t)N * C * 4 * Kc);
+  double* stats = ws.take<double>(3 * Kc);
+  double* rh4 = ws.take<double>(4 * Kc);
+  double* es4 = ws.take<double>(4 * Kc);
+  int32_t* flags = ws.take<int32_t>(Kc);
+  omc_status st = ws.done();
+  if (st == OMC_OK) st = omc_store_check_index(ctx, ws.head(), idx, n_idx, size);
   if (st != OMC_OK) return st;
   hipStream_t s = ctx->stream;
   for (int64_t k0 = 0; k0 < n_idx; k0 += Kc) {
     const int64_t kc = n_idx - k0 < Kc ? n_idx - k0 : Kc;
-    OMC_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)kc * sizeof(int32_t), s));
     RankEmit a;
     a.store = store; a.idx = idx; a.keys = keys; a.flags = flags; a.stats = stats; a.out = series;
     a.k0 = k0; a.Kc = kc; a.size = size; a.C = C; a.S = g.S; a.P = g.P; a.n_rows = N * C; a.mid_row0 = g.mid_row0; a.ld_out = 0;
     // the draws: z and the tail indicators
-    st = rank_gather(ctx, store, idx, k0, kc, size, g, nullptr, keys, flags);
-    if (st != OMC_OK) return st;
-    st = rank_sort(ctx, keys, kc, g.P);
+    st = rank_gather_sort(ctx, store, idx, k0, kc, size, g, nullptr, keys, flags);
     if (st != OMC_OK) return st;
     hipLaunchKernelGGL(k_rank_stats, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, s, kc, g.S, g.P, keys, stats);
     a.mode = RANK_EMIT_Z;
     hipLaunchKernelGGL(k_rank_emit, rank_emit_grid(a), dim3(256), 0, s, a);
     // the folded draws |x - med|
-    st = rank_gather(ctx, store, idx, k0, kc, size, g, stats, keys, nullptr);
-    if (st != OMC_OK) return st;
-    st = rank_sort(ctx, keys, kc, g.P);
+    st = rank_gather_sort(ctx, store, idx, k0, kc, size, g, stats, keys, nullptr);
     if (st != OMC_OK) return st;
     a.mode = RANK_EMIT_ZFOLD;
     hipLaunchKernelGGL(k_rank_emit, rank_emit_grid(a), dim3(256), 0, s, a);

@@ -1,6 +1,9 @@
 // What the store summaries that need every order statistic of a column share (omc_rank.hip: ranks and the rank-normalised
-// diagnostics; omc_hdi.hip: highest-density intervals).  Inline on the device: the key of a draw, the gather of a tile of draws
-// into columns of keys, the bisection in a sorted column.  The sort itself is compiled once, in omc_store_shared.hip:
+// diagnostics; omc_hdi.hip: highest-density intervals; omc_essq.hip: indicator ESS and order statistics; omc_psis.hip and
+// omc_loo_expect.hip: the importance ratios).  Inline on the device: the key of a draw, the gather of a tile of draws into columns
+// of keys, the bisection in a sorted column.  On the host: the geometry of a whole or split column (RankGeom) and the cursor that
+// sizes and carves ctx->rank_ws for a chunk (RankCarve).  Compiled once, in omc_store_shared.hip: the gather of such columns
+// (k_rank_gather behind rank_gather_sort) and the sort itself:
 //
 //   k_rank_sort_tile / k_rank_sort_global
 //                  a bitonic network over every column, keys only.  Its addressing depends on P and the tile T alone, never on
@@ -34,10 +37,69 @@ inline int64_t rank_pow2(int64_t S) {
   return P;
 }
 
+// The layout of a column's draws for k_rank_gather: draw s of a column (s < S) is row s of the store seen as [N C][size] when
+// s < first, else row s + skip -- the two halves of a split store --, and the middle row of an odd N (rows [mid_row0, mid_row0 + C),
+// mid_row0 < 0: none) is read for its NaN / inf only.
+struct RankGeom { int64_t S, P, first, skip, mid_row0; };
+inline RankGeom rank_geom(int64_t N, int64_t C, bool split) {
+  RankGeom g;
+  const int64_t M = N / 2;
+  g.S = split ? 2 * C * M : N * C;
+  g.P = rank_pow2(g.S);
+  g.first = split ? M * C : g.S;
+  g.skip = split ? (N - 2 * M) * C : 0;
+  g.mid_row0 = (split && (N & 1)) ? M * C : -1;
+  return g;
+}
+
 // omc_store_shared.hip
 std::vector<RankLaunch> rank_schedule(int64_t P, int64_t T);              // the launches that sort columns of P keys with tiles of T
 omc_status rank_sort(omc_ctx* ctx, uint64_t* keys, int64_t Kc, int64_t P);  // sorts the Kc columns of P keys
 int64_t rank_chunk(const omc_ctx* ctx, size_t per_elem, int64_t n_idx);   // Kc (above)
+// k_rank_gather and rank_sort: the draws of selected elements [k0, k0 + kc) as sorted columns keys [kc][g.P]; with stats the draws
+// are folded, |x - stats[3 e]|.  flags (or NULL: left as they are) are zeroed first and then hold what the gather saw.
+omc_status rank_gather_sort(omc_ctx* ctx, const double* store, const int64_t* idx, int64_t k0, int64_t kc, int64_t size, const RankGeom& g,
+                            const double* stats, uint64_t* keys, int32_t* flags);
+
+// A cursor over ctx->rank_ws behind RANK_HEAD, for a caller that works on chunks of Kc elements at per_elem bytes each.  Kc is
+// rank_chunk's; a caller with a limit of its own lowers it before the first take().  The first take() asks omc_ensure for
+// RANK_HEAD + Kc per_elem + 64 bytes; every take() hands out the next n objects of T where the cursor stands, so the arrays lie in
+// the order they are taken, nothing between them.  done() is what the caller returns on failure: omc_ensure's status, or
+// OMC_HIP_ERROR with a text if a take was misaligned or the cursor has passed the bytes asked for -- per_elem and the takes disagree,
+// and nothing has been launched yet.
+struct RankCarve {
+  omc_ctx* ctx;
+  size_t per_elem;
+  int64_t Kc;
+  char *at = nullptr, *end = nullptr;
+  omc_status st = OMC_OK;
+  bool aligned = true;
+
+  RankCarve(omc_ctx* c, size_t per_elem_, int64_t n_idx) : ctx(c), per_elem(per_elem_), Kc(rank_chunk(c, per_elem_, n_idx)) {}
+
+  template <typename T>
+  T* take(size_t n) {
+    if (!at && st == OMC_OK) {
+      const size_t need = RANK_HEAD + (size_t)Kc * per_elem + 64;
+      st = omc_ensure(ctx, ctx->rank_ws, need);
+      if (st != OMC_OK) return nullptr;
+      at = (char*)ctx->rank_ws.p + RANK_HEAD;
+      end = (char*)ctx->rank_ws.p + need;
+    }
+    if (st != OMC_OK) return nullptr;
+    T* p = (T*)at;
+    aligned = aligned && (uintptr_t)at % alignof(T) == 0;
+    at += n * sizeof(T);
+    return p;
+  }
+  int32_t* head() const { return (int32_t*)ctx->rank_ws.p; }  // the check words in front of the arrays
+  omc_status done() const {
+    if (st != OMC_OK || (aligned && at <= end)) return st;
+    omc_set_error_text(aligned ? "rank_ws: the arrays of a chunk pass the bytes their caller sized the workspace with"
+                               : "rank_ws: an array of a chunk is not aligned for its type");
+    return OMC_HIP_ERROR;
+  }
+};
 
 __device__ __forceinline__ uint64_t rank_key(double v) {
   if (v == 0.0) v = 0.0;  // -0.0 and +0.0 are one value

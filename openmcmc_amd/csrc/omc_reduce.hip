@@ -225,11 +225,6 @@ __global__ void __launch_bounds__(RED_THREADS) k_reduce_short(RedArgs g) {
   if (t < n_rows && sub == 0) red_write(g, row0 + t, acc);
 }
 
-omc_status red_invalid(const char* text) {
-  omc_set_error_text(text);
-  return OMC_INVALID_ARG;
-}
-
 template <int OP>
 void red_launch(omc_ctx* ctx, const RedArgs& g, bool short_form) {
   if (short_form) {
@@ -246,17 +241,17 @@ void red_launch(omc_ctx* ctx, const RedArgs& g, bool short_form) {
 
 extern "C" omc_status omc_store_reduce(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                                        int32_t op, int32_t omit_nan, const double* a, const double* b, double* out, int64_t* count_out) {
-  if (!ctx) return red_invalid("omc_store_reduce: no context");
-  if (n_iter < 1) return red_invalid("omc_store_reduce: n_iter < 1");
-  if (size < 1) return red_invalid("omc_store_reduce: size < 1");
-  if (!store || !out) return red_invalid("omc_store_reduce: store and out must not be NULL");
-  if (n_idx < 1 || (!idx && n_idx != size)) return red_invalid("omc_store_reduce: n_idx < 1, or no index and n_idx != size");
-  if (op < OMC_REDUCE_SUM || op > OMC_REDUCE_SUPNORM) return red_invalid("omc_store_reduce: unknown op");
-  if (op == OMC_REDUCE_COUNT_ABOVE && !a) return red_invalid("omc_store_reduce: COUNT_ABOVE needs the thresholds a");
-  if (op == OMC_REDUCE_SUPNORM && (!a || !b)) return red_invalid("omc_store_reduce: SUPNORM needs the centres a and the scales b");
+  if (!ctx) return omc_invalid("omc_store_reduce: no context");
+  if (n_iter < 1) return omc_invalid("omc_store_reduce: n_iter < 1");
+  if (size < 1) return omc_invalid("omc_store_reduce: size < 1");
+  if (!store || !out) return omc_invalid("omc_store_reduce: store and out must not be NULL");
+  if (n_idx < 1 || (!idx && n_idx != size)) return omc_invalid("omc_store_reduce: n_idx < 1, or no index and n_idx != size");
+  if (op < OMC_REDUCE_SUM || op > OMC_REDUCE_SUPNORM) return omc_invalid("omc_store_reduce: unknown op");
+  if (op == OMC_REDUCE_COUNT_ABOVE && !a) return omc_invalid("omc_store_reduce: COUNT_ABOVE needs the thresholds a");
+  if (op == OMC_REDUCE_SUPNORM && (!a || !b)) return omc_invalid("omc_store_reduce: SUPNORM needs the centres a and the scales b");
   OMC_HIP_CHECK(hipSetDevice(ctx->device));
   const omc_status st = omc_store_check_index(ctx, nullptr, idx, n_idx, size);
-  if (st == OMC_INVALID_ARG) return red_invalid("omc_store_reduce: an index outside [0, size)");  // (the helper's only use of that status)
+  if (st == OMC_INVALID_ARG) return omc_invalid("omc_store_reduce: an index outside [0, size)");  // (the helper's only use of that status)
   if (st != OMC_OK) return st;
   const StoreView v = omc_store_view(ctx, n_iter, size, true, store, idx, n_idx);  // pooled: R rows of row_stride = size doubles
   const int64_t R = v.R;
@@ -277,7 +272,7 @@ extern "C" omc_status omc_store_reduce(omc_ctx* ctx, int64_t n_iter, int64_t siz
   // rows beyond the LDS budget take the long form whatever the option says
   const bool short_form = TR >= 1 && (ctx->reduce_algo == 1 || (ctx->reduce_algo == 0 && size <= RED_SHORT_AUTO));
   const int64_t blocks = short_form ? (R + TR - 1) / TR : (R * g.wpr + RED_THREADS / 64 - 1) / (RED_THREADS / 64);
-  if (blocks > 0x7fffffffLL) return red_invalid("omc_store_reduce: more rows than one launch takes");
+  if (blocks > 0x7fffffffLL) return omc_invalid("omc_store_reduce: more rows than one launch takes");
   switch (op) {
     case OMC_REDUCE_SUM: red_launch<OMC_REDUCE_SUM>(ctx, g, short_form); break;
     case OMC_REDUCE_MIN: red_launch<OMC_REDUCE_MIN>(ctx, g, short_form); break;

@@ -11,8 +11,10 @@
 //                         slice boundaries and combination order are functions of the shape alone.  Two instantiations of
 //                         the one source, with and without an index: with the index a run-time branch the pass was up to 2 %
 //                         slower than the two kernels it replaces (profiles/store_refactor_ab.txt).
+//   k_rank_gather         the draws of a chunk of selected elements, whole or split in halves, as columns of keys (the gather tile of
+//                         omc_rank_sort.h; rank_gather_sort: omc_rank.hip, omc_essq.hip).
 //   k_rank_sort_tile / k_rank_sort_global
-//                         the key-only bitonic sort of omc_rank.hip and omc_hdi.hip (described in omc_rank_sort.h).
+//                         the key-only bitonic sort of every summary that needs order statistics (described in omc_rank_sort.h).
 #include "omc_moments.h"
 #include "omc_rank_sort.h"
 #include "omc_store_view.h"
@@ -145,6 +147,23 @@ __global__ void __launch_bounds__(256) k_rank_sort_global(uint64_t* __restrict__
   if ((a > b) == (((i & (P - 1)) & k) == 0)) { keys[i] = b; keys[i2] = a; }
 }
 
+// the gather tile of omc_rank_sort.h over the draws of RankGeom; stats (or NULL): fold the draws, |x - stats[3 e]|
+__global__ void __launch_bounds__(256) k_rank_gather(const double* __restrict__ store, const int64_t* __restrict__ idx, int64_t k0, int64_t Kc,
+                                                     int64_t size, int64_t C, int64_t S, int64_t P, int64_t first, int64_t skip,
+                                                     int64_t mid_row0, const double* __restrict__ stats, uint64_t* __restrict__ keys,
+                                                     int32_t* __restrict__ flags) {
+  const int64_t e0 = (int64_t)blockIdx.y * RANK_G_TE, e = e0 + (threadIdx.x & (RANK_G_TE - 1));
+  const bool fold = stats != nullptr;
+  const double med = (fold && e < Kc) ? stats[3 * e] : 0.0;
+  int32_t bits = 0;
+  if (mid_row0 >= 0 && blockIdx.x == 0 && e < Kc) {
+    const int64_t col = idx ? idx[k0 + e] : k0 + e;
+    for (int64_t c = threadIdx.x / RANK_G_TE; c < C; c += 256 / RANK_G_TE) bits |= rank_flag_bits(store[(mid_row0 + c) * size + col]);
+  }
+  rank_gather_tile(store, idx, k0, Kc, size, S, P, e0, (int64_t)blockIdx.x * RANK_G_TS, 0,
+                   [=](int64_t s) { return s < first ? s : s + skip; }, [=](double x, int64_t, int64_t) { return fold ? fabs(x - med) : x; }, bits, keys, flags);
+}
+
 }  // namespace
 
 void omc_store_check_index_launch(omc_ctx* ctx, const int64_t* idx_a, int64_t n_a, int64_t size_a, const int64_t* idx_b, int64_t n_b,
@@ -164,12 +183,12 @@ omc_status omc_store_check_index(omc_ctx* ctx, int32_t* word, const int64_t* idx
     if (st != OMC_OK) return st;
     word = (int32_t*)ctx->store_ws.p;
   }
-  OMC_HIP_CHECK(hipMemsetAsync(word, 0, sizeof(int32_t), ctx->stream));
+  omc_status st = omc_words_zero(ctx, word, 1);
+  if (st != OMC_OK) return st;
   omc_store_check_index_launch(ctx, idx_a, n_a, size_a, idx_b, n_b, size_b, word);
-  OMC_HIP_CHECK(hipGetLastError());
   int32_t got = 0;
-  OMC_HIP_CHECK(hipMemcpyAsync(&got, word, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  OMC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  st = omc_words_read(ctx, word, 1, &got);
+  if (st != OMC_OK) return st;
   return got ? OMC_INVALID_ARG : OMC_OK;
 }
 
@@ -178,13 +197,9 @@ omc_status omc_col_moments(omc_ctx* ctx, const StoreView& view, double* mean_out
   if (!v.idx) {  // every column takes part: the batches are adjacent columns of one matrix, tiled without regard to their borders
     v.n *= v.batches; v.batches = 1; v.batch_stride = 0;
   }
-  // row slices: about 2048 workgroups, no slice shorter than 256 rows (a function of the shape only)
   const int64_t tiles = (v.n + M_COLS - 1) / M_COLS, groups = tiles * v.batches;
-  int64_t slices = (2048 + groups - 1) / groups;
-  if (slices > (v.R + 255) / 256) slices = (v.R + 255) / 256;
-  if (slices < 1) slices = 1;
-  if (slices > 1024) slices = 1024;
-  const int64_t rpb = (v.R + slices - 1) / slices;
+  int64_t rpb;
+  const int64_t slices = omc_row_slices(groups, v.R, &rpb);
   omc_status st = omc_ensure(ctx, ctx->store_ws, (size_t)slices * v.batches * 3 * v.n * sizeof(double));
   if (st != OMC_OK) return st;
   double* part = (double*)ctx->store_ws.p;
@@ -233,6 +248,16 @@ omc_status rank_sort(omc_ctx* ctx, uint64_t* keys, int64_t Kc, int64_t P) {
   }
   OMC_HIP_CHECK(hipGetLastError());
   return OMC_OK;
+}
+
+omc_status rank_gather_sort(omc_ctx* ctx, const double* store, const int64_t* idx, int64_t k0, int64_t kc, int64_t size, const RankGeom& g,
+                            const double* stats, uint64_t* keys, int32_t* flags) {
+  if (flags) OMC_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)kc * sizeof(int32_t), ctx->stream));
+  const dim3 grid((unsigned)((g.P + RANK_G_TS - 1) / RANK_G_TS), (unsigned)((kc + RANK_G_TE - 1) / RANK_G_TE));
+  hipLaunchKernelGGL(k_rank_gather, grid, dim3(256), 0, ctx->stream, store, idx, k0, kc, size, ctx->n_chains, g.S, g.P, g.first, g.skip,
+                     g.mid_row0, stats, keys, flags);
+  OMC_HIP_CHECK(hipGetLastError());
+  return rank_sort(ctx, keys, kc, g.P);
 }
 
 int64_t rank_chunk(const omc_ctx* ctx, size_t per_elem, int64_t n_idx) {

@@ -21,6 +21,24 @@ inline StoreView omc_store_view(const omc_ctx* ctx, int64_t n_iter, int64_t size
   return StoreView{data, idx, pooled ? size : C * size, pooled ? 0 : size, pooled ? n_iter * C : n_iter, pooled ? 1 : C, idx ? n : size};
 }
 
+// what an entry point that answers a bad selection with a bare OMC_INVALID_ARG asks of it: a context, at least min_iter iterations,
+// a store of rows of size >= 1, n_idx >= 1 selected elements, and without an index every element of a row
+inline bool omc_selection_ok(const omc_ctx* ctx, int64_t n_iter, int64_t min_iter, int64_t size, const double* store, const int64_t* idx,
+                             int64_t n_idx) {
+  return ctx && n_iter >= min_iter && size >= 1 && store && n_idx >= 1 && (idx || n_idx == size);
+}
+
+// Row slices of a pass whose workgroups each own one of `groups` sets of columns and a slice of the rows: about 2048 workgroups, no
+// slice shorter than 256 rows, at most 1024 slices -- a function of the shape only.  Returns the slices.
+inline int64_t omc_row_slices(int64_t groups, int64_t rows, int64_t* rows_per_block) {
+  int64_t slices = (2048 + groups - 1) / groups;
+  if (slices > (rows + 255) / 256) slices = (rows + 255) / 256;
+  if (slices < 1) slices = 1;
+  if (slices > 1024) slices = 1024;
+  *rows_per_block = (rows + slices - 1) / slices;
+  return slices;
+}
+
 // omc_store_shared.hip
 // One read-back for one or two selections, before anything reads through them: OMC_INVALID_ARG if an entry of idx_a lies outside
 // [0, size_a) or one of idx_b outside [0, size_b).  A NULL selection passes.  word: a device word of the caller's workspace, or

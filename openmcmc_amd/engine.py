@@ -56,8 +56,8 @@ class Engine:
         self._quad_cache, self._logdet_cache, self._shared_cache, self._band_cache, self._model_cache = {}, {}, {}, {}, {}
 
     # ------------------------------------------------------------------ memory helpers
-    def empty(self, *shape):
-        return _torch().empty(*shape, dtype=_torch().float64, device=self.device)
+    def empty(self, *shape, dtype=None):
+        return _torch().empty(*shape, dtype=dtype or _torch().float64, device=self.device)
 
     def zeros(self, *shape):
         return _torch().zeros(*shape, dtype=_torch().float64, device=self.device)
@@ -1213,27 +1213,52 @@ class Engine:
         if n_iter < 4:
             raise ValueError("split R-hat and ESS need at least 4 stored iterations")
         rhat, ess = self.empty(size), self.empty(size)
-        lags = _torch().empty(size, dtype=_torch().int32, device=self.device)
+        lags = self.empty(size, dtype=_torch().int32)
         check(lib.omc_store_rhat_ess(self._ctx, n_iter, size, self._p(store), self._p(rhat), self._p(ess), lags.data_ptr()))
         return rhat, ess, lags
+
+    @staticmethod
+    def _check_text(st):
+        """check() for an entry point that says which argument it refuses: INVALID_ARG raises ValueError with the library's text"""
+        if st == _abi.INVALID_ARG:
+            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
+        check(st)
+
+    def _int64(self, v, what, empty_ok=True):
+        """device int64 tensor of a host array (uploaded synchronously) or a tensor of integers; empty_ok: an empty host
+        sequence passes whatever its type, for the caller's own complaint about the shape"""
+        torch = _torch()
+        if isinstance(v, torch.Tensor):
+            if v.is_floating_point() or v.dtype is torch.bool:
+                raise ValueError(f"{what} must hold integers")
+            return v.to(device=self.device, dtype=torch.int64).contiguous()
+        arr = np.asarray(v)
+        if (arr.size or not empty_ok) and arr.dtype.kind not in "iu":
+            raise ValueError(f"{what} must hold integers")
+        # (torch.tensor copies from the numpy array before it returns: no asynchronous read of a temporary)
+        return torch.tensor(np.ascontiguousarray(arr, dtype=np.int64), dtype=torch.int64, device=self.device)
+
+    def _f64(self, v):
+        """contiguous device fp64 tensor of a host array (uploaded synchronously) or a tensor"""
+        torch = _torch()
+        if isinstance(v, torch.Tensor):
+            return v.to(device=self.device, dtype=torch.float64).contiguous()
+        # (torch.tensor copies from the numpy array before it returns: no asynchronous read of a temporary)
+        return torch.tensor(np.ascontiguousarray(v, dtype=np.float64), dtype=torch.float64, device=self.device)
 
     def _store_index(self, index, size):
         """(device int64 tensor or None, number of selected elements) of an element selection of a store"""
         if index is None:
             return None, size
-        torch = _torch()
-        if isinstance(index, torch.Tensor):
-            if index.is_floating_point() or index.dtype is torch.bool:
-                raise ValueError("index must hold integers")
-            idx = index.to(device=self.device, dtype=torch.int64).contiguous()
-        else:
-            arr = np.asarray(index)
-            if arr.size and arr.dtype.kind not in "iu":
-                raise ValueError("index must hold integers")
-            idx = torch.as_tensor(np.ascontiguousarray(arr, dtype=np.int64), device=self.device)
+        idx = self._int64(index, "index")
         if idx.dim() != 1 or idx.numel() < 1:
             raise ValueError("index must be a non-empty one-dimensional sequence")
         return idx, idx.numel()
+
+    def _selection(self, store, index):
+        """(n_iter, size, device int64 tensor or None, number of selected elements) of a store and a selection of its elements"""
+        n_iter, size = self._store_shape(store)
+        return (n_iter, size) + self._store_index(index, size)
 
     def store_cov(self, store_a, store_b=None, index_a=None, index_b=None, pooled=True, correlation=False):
         """Covariance (correlation=True: correlation) matrix of the elements of a device store (n_iter, C, size_a), or of
@@ -1275,11 +1300,10 @@ class Engine:
         (omc_store_minmax): np.nanmin, np.nanmax and the number of non-NaN draws, shape (n_idx,) pooled over chains and
         iterations, else (C, n_idx); count is int64; an element without a non-NaN draw gives NaN, NaN, 0."""
         torch = _torch()
-        n_iter, size = self._store_shape(store)
-        idx, n = self._store_index(index, size)
+        n_iter, size, idx, n = self._selection(store, index)
         shape = (n,) if pooled else (self.n_chains, n)
         mn, mx = self.empty(*shape), self.empty(*shape)
-        cnt = torch.empty(shape, dtype=torch.int64, device=self.device)
+        cnt = self.empty(shape, dtype=torch.int64)
         check(lib.omc_store_minmax(self._ctx, n_iter, size, self._p(store), _ptr(idx), n,
                                    int(bool(pooled)), self._p(mn), self._p(mx), cnt.data_ptr()))
         return mn, mx, cnt
@@ -1290,17 +1314,16 @@ class Engine:
         (.., 3) = draws below edges[0], above edges[-1], NaN.  edges: 1-D (n_bins + 1,) shared by all elements or 2-D
         (n_idx, n_bins + 1) per element, a host array (uploaded synchronously) or a device tensor; non-decreasing, no NaN."""
         torch = _torch()
-        n_iter, size = self._store_shape(store)
-        idx, n = self._store_index(index, size)
-        e = self._store_edges(edges)
+        n_iter, size, idx, n = self._selection(store, index)
+        e = self._f64(edges)
         if e.dim() not in (1, 2) or (e.dim() == 2 and e.shape[0] != n):
             raise ValueError("edges must be (n_bins + 1,) or (number of selected elements, n_bins + 1)")
         n_bins = e.shape[-1] - 1
         if not 1 <= n_bins <= 1024:
             raise ValueError("between 1 and 1024 bins")
         lead = (n,) if pooled else (self.n_chains, n)
-        counts = torch.empty(lead + (n_bins,), dtype=torch.int64, device=self.device)
-        outside = torch.empty(lead + (3,), dtype=torch.int64, device=self.device)
+        counts = self.empty(lead + (n_bins,), dtype=torch.int64)
+        outside = self.empty(lead + (3,), dtype=torch.int64)
         check(lib.omc_store_histogram(self._ctx, n_iter, size, self._p(store), _ptr(idx), n,
                                       int(bool(pooled)), n_bins, e.data_ptr(), int(e.dim() == 2), counts.data_ptr(), outside.data_ptr()))
         return counts, outside
@@ -1349,7 +1372,7 @@ class Engine:
         bw_in = None if bw is None else column(bw, "bw")
         density = torch.empty(lead + (G,), dtype=torch.float64, device=self.device)
         bw_out, mode = (torch.empty(lead, dtype=torch.float64, device=self.device) for _ in range(2))
-        flag = torch.empty(lead, dtype=torch.int32, device=self.device)
+        flag = self.empty(lead, dtype=torch.int32)
         check(lib.omc_kde_binned(self._ctx, n_cols, G, counts.data_ptr(), self._p(lo), self._p(hi), self.KDE_RULES[rule],
                                  self._p(bw_in), float(bw_fct), int(bool(reflect[0])) | 2 * int(bool(reflect[1])),
                                  self._p(density), self._p(bw_out), flag.data_ptr(), self._p(mode)))
@@ -1372,13 +1395,6 @@ class Engine:
         check(lib.omc_store_histogram2d_layout(int(nx), int(ny), int(bool(per_pair)), int(pool_pairs), out))
         return list(out)
 
-    def _store_edges(self, edges):
-        torch = _torch()
-        if isinstance(edges, torch.Tensor):
-            return edges.to(device=self.device, dtype=torch.float64).contiguous()
-        # (torch.tensor copies from the numpy array before it returns: no asynchronous read of a temporary)
-        return torch.tensor(np.ascontiguousarray(edges, dtype=np.float64), dtype=torch.float64, device=self.device)
-
     def store_histogram2d(self, store_x, store_y, edges_x, edges_y, index_x=None, index_y=None, pooled=True, pool_pairs=False,
                           occupancy=False):
         """(counts, outside[, occupied]) of pairs of elements of device stores (n_iter, C, size_x) and (n_iter, C, size_y) -- the
@@ -1400,7 +1416,7 @@ class Engine:
         idx_y, n_y = self._store_index(index_y, size_y)
         if n != n_y:
             raise ValueError(f"{n} elements of x against {n_y} of y: pairs need equally many")
-        ex, ey = self._store_edges(edges_x), self._store_edges(edges_y)
+        ex, ey = self._f64(edges_x), self._f64(edges_y)
         if ex.dim() != ey.dim() or ex.dim() not in (1, 2) or (ex.dim() == 2 and (ex.shape[0] != n or ey.shape[0] != n)):
             raise ValueError("edges must be (nx + 1,) and (ny + 1,), or (number of pairs, nx + 1) and (number of pairs, ny + 1)")
         if ex.dim() == 2 and pool_pairs:
@@ -1411,9 +1427,9 @@ class Engine:
         if not (1 <= nx <= 1024 and 1 <= ny <= 1024):
             raise ValueError("between 1 and 1024 bins per axis")
         lead = (() if pooled else (self.n_chains,)) + (() if pool_pairs else (n,))
-        counts = torch.empty(lead + (nx, ny), dtype=torch.int64, device=self.device)
-        outside = torch.empty(lead + (2,), dtype=torch.int64, device=self.device)
-        occupied = torch.empty(lead + (nx, ny), dtype=torch.int64, device=self.device) if occupancy else None
+        counts = self.empty(lead + (nx, ny), dtype=torch.int64)
+        outside = self.empty(lead + (2,), dtype=torch.int64)
+        occupied = self.empty(lead + (nx, ny), dtype=torch.int64) if occupancy else None
         check(lib.omc_store_histogram2d(self._ctx, n_iter, size_x, self._p(store_x), _ptr(idx_x),
                                         size_y, self._p(store_y), _ptr(idx_y), n, int(bool(pooled)),
                                         int(bool(pool_pairs)), nx, ex.data_ptr(), ny, ey.data_ptr(), int(ex.dim() == 2),
@@ -1435,10 +1451,9 @@ class Engine:
         (omc_store_ranks): a device tensor (n_iter, C, n_idx), scipy.stats.rankdata(method="average") of the element's
         n_iter * C draws, bit for bit.  split=True: ranks among the split draws (first and last n_iter // 2 iterations of
         every chain, n_iter >= 4), NaN in the dropped middle row of an odd n_iter.  An element with a NaN draw gives NaN."""
-        n_iter, size = self._store_shape(store)
+        n_iter, size, idx, n = self._selection(store, index)
         if n_iter < (4 if split else 1):
             raise ValueError("split ranks need at least 4 stored iterations")
-        idx, n = self._store_index(index, size)
         out = self.empty(n_iter, self.n_chains, n)
         check(lib.omc_store_ranks(self._ctx, n_iter, size, self._p(store), _ptr(idx), n,
                                   int(bool(split)), self._p(out)))
@@ -1448,10 +1463,9 @@ class Engine:
         """Rank-normalised split R-hat, bulk-ESS and tail-ESS (Vehtari et al. 2021) of every selected element of a device
         store (n_iter, C, size), on the device (omc_store_rank_diagnostics): (rhat, ess_bulk, ess_tail) as device tensors
         of shape (n_idx,).  n_iter >= 4; an element with a NaN or infinite draw gives NaN."""
-        n_iter, size = self._store_shape(store)
+        n_iter, size, idx, n = self._selection(store, index)
         if n_iter < 4:
             raise ValueError("rank-normalised R-hat and ESS need at least 4 stored iterations")
-        idx, n = self._store_index(index, size)
         rhat, bulk, tail = self.empty(n), self.empty(n), self.empty(n)
         check(lib.omc_store_rank_diagnostics(self._ctx, n_iter, size, self._p(store), _ptr(idx), n,
                                              self._p(rhat), self._p(bulk), self._p(tail)))
@@ -1467,7 +1481,7 @@ class Engine:
         <= n_iter // 2 (include/omcmc_hip.h).  Intervals beyond 32 go in groups of 32.  algo: 0 auto, 1 bits in LDS, 2 bits in
         global memory -- same bits.  n_iter >= 4; an element with a NaN or infinite draw gives NaN."""
         torch = _torch()
-        n_iter, size = self._store_shape(store)
+        n_iter, size, idx, n = self._selection(store, index)
         if n_iter < 4:
             raise ValueError("the ESS of an indicator needs at least 4 stored iterations")
         hi = np.ascontiguousarray(np.atleast_1d(np.asarray(prob_hi, dtype=np.float64)))
@@ -1475,11 +1489,10 @@ class Engine:
         if hi.ndim != 1 or hi.size < 1 or lo.shape != hi.shape:
             raise ValueError("prob_lo and prob_hi must be equally long non-empty one-dimensional sequences")
         n_cnt = int(counts)
-        idx, n = self._store_index(index, size)
         n_p = hi.size
         ess, q = self.empty(n_p, n), self.empty(n_p, n, 2)
-        lags = torch.empty((n_p, n), dtype=torch.int32, device=self.device)
-        cnt = torch.empty((n_p, n, 2 + 2 * n_cnt), dtype=torch.int64, device=self.device) if n_cnt > 0 else None
+        lags = self.empty((n_p, n), dtype=torch.int32)
+        cnt = self.empty((n_p, n, 2 + 2 * n_cnt), dtype=torch.int64) if n_cnt > 0 else None
         dp = C.POINTER(C.c_double)
         for i in range(0, n_p, 32):  # at most 32 intervals per call of omc_store_ess_indicator
             m = min(32, n_p - i)
@@ -1495,20 +1508,10 @@ class Engine:
         draws (split=True: first and last n_iter // 2 iterations of every chain, n_iter >= 4) or all n_iter * C draws.  pos:
         integers (n_idx, n_pos), a host array or a device tensor; a position outside the column raises ValueError.  An element
         with a NaN draw gives NaN; a zero comes back as +0.0."""
-        torch = _torch()
-        n_iter, size = self._store_shape(store)
+        n_iter, size, idx, n = self._selection(store, index)
         if n_iter < (4 if split else 1):
             raise ValueError("split order statistics need at least 4 stored iterations")
-        idx, n = self._store_index(index, size)
-        if isinstance(pos, torch.Tensor):
-            if pos.is_floating_point() or pos.dtype is torch.bool:
-                raise ValueError("pos must hold integers")
-            p = pos.to(device=self.device, dtype=torch.int64).contiguous()
-        else:
-            arr = np.asarray(pos)
-            if arr.dtype.kind not in "iu":
-                raise ValueError("pos must hold integers")
-            p = torch.tensor(np.ascontiguousarray(arr, dtype=np.int64), dtype=torch.int64, device=self.device)
+        p = self._int64(pos, "pos", empty_ok=False)
         if p.dim() != 2 or p.shape[0] != n or p.shape[1] < 1:
             raise ValueError(f"pos must be (number of selected elements = {n}, n_pos), got shape {tuple(p.shape)}")
         out = self.empty(n, p.shape[1])
@@ -1525,16 +1528,15 @@ class Engine:
         each inside (0, 1); a scalar is one probability (n_prob = 1).  omit_nan leaves NaN draws out; without it a column
         with a NaN gives NaN.  A column with an infinite draw or without a valid draw gives NaN."""
         torch = _torch()
-        n_iter, size = self._store_shape(store)
+        n_iter, size, idx, n = self._selection(store, index)
         probs = np.atleast_1d(np.asarray(prob, dtype=np.float64))
         if probs.ndim != 1 or not 1 <= probs.size <= 8:
             raise ValueError("prob must be a number or a sequence of 1 to 8 numbers")
         if not np.all((probs > 0) & (probs < 1)):
             raise ValueError("every prob must lie inside (0, 1)")
-        idx, n = self._store_index(index, size)
         lead = (probs.size,) if pooled else (probs.size, self.n_chains)
         out = self.empty(*lead, n, 2)
-        cnt = torch.empty(lead[1:] + (n,), dtype=torch.int64, device=self.device)
+        cnt = self.empty(lead[1:] + (n,), dtype=torch.int64)
         host = (C.c_double * probs.size)(*probs.tolist())
         check(lib.omc_store_hdi(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, host, probs.size,
                                 int(not pooled), int(bool(omit_nan)), self._p(out), cnt.data_ptr()))
@@ -1546,11 +1548,7 @@ class Engine:
         """device fp64 (n,) of a vector aligned with the selection: a host array or a device tensor, a scalar is broadcast"""
         if v is None:
             return None
-        torch = _torch()
-        if isinstance(v, torch.Tensor):
-            t = v.to(device=self.device, dtype=torch.float64)
-        else:  # (torch.tensor copies from the numpy array before it returns: no asynchronous read of a temporary)
-            t = torch.tensor(np.ascontiguousarray(v, dtype=np.float64), dtype=torch.float64, device=self.device)
+        t = self._f64(v)
         if t.numel() == 1:
             t = t.reshape(1).expand(n)
         if t.dim() != 1 or t.shape[0] != n:
@@ -1567,19 +1565,16 @@ class Engine:
         "argmin" / "argmax" the position of the first NaN.  a, b: host arrays or device tensors with one value per SELECTED
         element, scalars are broadcast.  "sum" is within n_idx 2^-53 sum|terms| of the exact sum, everything else is exact."""
         torch = _torch()
-        n_iter, size = self._store_shape(store)
+        n_iter, size, idx, n = self._selection(store, index)
         code = self.REDUCE_OPS.get(op)
         if code is None:
             raise ValueError(f"unknown reduction {op!r}: one of {', '.join(self.REDUCE_OPS)}")
-        idx, n = self._store_index(index, size)
         av, bv = self._reduce_vector(a, n, "a"), self._reduce_vector(b, n, "b")
         out = self.empty(n_iter, self.n_chains)
-        cnt = torch.empty((n_iter, self.n_chains), dtype=torch.int64, device=self.device)
+        cnt = self.empty((n_iter, self.n_chains), dtype=torch.int64)
         st = lib.omc_store_reduce(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, code,
                                   int(bool(omit_nan)), self._p(av), self._p(bv), self._p(out), cnt.data_ptr())
-        if st == _abi.INVALID_ARG:  # the library says which argument
-            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
-        check(st)
+        self._check_text(st)
         return out, cnt
 
     def store_autocorr(self, store, max_lag, index=None, pooled=True, normalize=True):
@@ -1592,23 +1587,20 @@ class Engine:
         0 <= max_lag <= n_iter - 1, n_iter >= 2.  A column with a NaN or infinite draw gives NaN; a column that never moved
         an autocovariance of 0, NaN once normalised, tau NaN and window 0."""
         torch = _torch()
-        n_iter, size = self._store_shape(store)
+        n_iter, size, idx, n = self._selection(store, index)
         if n_iter < 2:
             raise ValueError("the autocorrelation needs at least 2 stored iterations")
         max_lag = int(max_lag)
         if not 0 <= max_lag <= n_iter - 1:
             raise ValueError(f"max_lag must lie in [0, n_iter - 1] = [0, {n_iter - 1}]")
-        idx, n = self._store_index(index, size)
         lead = () if pooled else (self.n_chains,)
         acf = self.empty(*lead, n, max_lag + 1)
         tau = self.empty(*lead, n)
-        window = torch.empty(lead + (n,), dtype=torch.int32, device=self.device)
+        window = self.empty(lead + (n,), dtype=torch.int32)
         mean = self.empty(self.n_chains, n)
         st = lib.omc_store_autocorr(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, max_lag, int(not pooled),
                                     int(bool(normalize)), self._p(acf), self._p(tau), window.data_ptr(), self._p(mean))
-        if st == _abi.INVALID_ARG:  # the library says which argument
-            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
-        check(st)
+        self._check_text(st)
         return acf, tau, window, mean
 
     def store_project(self, store, W, index=None, offset=None, base=None, omit_nan=True, prec=None, z=None, replicate=0, out=None):
@@ -1625,8 +1617,7 @@ class Engine:
         sum|terms|) of the exact value; repeated calls, and the same rows in a store of fewer iterations or chains, are
         bit-equal."""
         torch = _torch()
-        n_iter, size = self._store_shape(store)
-        idx, n = self._store_index(index, size)
+        n_iter, size, idx, n = self._selection(store, index)
         if (isinstance(W, torch.Tensor) and W.is_cuda and W.dtype is torch.float64 and W.dim() == 2 and W.shape[0] > 1
                 and W.stride(1) == 1 and W.stride(0) >= W.shape[1]):
             Wt = W  # rows of a wider device matrix are read where they lie (ld_w = the row stride)
@@ -1665,15 +1656,20 @@ class Engine:
         st = lib.omc_store_project(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, m, self._p(Wt), Wt.stride(0), self._p(off),
                                    self._p(base), int(bool(omit_nan)), self._p(prec), 0 if prec is None else prec.shape[2],
                                    self._p(z), replicate, self._p(out))
-        if st == _abi.INVALID_ARG:  # the library says which argument
-            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
-        check(st)
+        self._check_text(st)
         return out
+
+    def _loo_inputs(self, store, index, y, prec):
+        """_loglik_inputs of store_psis / store_loo_expect, where y and prec are both None for an entry of log-likelihoods"""
+        if (y is None) != (prec is None):
+            raise ValueError("y and prec must be given together")
+        if y is None:
+            return self._selection(store, index) + (None, None)
+        return self._loglik_inputs(store, y, prec, index)
 
     def _loglik_inputs(self, store, y, prec, index):
         """(n_iter, size, idx, n, y, prec) of the observation and precision arguments of store_loglik / store_psis"""
-        n_iter, size = self._store_shape(store)
-        idx, n = self._store_index(index, size)
+        n_iter, size, idx, n = self._selection(store, index)
         yv = self._reduce_vector(y.reshape(-1) if isinstance(y, _torch().Tensor) else np.asarray(y, dtype=np.float64).reshape(-1), n, "y")
         n_it, sz = self._store_shape(prec)
         if n_it != n_iter:
@@ -1697,9 +1693,7 @@ class Engine:
         ll_out = self.empty(n_iter, self.n_chains, n) if ll else None
         st = lib.omc_store_loglik(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, self._p(yv), self._p(prec), prec.shape[2],
                                   self._p(outs[0]), self._p(outs[1]), self._p(outs[2]), self._p(ll_out))
-        if st == _abi.INVALID_ARG:  # the library says which argument
-            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
-        check(st)
+        self._check_text(st)
         return outs[0], outs[1], outs[2], ll_out
 
     def store_psis(self, store, tail_max, index=None, y=None, prec=None):
@@ -1710,34 +1704,24 @@ class Engine:
         entry from which they are computed on load (the same bits).  tail_max: a number or one per selected element, each in
         1 .. n_iter * C - 1.  A column with an ll that is not finite gives NaN, NaN and -1."""
         torch = _torch()
-        if (y is None) != (prec is None):
-            raise ValueError("y and prec must be given together")
-        if y is None:
-            n_iter, size = self._store_shape(store)
-            idx, n = self._store_index(index, size)
-            yv = None
-        else:
-            n_iter, size, idx, n, yv, prec = self._loglik_inputs(store, y, prec, index)
+        n_iter, size, idx, n, yv, prec = self._loo_inputs(store, index, y, prec)
         tm = self._tail_max(tail_max, n)
         elpd, k = self.empty(n), self.empty(n)
-        tail = torch.empty(n, dtype=torch.int64, device=self.device)
+        tail = self.empty(n, dtype=torch.int64)
         st = lib.omc_store_psis(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, self._p(yv), self._p(prec),
                                 0 if prec is None else prec.shape[2], tm.data_ptr(), self._p(elpd), self._p(k), tail.data_ptr())
-        if st == _abi.INVALID_ARG:  # the library says which argument
-            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
-        check(st)
+        self._check_text(st)
         return elpd, k, tail
 
     def _tail_max(self, tail_max, n):
         """tail_max, a number or one per selected element, as a device int64 tensor (n,)"""
         torch = _torch()
-        tm = np.asarray(tail_max.cpu().numpy() if isinstance(tail_max, torch.Tensor) else tail_max)
-        if tm.size and tm.dtype.kind not in "iu":
-            raise ValueError("tail_max must hold integers")
-        tm = np.ascontiguousarray(np.broadcast_to(tm.reshape(-1), (n,)) if tm.size == 1 else tm.reshape(-1), dtype=np.int64)
-        if tm.shape != (n,):
+        tm = self._int64(tail_max.cpu().numpy() if isinstance(tail_max, torch.Tensor) else tail_max, "tail_max").reshape(-1)
+        if tm.numel() == 1:
+            tm = tm.expand(n)
+        if tm.shape[0] != n:
             raise ValueError(f"tail_max must be a number or hold one value per selected element ({n})")
-        return torch.tensor(tm, dtype=torch.int64, device=self.device)
+        return tm.contiguous()
 
     def store_loo_expect(self, store, tail_max, index=None, y=None, prec=None, f="entry", values=None, values_index=None,
                          threshold=None, want=("mean", "var", "ess", "k", "tail"), lw=False):
@@ -1763,14 +1747,7 @@ class Engine:
                 raise ValueError(f"unknown output {w!r}: one of {', '.join(names)}")
         if not want and not lw:
             raise ValueError("nothing asked for: want is empty and lw is False")
-        if (y is None) != (prec is None):
-            raise ValueError("y and prec must be given together")
-        if y is None:
-            n_iter, size = self._store_shape(store)
-            idx, n = self._store_index(index, size)
-            yv = None
-        else:
-            n_iter, size, idx, n, yv, prec = self._loglik_inputs(store, y, prec, index)
+        n_iter, size, idx, n, yv, prec = self._loo_inputs(store, index, y, prec)
         vidx, vsize = None, 0
         if f == "entry":
             if values is None:
@@ -1790,16 +1767,14 @@ class Engine:
             thr = self._reduce_vector(threshold.reshape(-1) if isinstance(threshold, torch.Tensor)
                                       else np.asarray(threshold, dtype=np.float64).reshape(-1), n, "threshold")
         tm = self._tail_max(tail_max, n)
-        out = {w: (torch.empty(n, dtype=torch.int64, device=self.device) if w == "tail" else self.empty(n)) for w in want}
+        out = {w: (self.empty(n, dtype=torch.int64) if w == "tail" else self.empty(n)) for w in want}
         if lw:
             out["lw"] = self.empty(n_iter, self.n_chains, n)
         p = {w: (out[w].data_ptr() if w in out else None) for w in names + ("lw",)}
         st = lib.omc_store_loo_expect(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, self._p(yv), self._p(prec),
                                       0 if prec is None else prec.shape[2], tm.data_ptr(), kinds[f], self._p(values), vsize, _ptr(vidx),
                                       self._p(thr), p["mean"], p["var"], p["below"], p["ess"], p["invprec"], p["k"], p["tail"], p["lw"])
-        if st == _abi.INVALID_ARG:  # the library says which argument
-            raise ValueError("libomcmc_hip: " + (lib.omc_last_error() or b"invalid argument").decode())
-        check(st)
+        self._check_text(st)
         return out
 
     def store_thin(self, store, every, first=0):
