@@ -53,29 +53,36 @@ def ms_per_sweep(tree, command):
     return float(re.search(r"([0-9.]+) ms per sweep", text).group(1))
 
 
-def main():
+def figures(tree, command):
+    """{name of a figure within the line ("" where it has one): ms} of one child"""
+    return {"": ms_per_sweep(tree, command)}
+
+
+def main(lines=LINES, figures=figures):
+    """The alternating rounds and the table; another set of lines (benchmarks/mh_host_ab.py) passes its own and how to read them."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--before", default="build/ab/parent")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     trees = {"before": os.path.join(ROOT, args.before), "after": ROOT}
-    ms = {(label, name): [] for label, _ in LINES for name in trees}
+    ms = {}
     try:
         for r in range(args.rounds):
-            for label, command in LINES:
+            for label, command in lines:
                 for name, tree in trees.items():
-                    ms[label, name].append(ms_per_sweep(tree, command))
-                    print(f"round {r + 1}: {label:34s} {name:6s} {ms[label, name][-1]:9.3f} ms per sweep", flush=True)
+                    for sub, value in figures(tree, command).items():
+                        ms.setdefault((label + sub, name), []).append(value)
+                        print(f"round {r + 1}: {label + sub:34s} {name:6s} {value:9.3f} ms per sweep", flush=True)
         headline = {name: run(tree, HEADLINE)[0] for name, tree in trees.items()}
-    except ChildFailed as e:
+    except (ChildFailed, subprocess.TimeoutExpired) as e:
         print(e)
         return 2
     rows = [f"before = {args.before}, after = the working tree, one library; ms per sweep, median [min, max] over {args.rounds} alternating rounds;",
             "bar: after's median <= before's median + before's spread (max - min)", "",
             f"{'line':34s} {'before':>28s} {'after':>28s} {'bar':>9s}  verdict"]
     missed = 0
-    for label, _ in LINES:
+    for label in dict.fromkeys(label for label, _ in ms):
         b, a = ms[label, "before"], ms[label, "after"]
         bar = statistics.median(b) + max(b) - min(b)
         ok = statistics.median(a) <= bar

@@ -131,7 +131,8 @@ def same(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
 
 
-def main():
+def main(child=child, script=os.path.abspath(__file__)):
+    """The driver and the comparison; another case table (benchmarks/mh_same_bits.py) passes its own `child` and file."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--before", default="build/ab/parent")
     ap.add_argument("--child")
@@ -144,7 +145,7 @@ def main():
         for name, tree in (("before", os.path.join(ROOT, args.before)), ("after", ROOT)):
             env = dict(os.environ, OMC_HIP_LIB=os.path.join(ROOT, "openmcmc_amd", "libomcmc_hip.so"))
             path = os.path.join(tmp, name + ".npz")
-            run = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path, "--tree", tree], env=env, timeout=900)
+            run = subprocess.run([sys.executable, script, "--child", path, "--tree", tree], env=env, timeout=900)
             if run.returncode != 0:
                 print(f"the child of the {name} tree ended with status {run.returncode}: nothing compared")
                 return 2
@@ -158,7 +159,7 @@ def main():
         ok = key in before and key in after and same(before[key], after[key])
         groups.setdefault(key.split("|")[0], []).append((key, ok))
     for name, found in sorted(groups.items()):
-        arrays = [ok for key, ok in found if "|store|" in key or "|state|" in key]
+        arrays = [ok for key, ok in found if not key.endswith(("|calls", "|raised"))]
         calls = [(key, ok) for key, ok in found if key.endswith("|calls")]
         raised = sorted({str(after[key]) for key, _ in found if key.endswith("|raised") and key in after})
         n_calls = sum(len(str(after[key]).split("\n")) for key, _ in calls if key in after and str(after[key]))

@@ -452,22 +452,23 @@ class Engine:
         """Drop what the library derived from the last (Q, L, step) of the fused Metropolis-Hastings routes."""
         check(lib.omc_mh_invalidate(self._ctx))
 
-    def mala_step(self, Q, mu, L, sumlogL, step, x, z=None, u=None, draw_index=0, accept_count=None,
-                  proposal_count=None):
+    def _step_args(self, d, step, z, u, draw_index, x):
+        """The arguments the four fused single steps share: step, z and its stride, u, the draw index, x and its stride."""
+        return (float(step), self._p(z, self.n_chains, d), 0 if z is None else z.stride(0), self._chain_scalar(u), int(draw_index),
+                self._p(x, self.n_chains, d), x.stride(0))
+
+    def mala_step(self, Q, mu, L, sumlogL, step, x, z=None, u=None, draw_index=0, accept_count=None, proposal_count=None):
         d = Q.shape[0]
-        check(lib.omc_mala_step(self._ctx, d, self._p(Q), self._vec(mu, d), self._p(L), self._p(sumlogL), float(step),
-                                self._p(z, self.n_chains, d), 0 if z is None else z.stride(0), self._chain_scalar(u),
-                                int(draw_index), self._p(x, self.n_chains, d), x.stride(0), self._ip(accept_count),
-                                self._ip(proposal_count)))
+        check(lib.omc_mala_step(self._ctx, d, self._p(Q), self._vec(mu, d), self._p(L), self._p(sumlogL),
+                                *self._step_args(d, step, z, u, draw_index, x), self._ip(accept_count), self._ip(proposal_count)))
 
     def mala_step_white(self, mu, L, sumlogL, step, x, state_is_current=False, z=None, u=None, draw_index=0, accept_count=None,
                         proposal_count=None, log_p_out=None):
         """omc_mala_step_white: the ManifoldMALA step for L = chol(Q / step^2) in whitened coordinates; log_p_out (C,) takes
         the target's log density at the state the step leaves behind."""
         d = L.shape[0]
-        check(lib.omc_mala_step_white(self._ctx, d, self._vec(mu, d), self._p(L), self._p(sumlogL), float(step),
-                                      self._p(z, self.n_chains, d), 0 if z is None else z.stride(0), self._chain_scalar(u),
-                                      int(draw_index), self._p(x, self.n_chains, d), x.stride(0), int(bool(state_is_current)),
+        check(lib.omc_mala_step_white(self._ctx, d, self._vec(mu, d), self._p(L), self._p(sumlogL),
+                                      *self._step_args(d, step, z, u, draw_index, x), int(bool(state_is_current)),
                                       self._ip(accept_count), self._ip(proposal_count), self._chain_scalar(log_p_out)))
 
     def mala_run_white(self, mu, L, sumlogL, step, x, n_steps, state_is_current=False, z=None, u=None, draw_index0=0, draw_stride=1,
@@ -490,21 +491,17 @@ class Engine:
                                      self._p(logp_store), self._ip(accept_count), self._ip(proposal_count),
                                      self._chain_scalar(log_p_out)))
 
-    def rw_step(self, mu, LQ, sumlogLQ, step, x, z=None, u=None, draw_index=0, accept_count=None,
-                proposal_count=None):
+    def rw_step(self, mu, LQ, sumlogLQ, step, x, z=None, u=None, draw_index=0, accept_count=None, proposal_count=None):
         d = LQ.shape[0]
-        check(lib.omc_rw_step(self._ctx, d, self._vec(mu, d), self._p(LQ), self._p(sumlogLQ), float(step),
-                              self._p(z, self.n_chains, d), 0 if z is None else z.stride(0), self._chain_scalar(u),
-                              int(draw_index), self._p(x, self.n_chains, d), x.stride(0), self._ip(accept_count),
-                              self._ip(proposal_count)))
+        check(lib.omc_rw_step(self._ctx, d, self._vec(mu, d), self._p(LQ), self._p(sumlogLQ),
+                              *self._step_args(d, step, z, u, draw_index, x), self._ip(accept_count), self._ip(proposal_count)))
 
     def rw_step_white(self, mu, LQ, sumlogLQ, step, x, state_is_current=False, z=None, u=None, draw_index=0,
                       accept_count=None, proposal_count=None, log_p_out=None):
         """omc_rw_step_white: the fused random-walk step with L_Q'(x - mu) carried from step to step."""
         d = LQ.shape[0]
-        check(lib.omc_rw_step_white(self._ctx, d, self._vec(mu, d), self._p(LQ), self._p(sumlogLQ), float(step),
-                                    self._p(z, self.n_chains, d), 0 if z is None else z.stride(0), self._chain_scalar(u),
-                                    int(draw_index), self._p(x, self.n_chains, d), x.stride(0), int(bool(state_is_current)),
+        check(lib.omc_rw_step_white(self._ctx, d, self._vec(mu, d), self._p(LQ), self._p(sumlogLQ),
+                                    *self._step_args(d, step, z, u, draw_index, x), int(bool(state_is_current)),
                                     self._ip(accept_count), self._ip(proposal_count), self._chain_scalar(log_p_out)))
 
     # ------------------------------------------------------------------ per-model constants

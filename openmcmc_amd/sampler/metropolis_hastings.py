@@ -1,25 +1,32 @@
 """Metropolis-Hastings samplers on chain-batched state (reference sampler/metropolis_hastings.py).
 
-Two routes:
-  * fused: RandomWalk (untruncated) and ManifoldMALA for a parameter whose conditional model is one Normal with
+Routes:
+  * fused Gaussian: RandomWalk (untruncated) and ManifoldMALA for a parameter whose conditional model is one Normal with
     the parameter as response, a shared mean and a shared dense precision (Normal("x", mean="mu", precision="Q")
-    -- BASELINE configs[3]).  The Hessian of that target is constant, so chol(H/step^2) is factorised once per
-    sampler instead of five times per update and every chain advances with level-3 BLAS
-    on the d x C state matrix (omc_mala_step / omc_rw_step).
+    -- BASELINE configs[3]).  The Hessian of that target is constant, so chol(H/step^2) is factorised once per sampler instead of
+    five times per update and every chain advances with level-3 BLAS on the d x C state matrix: in the whitened
+    coordinates a = L'(x - mu) (omc_rw_step_white, omc_mala_step_white, blocks of steps through omc_mala_run_white; one protocol
+    for the library's cached a, `_fused_gaussian_step`) or, ManifoldMALA(whitened=False), on the products of omc_mala_step.
   * generic: any model whose log_p the device can evaluate.  The proposal (omc_rw_propose: Gaussian or truncated
     Gaussian random walk), the model log-density of the current and the proposed state, the accept test
     (omc_mh_accept) and the per-chain merge of the two states (omc_chain_select) are separate launches over all
     chains; `state_update_function` callbacks receive and return chain-batched state.  This is the route of
     RandomWalkLoop over the knots of a basis and of ReversibleJump (BASELINE configs[4]).
+  * knot loop: RandomWalkLoop over the knots of a library basis as one launch (omc_knot_loop) when `_knot_plan` allows.
+  * ManifoldMALA beyond the Gaussian target, named by `ManifoldMALA.route(state)`: "diag" (a per-chain diagonal Hessian: omc_mala_diag
+    does both halves of the proposal), "transform" (a parameter under the exponential transform: the whole update in
+    omc_mala_transform_step), "dense" (a constant Hessian of shared matrices with per-chain scales) and "general" (a per-chain
+    (C, d, d) Hessian); the last two are one proposal skeleton (`_mmala_step`) over two precision objects.
 """
 
 from dataclasses import dataclass, field
+from functools import partial
 from typing import Callable
 
 import numpy as np
 
 from openmcmc_amd.chains import ChainArray, is_chain
-from openmcmc_amd.distribution.location_scale import Normal
+from openmcmc_amd.distribution.location_scale import Normal, NullDistribution
 from openmcmc_amd.parameter import Identity
 from openmcmc_amd.sampler.sampler import MCMCSampler
 
@@ -62,17 +69,35 @@ class MetropolisHastings(MCMCSampler):
     step: np.ndarray = field(default_factory=lambda: np.array([0.2], ndmin=2), init=True)
     accept_rate: AcceptRate = field(default_factory=lambda: AcceptRate(), init=False)
 
-    def __post_init__(self):
-        super().__post_init__()
+    def _init_runtime(self):
+        """(every `__post_init__` of the family comes here: RandomWalk and ReversibleJump skip the base's on purpose)"""
+        super()._init_runtime()
+        # empty caches: what the fused routes' factor was made from and where they leave log p; the members and the value of the generic
+        # route's last log-density; _transform_plan's (host objects, statistics made from them); proposal's device steps and limits
+        self._plan_key = self._log_p_buf = self._lp_members = self._lp_state = self._transform_memo = None
+        self._dev_consts = {}
         self.step = np.array(self.step, ndmin=2)
+        self._init_hooks()
+
+    def _init_hooks(self):
         self.inject_uniform = None  # test hook like `inject`, for the accept/reject uniforms
         self.trace = None  # test hook: a dict that receives the internals of the last proposal / decision
+
+    def _hook(self, name, *extra):
+        """The draws a test hook injects for this sweep (and column, ...), None when the hook is unset."""
+        hook = getattr(self, name)
+        return None if hook is None else hook(self, self._sweep, *extra)
 
     def bind(self, engine, position=0, n_samplers=1):
         super().bind(engine, position, n_samplers)
         self.accept_rate.attach(engine)
         self._white_tag, self._white_serial = None, 0  # a sampler object taken into another run starts without a cached state
         return self
+
+    def _blocks_per_proposal(self, p):
+        return (p + 1) // 2 + 1  # Philox blocks for p proposal draws, plus one for the accept uniform
+
+    _accept_block = _blocks_per_proposal  # ... which a whole-vector proposal takes from the block behind those
 
     def _white_state_tag(self, state, x, L, mu):
         """What the library's cached whitened state a = L'(x - mu) of the fused steps belongs to: this state entry (the object,
@@ -83,14 +108,24 @@ class MetropolisHastings(MCMCSampler):
 
     def _white_state_is_current(self, engine, x, tag):
         """... and as far as the library's own writes go, which torch's version counter does not see (Engine.note_write)."""
-        return getattr(self, "_white_tag", None) == tag and not engine.written_since(x, getattr(self, "_white_serial", 0))
+        return self._white_tag == tag and not engine.written_since(x, self._white_serial)
 
-    def _log_p_buffer(self, engine):
-        """(C,) device buffer the fused steps leave the target's log density in."""
-        buf = getattr(self, "_log_p_buf", None)
-        if buf is None or buf.shape[0] != engine.n_chains:
-            buf = self._log_p_buf = engine.empty(engine.n_chains)
-        return buf
+    def _fused_gaussian_step(self, state, entry, scale, **extras):
+        """One call of a fused whitened entry point of the engine (rw_step_white, mala_step_white, mala_run_white; `extras` are its own
+        arguments) with L = chol(scale * Q), and the whole protocol around it.  The step is element-wise in a = L'(x - mu); the library
+        keeps a for the x it wrote last and may reuse it if this is still that state entry, factor and mean (`_white_state_tag`) and
+        nobody else has written x since.  Leaves the target's log density at the state just left in x in `last_log_p` (MCMC.run_mcmc)."""
+        eng = self._need_engine()
+        Q, mu = self._target(state)
+        L, sl = self._factor_plan(eng, state, Q, scale)
+        x = self._x(state)
+        tag = self._white_state_tag(state, x, L, mu)
+        if self._log_p_buf is None or self._log_p_buf.shape[0] != eng.n_chains:
+            self._log_p_buf = eng.empty(eng.n_chains)
+        entry(mu, L, sl, float(self.step.item()), x, state_is_current=self._white_state_is_current(eng, x, tag),
+              accept_count=self.accept_rate.accept, proposal_count=self.accept_rate.proposal, log_p_out=self._log_p_buf, **extras)
+        self._white_tag, self._white_serial = tag, eng._write_serial
+        self.last_log_p = (self._log_p_buf, x)
 
     def _gaussian_target(self, state):
         """Does the fused route apply?  (one Normal with the parameter as response, shared mean and precision)"""
@@ -102,17 +137,13 @@ class MetropolisHastings(MCMCSampler):
         return not (is_chain(state[dist.precision.form]) or is_chain(state[dist.mean.form]))
 
     def _target(self, state):
-        """(Q device, mu device or None, d) of the Gaussian target of the fused route."""
+        """(Q device, mu device or None) of the Gaussian target of the fused route (the caller has asked `_gaussian_target`)."""
         eng = self._need_engine()
-        if not self._gaussian_target(state):
-            raise NotImplementedError("fused MH route needs Normal(param, mean=<shared>, precision=<shared matrix>) "
-                                      "and a scalar step")
         dist = self.model[self.param]
         Q, mu = state[dist.precision.form], state[dist.mean.form]
         # device copies are cached by the identity of the STATE ENTRY (a reshaped copy would be a new object every step:
         # one upload per step, and a new address for everything the library derives from the mean)
-        mu_dev = eng.shared(mu).reshape(-1) if np.any(mu) else None
-        return eng.shared(Q), mu_dev, Q.shape[0]
+        return eng.shared(Q), eng.shared(mu).reshape(-1) if np.any(mu) else None
 
     def _factor_plan(self, eng, state, Q, scale):
         """chol(scale * Q) of the fused routes, kept from step to step (the reference refactorises every step,
@@ -120,7 +151,7 @@ class MetropolisHastings(MCMCSampler):
         the state, or another step size.  The library keeps matrices derived from the factor (drift matrix, L^-T) keyed
         by device addresses; a rebuilt factor may land on a recycled address, so that cache is dropped as well."""
         key = (float(scale), id(state[self.model[self.param].precision.form]), int(Q.data_ptr()), int(Q._version))
-        if self._plan is None or getattr(self, "_plan_key", None) != key:
+        if self._plan is None or self._plan_key != key:
             eng.mh_invalidate()
             self._plan = eng.dense_cholesky(Q, scale)
             self._plan_key = key
@@ -147,7 +178,7 @@ class MetropolisHastings(MCMCSampler):
         # metropolis_hastings.py:150-155).  Proposals and callbacks must REPLACE state entries, never mutate them.
         changed = [k for k, v in prop_state.items() if v is not current_state.get(k)]
         members = self.model.affected_by(changed)
-        if lp_cur is None or getattr(self, "_lp_members", None) != members:
+        if lp_cur is None or self._lp_members != members:
             lp_cur = self.model.log_p(current_state, engine=eng, members=members)
         self._lp_members = members
         lp_prop = self.model.log_p(prop_state, engine=eng, members=members)
@@ -197,6 +228,68 @@ def _add_contribution(engine, total, extra):
     return total
 
 
+class _SharedPrecision:
+    """Lambda_c = (sum_k s_kc M_k + diag(d_c)) / step^2 for ManifoldMALA._mmala_step, from the shared matrices, per-chain scales and
+    per-chain diagonal of Model.grad_terms.  Constant in the parameter: one object serves both points of a step."""
+
+    def __init__(self, eng, terms, diag, s2, shape, draw_index):
+        Cn, p = shape
+        self.eng, self.shape, self.draw_index, self.logdet = eng, shape, draw_index, None
+        self.terms = [{"mat": None if t["mat"] is None else eng.shared(t["mat"]),
+                       "scale": eng.full((Cn,), 1.0 / s2) if t["scale"] is None else t["scale"] / s2} for t in terms]
+        if not self.terms:
+            self.terms.append({"mat": None, "scale": eng.zeros(Cn)})
+        self.diag = None if diag is None else diag / s2
+        self.T = eng.dense_terms(self.terms, p)
+
+    def times(self, v):  # Lambda_c v_c for every chain
+        out = None if self.diag is None else self.diag * v
+        for t in self.terms:
+            part = (v if t["mat"] is None else self.eng.design_predict(t["mat"], v.contiguous())) * t["scale"].unsqueeze(1)
+            out = part if out is None else out + part
+        return out
+
+    def quad(self, d):  # d_c' Lambda_c d_c
+        out = None if self.diag is None else (self.diag * d * d).sum(dim=1)
+        for t in self.terms:
+            q = (d * d).sum(dim=1) if t["mat"] is None else self.eng.dense_quadform(t["mat"], d.contiguous())
+            out = q * t["scale"] if out is None else out + q * t["scale"]
+        return out
+
+    def draw(self, b, z):
+        """(m + L^-T z, m = Lambda^-1 b) in one launch; the first draw takes the stream's index and leaves log det Lambda"""
+        eng, first = self.eng, self.logdet is None
+        out, mean, self.logdet = eng.empty(*self.shape), eng.empty(*self.shape), eng.empty(self.shape[0]) if first else self.logdet
+        eng.dense_sample_canonical(self.shape[1], self.T, out, z=z, rhs_chain=b, draw_index=self.draw_index if first else 0,
+                                   mean_out=mean, logdet_out=self.logdet if first else None, diag_chain=self.diag)
+        return out, mean
+
+
+class _ChainPrecision:
+    """Lambda_c as a (C, d, d) tensor for ManifoldMALA._mmala_step.  Up to one wave's 64 columns the library's small-matrix kernels
+    (one wave per chain); beyond, the same operations as batched dense factorisations (Engine.chain_spd_ops / chain_sample_canonical):
+    the reference has no size limit here (metropolis_hastings.py:325-348).  `logdet` comes with the product of `times` (one launch)."""
+
+    def __init__(self, eng, Lam, zero, draw_index):
+        self.eng, self.Lam, self.logdet = eng, Lam, None
+        if Lam.shape[1] <= 64:
+            self.ops, self.sample = eng.small_spd_ops, partial(eng.small_sample_canonical, prior_prec=zero, draw_index=draw_index)
+        else:
+            self.ops, self.sample = eng.chain_spd_ops, partial(eng.chain_sample_canonical, draw_index=draw_index)
+
+    def times(self, v):
+        Av, _, self.logdet = self.ops(self.Lam, v, want_Av=True, want_logdet=True)
+        return Av
+
+    def quad(self, d):
+        return self.ops(self.Lam, d, want_quad=True)[1]
+
+    def draw(self, b, z):
+        """(m + L^-T z, m = Lambda^-1 b) in one launch"""
+        mean = self.eng.empty(*b.shape)
+        return self.sample(self.Lam, b, z=z, mean_out=mean), mean
+
+
 @dataclass
 class RandomWalk(MetropolisHastings):
     """(Truncated) Gaussian random-walk proposal (metropolis_hastings.py:176-269).
@@ -212,12 +305,15 @@ class RandomWalk(MetropolisHastings):
         if self.state_update_function is None:
             self.model = self.model.conditional(self.param)
         self._init_runtime()
-        self.step = np.array(self.step, ndmin=2)
-        self.inject_uniform = None
-        self.trace = None  # test hook: a dict that receives the internals of the last proposal / decision
 
-    def _blocks_per_proposal(self, p):
-        return (p + 1) // 2 + 1  # Philox blocks for p proposal draws, plus one for the accept uniform
+    def _column(self, state, param_index):
+        """(column (0 for None: the whole vector), are the columns ragged, their live number per chain if so, proposal and accept blocks)"""
+        x = state[self.param]
+        p = x.shape[0]
+        col = 0 if param_index is None else int(param_index)
+        ragged_cols = x.ragged is not None and x.ragged[1] == 1
+        sub = col * self._blocks_per_proposal(p)
+        return col, ragged_cols, x.count(state) if ragged_cols else None, sub, sub + (p + 1) // 2
 
     def proposal(self, current_state: dict, param_index: int = None, inject=None):
         """metropolis_hastings.py:212-269 for every chain; returns (prop_state, logq_fwd (C,), logq_rev (C,))."""
@@ -233,9 +329,7 @@ class RandomWalk(MetropolisHastings):
             if param_index is None:
                 raise NotImplementedError("(p, n) step sizes without a column index")
             step = step[:, [param_index]]
-        cache = getattr(self, "_dev_consts", None)
-        if cache is None:
-            cache = self._dev_consts = {}
+        cache = self._dev_consts
         skey = ("step", 0 if self.step.shape[1] == 1 else param_index)
         if skey not in cache:
             cache[skey] = eng.to_device(np.ascontiguousarray(step.reshape(-1)))
@@ -245,53 +339,34 @@ class RandomWalk(MetropolisHastings):
                 raise ValueError("domain_limits must have one (lower, upper) row per element of the parameter")
             cache["lim"] = (eng.to_device(lim[:, 0].copy()), eng.to_device(lim[:, 1].copy()))
         lower, upper = cache.get("lim", (None, None))
-        col = 0 if param_index is None else int(param_index)
-        ragged_cols = x.ragged is not None and x.ragged[1] == 1
+        col, ragged_cols, count, sub, _ = self._column(current_state, param_index)
         data = x.data if x.data.is_contiguous() else x.data.contiguous()
         z = data.clone()
-        sub = col * self._blocks_per_proposal(p)
         lq_f, lq_r = eng.rw_propose(data, z, cache[skey], lower, upper, column=col if n_rep > 1 or ragged_cols else None,
-                                    count=x.count(current_state) if ragged_cols else None, inject=inject,
-                                    draw_index=self._draw_index(), sub=sub)
-        prop_state = dict(current_state)  # shallow: only the entries a proposal replaces are new objects
-        prop_state[self.param] = x.like(z)
+                                    count=count, inject=inject, draw_index=self._draw_index(), sub=sub)
+        prop_state = {**current_state, self.param: x.like(z)}  # shallow: only the entries a proposal replaces are new objects
         if callable(self.state_update_function):
             prop_state, f_extra, r_extra = self.state_update_function(prop_state, param_index)
             lq_f, lq_r = _add_contribution(eng, lq_f, f_extra), _add_contribution(eng, lq_r, r_extra)
         return prop_state, lq_f, lq_r
 
     def _generic_step(self, current_state, param_index=None, lp_cur=None):
-        x = current_state[self.param]
-        p = x.shape[0]
-        col = 0 if param_index is None else int(param_index)
-        inject = self.inject(self, self._sweep, param_index) if self.inject is not None else None
-        u = self.inject_uniform(self, self._sweep, param_index) if self.inject_uniform is not None else None
+        inject, u = self._hook("inject", param_index), self._hook("inject_uniform", param_index)
         prop_state, lq_f, lq_r = self.proposal(current_state, param_index, inject=inject)
-        ragged_cols = x.ragged is not None and x.ragged[1] == 1
+        col, _, count, _, sub_accept = self._column(current_state, param_index)
         trace = None
         if self.trace is not None:
             trace = {"z": prop_state[self.param].data.clone(), "lq_fwd": lq_f.clone(), "lq_rev": lq_r.clone()}
             self.trace.setdefault("steps", []).append(trace)
-        return self._accept_reject_proposal(current_state, prop_state, lq_f, lq_r,
-                                            count=x.count(current_state) if ragged_cols else None, index=col, u=u,
-                                            sub=col * self._blocks_per_proposal(p) + (p + 1) // 2, trace=trace,
-                                            lp_cur=lp_cur)
+        return self._accept_reject_proposal(current_state, prop_state, lq_f, lq_r, count=count, index=col, u=u, sub=sub_accept,
+                                            trace=trace, lp_cur=lp_cur)
 
     def sample(self, current_state: dict) -> dict:
         self.last_log_p = None  # set again by the fused whitened steps only
         eng = self._need_engine()
-        if self.domain_limits is None and self.state_update_function is None and self._gaussian_target(current_state):
-            Q, mu, d = self._target(current_state)
-            LQ, sl = self._factor_plan(eng, current_state, Q, 1.0)  # chol(Q) for log p (gmrf.py:339)
-            z = self.inject(self, self._sweep) if self.inject is not None else None
-            u = self.inject_uniform(self, self._sweep) if self.inject_uniform is not None else None
-            x = self._x(current_state)
-            tag = self._white_state_tag(current_state, x, LQ, mu)  # see ManifoldMALA.sample: may the library reuse its L_Q'(x - mu)?
-            eng.rw_step_white(mu, LQ, sl, float(self.step.item()), x, state_is_current=self._white_state_is_current(eng, x, tag),
-                              z=z, u=u, draw_index=self._draw_index(), accept_count=self.accept_rate.accept,
-                              proposal_count=self.accept_rate.proposal, log_p_out=self._log_p_buffer(eng))
-            self._white_tag, self._white_serial = tag, eng._write_serial
-            self.last_log_p = (self._log_p_buf, x)  # the target's log density at the state just left in x (see MCMC.run_mcmc)
+        if self.domain_limits is None and self.state_update_function is None and self._gaussian_target(current_state):  # (gmrf.py:339)
+            self._fused_gaussian_step(current_state, eng.rw_step_white, 1.0, z=self._hook("inject"), u=self._hook("inject_uniform"),
+                                      draw_index=self._draw_index())
         else:
             current_state = self._generic_step(current_state)
         self._sweep += 1
@@ -378,16 +453,15 @@ class RandomWalkLoop(RandomWalk):
     def _knot_loop(self, current_state, plan):
         eng = self.engine
         x, Bm = plan["x"], plan["B"]
-        kmax = x.shape[1]
         count = x.count(current_state)
         inj = {}
         if self.inject is not None or self.inject_uniform is not None:  # test hooks: one (C,) vector per column visited
             n_cols = int(count.max().item())
-            for name, hook in (("inject_z", self.inject), ("inject_u", self.inject_uniform)):
-                if hook is not None:
-                    rows = eng.zeros(kmax, eng.n_chains)
+            for name, hook in (("inject_z", "inject"), ("inject_u", "inject_uniform")):
+                if getattr(self, hook) is not None:
+                    rows = eng.zeros(x.shape[1], eng.n_chains)
                     for j in range(n_cols):
-                        rows[j] = hook(self, self._sweep, j).reshape(-1)
+                        rows[j] = self._hook(hook, j).reshape(-1)
                     inj[name] = rows
         eng.knot_loop(plan["basis"].X, plan["basis"].scale, plan["y"], Bm.data.transpose(1, 2), plan["coef"], x.data[:, 0, :],
                       count, float(self.step.item()), plan["lower"], plan["upper"], add_shared=plan["shared"],
@@ -404,16 +478,11 @@ class RandomWalkLoop(RandomWalk):
         plan = self._knot_plan(current_state) if self.fused else None
         if plan is not None:
             current_state = self._knot_loop(current_state, plan)
-            self._sweep += 1
-            return current_state
-        x = current_state[self.param]
-        n_cols = x.shape[1]
-        if x.ragged is not None and x.ragged[1] == 1:
-            n_cols = int(x.count(current_state).max().item())
-        lp = None  # log-density of the current state, carried from one column to the next
-        for param_index in range(n_cols):
-            current_state = self._generic_step(current_state, param_index, lp_cur=lp)
-            lp = self._lp_state
+        else:
+            _, ragged_cols, count, _, _ = self._column(current_state, 0)
+            self._lp_state = None  # log-density of the current state, carried from one column to the next
+            for param_index in range(int(count.max().item()) if ragged_cols else current_state[self.param].shape[1]):
+                current_state = self._generic_step(current_state, param_index, lp_cur=self._lp_state)
         self._sweep += 1
         return current_state
 
@@ -474,7 +543,7 @@ class ManifoldMALA(MetropolisHastings):
         # the host objects the statistics are made from: kept in the memo and compared with `is` (an id() alone can be reused)
         made_from = [A, resp, st_l.matrix, st_p.matrix] + [state[k] for k in mean.get_param_list() if k != self.param] \
             + [state[k] for k in prior.mean.get_param_list()]
-        memo = getattr(self, "_transform_memo", None)
+        memo = self._transform_memo
         if memo is None or len(memo[0]) != len(made_from) or any(a is not b for a, b in zip(memo[0], made_from)):
             eng = self._need_engine()
             dense = lambda M: M.toarray() if sparse.issparse(M) else np.asarray(M, dtype=np.float64)  # noqa: E731
@@ -501,8 +570,7 @@ class ManifoldMALA(MetropolisHastings):
         x = current_state[self.param]
         xv = x.vector()
         Cn, p = xv.shape
-        z = self.inject(self, self._sweep) if self.inject is not None else None
-        u = self.inject_uniform(self, self._sweep) if self.inject_uniform is not None else None
+        z, u = self._hook("inject"), self._hook("inject_uniform")
         prop = lq_f = lq_r = None
         if self.trace is not None:
             prop, lq_f, lq_r = eng.empty(Cn, p), eng.empty(Cn), eng.empty(Cn)
@@ -526,64 +594,47 @@ class ManifoldMALA(MetropolisHastings):
         step = float(self.step.item())
         count = x.count(current_state) if (x.ragged is not None and x.ragged[1] == 0) else None
         grad, h = self.model.grad_log_p_diag(current_state, self.param, eng)
-        z = self.inject(self, self._sweep) if self.inject is not None else None
-        xp, lq_f = eng.mala_diag(x.vector(), grad, h, step, count=count, z=z, draw_index=self._draw_index(), sub=0)
-        prop_state = dict(current_state)
-        prop_state[self.param] = x.like(xp.unsqueeze(2))
+        xp, lq_f = eng.mala_diag(x.vector(), grad, h, step, count=count, z=self._hook("inject"), draw_index=self._draw_index(), sub=0)
+        prop_state = {**current_state, self.param: x.like(xp.unsqueeze(2))}
         grad_p, h_p = self.model.grad_log_p_diag(prop_state, self.param, eng)
         lq_r = eng.mala_diag(xp, grad_p, h_p, step, count=count, x_other=x.vector().contiguous())
-        u = self.inject_uniform(self, self._sweep) if self.inject_uniform is not None else None
-        return self._accept_reject_proposal(current_state, prop_state, lq_f, lq_r, u=u, sub=(x.shape[0] + 1) // 2 + 1)
+        return self._accept_reject_proposal(current_state, prop_state, lq_f, lq_r, u=self._hook("inject_uniform"),
+                                            sub=self._accept_block(x.shape[0]))
 
     def _dense_step(self, current_state: dict) -> dict:
         """Generic route for a Hessian that is a per-chain combination of shared matrices (+ a per-chain diagonal):
-        regression coefficients under a Gaussian or a mixture prior.  Lambda_c = H_c / step^2 is factorised per chain by
-        the dense route (omc_dense_sample_canonical with b = Lambda x + g/2 gives x' = m + L^-T z and m at once, again
-        with z = 0 for the reverse mean); log q = (1/2) log det Lambda - (1/2)(. - m)' Lambda (. - m)
-        (metropolis_hastings.py:301-373), the quadratic forms term by term as GEMMs."""
+        regression coefficients under a Gaussian or a mixture prior (`_mmala_step` over `_SharedPrecision`)."""
+        eng, s2 = self.engine, float(self.step.item()) ** 2
+
+        def point(state, zero, forward):  # (the Hessian does not depend on the parameter: the proposed point keeps the forward object)
+            grad, terms, diag = self.model.grad_terms(state, self.param, eng)
+            return grad, forward or _SharedPrecision(eng, terms, diag, s2, zero.shape, self._draw_index())
+        return self._mmala_step(current_state, point)
+
+    def _mmala_step(self, current_state, point, trace=False):
+        """The proposal of metropolis_hastings.py:301-373 and its accept test over Lambda_c = H_c / step^2 as an object (`_SharedPrecision`,
+        `_ChainPrecision`): from x, b = Lambda x + g/2, x' = m + L^-T z with m = Lambda^-1 b, log q(x'|x) = (1/2) log det Lambda
+        - (1/2)(x' - m)' Lambda (x' - m); the same from x' with z = 0 for log q(x|x').  `point(state, zero, forward)` -> (gradient
+        (C, d), precision) at a state; `forward` is None at x and the precision found there at x'."""
         eng = self.engine
         x = current_state[self.param]
         xv = x.vector().contiguous()
-        Cn, p = xv.shape
-        s2 = float(self.step.item()) ** 2
-        grad, terms, diag = self.model.grad_terms(current_state, self.param, eng)
-        dterms = []
-        for t in terms:
-            sc = eng.full((Cn,), 1.0 / s2) if t["scale"] is None else t["scale"] / s2
-            dterms.append({"mat": None if t["mat"] is None else eng.shared(t["mat"]), "scale": sc})
-        if not dterms:
-            dterms.append({"mat": None, "scale": eng.zeros(Cn)})
-        dscaled = None if diag is None else diag / s2
-        T = eng.dense_terms(dterms, p)
+        zero = eng.zeros(*xv.shape)
 
-        def lam_times(v):   # Lambda_c v_c for every chain
-            out = None if dscaled is None else dscaled * v
-            for t in dterms:
-                part = (v if t["mat"] is None else eng.design_predict(t["mat"], v.contiguous())) * t["scale"].unsqueeze(1)
-                out = part if out is None else out + part
-            return out
+        def log_q(prec, start, grad, z, end=None):  # (the point drawn from `start` with noise z, log q(end or that point | start))
+            drawn, mean = prec.draw(_lin(eng, 1.0, prec.times(start), 0.5, grad), z)
+            dev = _lin(eng, 1.0, drawn if end is None else end, -1.0, mean)
+            return drawn, _lin(eng, 0.5, prec.logdet, -0.5, prec.quad(dev))
 
-        def lam_quad(d):    # d_c' Lambda_c d_c
-            out = None if dscaled is None else (dscaled * d * d).sum(dim=1)
-            for t in dterms:
-                q = (d * d).sum(dim=1) if t["mat"] is None else eng.dense_quadform(t["mat"], d.contiguous())
-                out = q * t["scale"] if out is None else out + q * t["scale"]
-            return out
-
-        z = self.inject(self, self._sweep) if self.inject is not None else None
-        xp, mu, logdet = eng.empty(Cn, p), eng.empty(Cn, p), eng.empty(Cn)
-        eng.dense_sample_canonical(p, T, xp, z=z, rhs_chain=_lin(eng, 1.0, lam_times(xv), 0.5, grad), draw_index=self._draw_index(),
-                                   mean_out=mu, logdet_out=logdet, diag_chain=dscaled)
-        lq_f = _lin(eng, 0.5, logdet, -0.5, lam_quad(_lin(eng, 1.0, xp, -1.0, mu)))
-        prop_state = dict(current_state)
-        prop_state[self.param] = x.like(xp.unsqueeze(2))
-        grad_p, _, _ = self.model.grad_terms(prop_state, self.param, eng)   # the Hessian does not depend on the parameter
-        mu_p, scratch = eng.empty(Cn, p), eng.empty(Cn, p)
-        eng.dense_sample_canonical(p, T, scratch, z=eng.zeros(Cn, p), rhs_chain=_lin(eng, 1.0, lam_times(xp), 0.5, grad_p),
-                                   mean_out=mu_p, diag_chain=dscaled)
-        lq_r = _lin(eng, 0.5, logdet, -0.5, lam_quad(_lin(eng, 1.0, xv, -1.0, mu_p)))
-        u = self.inject_uniform(self, self._sweep) if self.inject_uniform is not None else None
-        return self._accept_reject_proposal(current_state, prop_state, lq_f, lq_r, u=u, sub=(p + 1) // 2 + 1)
+        grad, prec = point(current_state, zero, None)
+        xp, lq_f = log_q(prec, xv, grad, self._hook("inject"))
+        prop_state = {**current_state, self.param: x.like(xp.unsqueeze(2))}
+        grad_p, prec_p = point(prop_state, zero, prec)
+        _, lq_r = log_q(prec_p, xp, grad_p, zero, end=xv)
+        if trace and self.trace is not None:
+            self.trace.setdefault("steps", []).append({"prop": xp.clone(), "lq_fwd": lq_f.clone(), "lq_rev": lq_r.clone()})
+        return self._accept_reject_proposal(current_state, prop_state, lq_f, lq_r, u=self._hook("inject_uniform"),
+                                            sub=self._accept_block(xv.shape[1]))
 
     def _grad_hess_per_chain(self, state):
         """(grad (C, d), H (C, d, d)) of the whole model w.r.t. the parameter, for every chain, whatever each member
@@ -618,51 +669,16 @@ class ManifoldMALA(MetropolisHastings):
     def _general_step(self, current_state: dict) -> dict:
         """Any model whose device log_p exists, for a fixed-size parameter: gradient and Hessian of every
         member as the reference's generic path computes them (analytic where a distribution has one, central differences
-        otherwise, distribution.py:90-198), a per-chain Lambda_c = H_c / step^2 factorised per chain in natural order
-        (omc_small_sample_canonical: x' = m + L^-T z and m at once; again with z = 0 at the proposed state for the reverse
-        mean), log q = (1/2) log det Lambda - (1/2)(. - m)' Lambda (. - m) (metropolis_hastings.py:301-373)."""
-        eng = self.engine
+        otherwise, distribution.py:90-198), Lambda_c = H_c / step^2 factorised per chain (`_mmala_step` over `_ChainPrecision`)."""
         x = current_state[self.param]
         if x.ragged is not None or x.shape[1] != 1:
             raise NotImplementedError("generic ManifoldMALA route: fixed-size (d, 1) parameter")
-        xv = x.vector().contiguous()
-        Cn, d = xv.shape
-        s2 = float(self.step.item()) ** 2
-        zero = eng.zeros(Cn, d)
-        # up to one wave's 64 columns the library's small-matrix kernels (one wave per chain); beyond, the same operations as
-        # batched dense factorisations (Engine.chain_spd_ops / chain_sample_canonical): the reference has no size limit here
-        # (metropolis_hastings.py:325-348)
-        if d <= 64:
-            spd_ops = eng.small_spd_ops
+        eng, s2 = self.engine, float(self.step.item()) ** 2
 
-            def draw(Lam_, b_, z_, mean_out):
-                return eng.small_sample_canonical(Lam_, b_, zero, z=z_, draw_index=self._draw_index(), mean_out=mean_out)
-        else:
-            spd_ops = eng.chain_spd_ops
-
-            def draw(Lam_, b_, z_, mean_out):
-                return eng.chain_sample_canonical(Lam_, b_, z=z_, draw_index=self._draw_index(), mean_out=mean_out)
-        grad, H = self._grad_hess_per_chain(current_state)
-        Lam = H / s2
-        Lx, _, logdet_f = spd_ops(Lam, xv, want_Av=True, want_logdet=True)
-        z = self.inject(self, self._sweep) if self.inject is not None else None
-        mu_f = eng.empty(Cn, d)
-        xp = draw(Lam, _lin(eng, 1.0, Lx, 0.5, grad), z, mu_f)
-        _, quad_f, _ = spd_ops(Lam, _lin(eng, 1.0, xp, -1.0, mu_f), want_quad=True)
-        lq_f = _lin(eng, 0.5, logdet_f, -0.5, quad_f)
-        prop_state = dict(current_state)
-        prop_state[self.param] = x.like(xp.unsqueeze(2))
-        grad_p, H_p = self._grad_hess_per_chain(prop_state)
-        Lam_p = H_p / s2
-        Lxp, _, logdet_r = spd_ops(Lam_p, xp, want_Av=True, want_logdet=True)
-        mu_r = eng.empty(Cn, d)
-        draw(Lam_p, _lin(eng, 1.0, Lxp, 0.5, grad_p), zero, mu_r)
-        _, quad_r, _ = spd_ops(Lam_p, _lin(eng, 1.0, xv, -1.0, mu_r), want_quad=True)
-        lq_r = _lin(eng, 0.5, logdet_r, -0.5, quad_r)
-        if self.trace is not None:
-            self.trace.setdefault("steps", []).append({"prop": xp.clone(), "lq_fwd": lq_f.clone(), "lq_rev": lq_r.clone()})
-        u = self.inject_uniform(self, self._sweep) if self.inject_uniform is not None else None
-        return self._accept_reject_proposal(current_state, prop_state, lq_f, lq_r, u=u, sub=(d + 1) // 2 + 1)
+        def point(state, zero, forward):  # (the Hessian moves with the state: evaluated and factorised again at the proposed point)
+            grad, H = self._grad_hess_per_chain(state)
+            return grad, _ChainPrecision(eng, H / s2, zero, self._draw_index())
+        return self._mmala_step(current_state, point, trace=True)
 
     def can_run_block(self, state) -> bool:
         """May MCMC.run_mcmc hand this sampler whole blocks of iterations (omc_mala_run_white)?  The fused whitened route, no
@@ -674,58 +690,48 @@ class ManifoldMALA(MetropolisHastings):
         """n_steps calls of `sample` as one library call: blocks of 32 steps per launch, the state of every step into
         x_store (n_steps, C, d) and the target's log density there into logp_store (n_steps, C) when given (what
         sampler.store and mcmc.py:108 keep per iteration).  Same streams, same decisions, same states as the single steps."""
-        eng = self._need_engine()
-        Q, mu, d = self._target(current_state)
-        step = float(self.step.item())
-        L, sl = self._factor_plan(eng, current_state, Q, 1.0 / step**2)
-        x = self._x(current_state)
-        tag = self._white_state_tag(current_state, x, L, mu)
-        eng.mala_run_white(mu, L, sl, step, x, int(n_steps), state_is_current=self._white_state_is_current(eng, x, tag),
-                           draw_index0=self._draw_index(), draw_stride=self._n_samplers, x_store=x_store, logp_store=logp_store,
-                           accept_count=self.accept_rate.accept, proposal_count=self.accept_rate.proposal,
-                           log_p_out=self._log_p_buffer(eng))
-        self._white_tag, self._white_serial = tag, eng._write_serial
-        self.last_log_p = (self._log_p_buf, x)
+        if not self._gaussian_target(current_state):
+            raise NotImplementedError("fused MH route needs Normal(param, mean=<shared>, precision=<shared matrix>) and a scalar step")
+        self._fused_gaussian_step(current_state, self._need_engine().mala_run_white, 1.0 / float(self.step.item()) ** 2,
+                                  n_steps=int(n_steps), draw_index0=self._draw_index(), draw_stride=self._n_samplers, x_store=x_store,
+                                  logp_store=logp_store)
         self._sweep += int(n_steps)
         return current_state
+
+    def _route(self, state):
+        """(the route `sample` takes in this state, the plan of the "transform" route or None)"""
+        if self._gaussian_target(state):
+            return ("white" if self.whitened else "products"), None
+        # a per-chain diagonal Hessian: a variable-size parameter, or nothing but the parameter's own mixture prior and null distributions
+        if state[self.param].ragged is not None or all((getattr(d, "is_mixture", False) and k == self.param)
+                                                       or isinstance(d, NullDistribution) for k, d in self.model.items()):
+            return "diag", None
+        plan = self._transform_plan(state)
+        if plan is not None:
+            return "transform", plan
+        structured = all(hasattr(d, "grad_terms") and d.constant_hessian(self.param)
+                         for d in self.model.values() if self.param in d.param_list)
+        return ("dense" if structured else "general"), None  # a constant Hessian of shared matrices, or one per chain and point
+
+    def route(self, state) -> str:
+        """Which of "white", "products", "diag", "transform", "dense", "general" does `sample` take in this state?"""
+        return self._route(state)[0]
 
     def sample(self, current_state: dict) -> dict:
         self.last_log_p = None  # set again by the fused whitened steps only
         eng = self._need_engine()
-        if not self._gaussian_target(current_state):
-            x = current_state[self.param]
-            diag_only = x.ragged is not None or all(
-                getattr(d, "is_mixture", False) and k == self.param or type(d).__name__ == "NullDistribution"
-                for k, d in self.model.items())
-            plan = None if diag_only else self._transform_plan(current_state)
-            if diag_only:
-                current_state = self._diag_step(current_state)
-            elif plan is not None:
-                current_state = self._transform_step(current_state, plan)
-            else:
-                structured = all(hasattr(d, "grad_terms") and d.constant_hessian(self.param)
-                                 for d in self.model.values() if self.param in d.param_list)
-                current_state = self._dense_step(current_state) if structured else self._general_step(current_state)
-            self._sweep += 1
-            return current_state
-        Q, mu, d = self._target(current_state)
+        route, plan = self._route(current_state)
         step = float(self.step.item())
-        L, sl = self._factor_plan(eng, current_state, Q, 1.0 / step**2)  # chol(H/step^2), H = Q (metropolis_hastings.py:345-346)
-        z = self.inject(self, self._sweep) if self.inject is not None else None
-        u = self.inject_uniform(self, self._sweep) if self.inject_uniform is not None else None
-        x = self._x(current_state)
-        if self.whitened:
-            # L = chol(Q / step^2): the step is element-wise in a = L'(x - mu) (omc_mala_step_white).  The library keeps a
-            # for the x it wrote last; it may be reused if nobody else has written x since (torch's version counter sees
-            # every write but the library's own).
-            tag = self._white_state_tag(current_state, x, L, mu)
-            eng.mala_step_white(mu, L, sl, step, x, state_is_current=self._white_state_is_current(eng, x, tag), z=z, u=u,
-                                draw_index=self._draw_index(), accept_count=self.accept_rate.accept,
-                                proposal_count=self.accept_rate.proposal, log_p_out=self._log_p_buffer(eng))
-            self._white_tag, self._white_serial = tag, eng._write_serial
-            self.last_log_p = (self._log_p_buf, x)  # the target's log density at the state just left in x (see MCMC.run_mcmc)
+        if route == "white":  # L = chol(H/step^2), H = Q (metropolis_hastings.py:345-346)
+            self._fused_gaussian_step(current_state, eng.mala_step_white, 1.0 / step**2, z=self._hook("inject"),
+                                      u=self._hook("inject_uniform"), draw_index=self._draw_index())
+        elif route == "products":
+            Q, mu = self._target(current_state)
+            L, sl = self._factor_plan(eng, current_state, Q, 1.0 / step**2)
+            eng.mala_step(Q, mu, L, sl, step, self._x(current_state), z=self._hook("inject"), u=self._hook("inject_uniform"),
+                          draw_index=self._draw_index(), accept_count=self.accept_rate.accept, proposal_count=self.accept_rate.proposal)
         else:
-            eng.mala_step(Q, mu, L, sl, step, x, z=z, u=u, draw_index=self._draw_index(),
-                          accept_count=self.accept_rate.accept, proposal_count=self.accept_rate.proposal)
+            current_state = {"diag": self._diag_step, "transform": partial(self._transform_step, plan=plan), "dense": self._dense_step,
+                             "general": self._general_step}[route](current_state)
         self._sweep += 1
         return current_state

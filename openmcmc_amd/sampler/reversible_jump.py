@@ -23,14 +23,13 @@ valid without a callback when they are all-zero: the padding already holds zeros
 from dataclasses import dataclass
 from typing import Callable, Union
 
-import numpy as np
-
 from openmcmc_amd.chains import ChainArray, is_chain
 from openmcmc_amd.distribution.distribution import Gamma, Uniform
 from openmcmc_amd.distribution.location_scale import Normal
 from openmcmc_amd.sampler.metropolis_hastings import MetropolisHastings, _add_contribution
 
-# Philox sub-streams within one ReversibleJump.sample call (block numbers; omc_rj_move owns 0..63)
+# Philox sub-streams within one ReversibleJump.sample call (block numbers; omc_rj_move owns 0..63).  The accept uniform sits behind
+# this layout's last block, not at MetropolisHastings._accept_block of a vector length: no p gives 97 a meaning here.
 _SUB_ASSOCIATED, _SUB_MATCH, _SUB_ACCEPT = 64, 96, 97
 
 
@@ -49,17 +48,17 @@ class ReversibleJump(MetropolisHastings):
     def __post_init__(self):
         # reversible_jump.py:66-74: the WHOLE model stays attached
         self._init_runtime()
-        self.step = np.array(self.step, ndmin=2)
-        self.inject_uniform = None
-        self.trace = None
-        # test hooks: callables (sampler, sweep) -> device tensors replaying the reference's draws
-        self.inject_move = None       # (u (C,), deletion index int64 (C,))
-        self.inject_associated = None  # {key: uniforms (C, p)}
-        self.inject_match = None      # (C,) uniform (limits) or normal draw of the matched coefficient
         if isinstance(self.associated_params, str):
             self.associated_params = [self.associated_params]
         if self.associated_params is None:
             self.associated_params = []
+
+    def _init_hooks(self):
+        super()._init_hooks()
+        # test hooks: callables (sampler, sweep) -> device tensors replaying the reference's draws
+        self.inject_move = None       # (u (C,), deletion index int64 (C,))
+        self.inject_associated = None  # {key: uniforms (C, p)}
+        self.inject_match = None      # (C,) uniform (limits) or normal draw of the matched coefficient
 
     # ------------------------------------------------------------------ proposal
     def proposal(self, current_state: dict, param_index: int = None):
@@ -68,8 +67,8 @@ class ReversibleJump(MetropolisHastings):
         if not is_chain(n_cur) or n_cur.size != 1:
             raise NotImplementedError("the jump parameter must be a per-chain (1, 1) count")
         count = n_cur.scalar()
-        di, t = self._draw_index(), self._sweep
-        u_move, idx = self.inject_move(self, t) if self.inject_move is not None else (None, None)
+        di = self._draw_index()
+        u_move, idx = self._hook("inject_move") or (None, None)
         # log_p(current_state, by_observation=True)[-1] of every associated parameter (:132, :143): the density of the
         # LAST element of the CURRENT value -- a constant for a Uniform prior, a per-chain number for a Gamma one
         dens_const, dens_chain = 0.0, None
@@ -93,19 +92,17 @@ class ReversibleJump(MetropolisHastings):
         prop_state = dict(current_state)
         prop_state[self.param] = ChainArray(count_prop.reshape(-1, 1, 1))
         prop_state["__rj_move__"] = {"birth": birth, "deletion_index": del_index}
-        inj_assoc = self.inject_associated(self, t) if self.inject_associated is not None else {}
+        inj_assoc = self._hook("inject_associated") or {}
         for j, key in enumerate(self.associated_params):
             dist, cur = self.model[key], current_state[key]
             new = dist.rvs(current_state, n=1, engine=eng, draw_index=di, sub=_SUB_ASSOCIATED + 2 * j,
                            inject=inj_assoc.get(key))  # reversible_jump.py:130
             prop_state[key] = cur.like(eng.ragged_resize(cur.data, count, birth, del_index, axis=cur.ragged[1],
                                                          new_vals=new.data.reshape(eng.n_chains, -1)))
-        if callable(self.state_birth_function):
-            prop_state, f_extra, r_extra = self.state_birth_function(current_state, prop_state)
-            lq_f, lq_r = _add_contribution(eng, lq_f, f_extra), _add_contribution(eng, lq_r, r_extra)
-        if callable(self.state_death_function):
-            prop_state, f_extra, r_extra = self.state_death_function(current_state, prop_state, del_index)
-            lq_f, lq_r = _add_contribution(eng, lq_f, f_extra), _add_contribution(eng, lq_r, r_extra)
+        for callback, more in ((self.state_birth_function, ()), (self.state_death_function, (del_index,))):
+            if callable(callback):
+                prop_state, f_extra, r_extra = callback(current_state, prop_state, *more)
+                lq_f, lq_r = _add_contribution(eng, lq_f, f_extra), _add_contribution(eng, lq_r, r_extra)
         if self.matching_params is not None:
             prop_state = self._matched_transition(current_state, prop_state, count, birth, del_index, lq_f, lq_r)
         del prop_state["__rj_move__"]
@@ -130,17 +127,15 @@ class ReversibleJump(MetropolisHastings):
             raise NotImplementedError("matched transitions need per-chain coefficient vector and basis matrices")
         # X'X of the larger basis only: the proposed one where a chain makes a birth, the current one for a death
         gram = eng.design_gram_select(B_cur.columns(), B_cur.count(current_state), B_prop.columns(), B_prop.count(prop_state), birth)
-        inject = self.inject_match(self, self._sweep) if self.inject_match is not None else None
         out = eng.rj_matched_transition(gram, gram, count, birth, del_index, coef.vector(), scale, limits, lq_f, lq_r,
-                                        inject=inject, draw_index=self._draw_index(), sub=_SUB_MATCH)
+                                        inject=self._hook("inject_match"), draw_index=self._draw_index(), sub=_SUB_MATCH)
         prop_state[vector] = coef.like(out.unsqueeze(2))
         return prop_state
 
     # ------------------------------------------------------------------ sample
     def sample(self, current_state: dict) -> dict:
         prop_state, lq_f, lq_r = self.proposal(current_state)
-        u = self.inject_uniform(self, self._sweep) if self.inject_uniform is not None else None
-        current_state = self._accept_reject_proposal(current_state, prop_state, lq_f, lq_r, u=u, sub=_SUB_ACCEPT,
-                                                     trace=self.trace)
+        current_state = self._accept_reject_proposal(current_state, prop_state, lq_f, lq_r, u=self._hook("inject_uniform"),
+                                                     sub=_SUB_ACCEPT, trace=self.trace)
         self._sweep += 1
         return current_state

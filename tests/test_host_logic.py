@@ -252,6 +252,39 @@ def test_null_distribution_and_band_recognition():
         band_storage(sparse.csc_matrix(np.triu(np.ones((8, 8)), 0) * (np.abs(np.subtract.outer(np.arange(8), np.arange(8))) <= 2)), 8)
 
 
+def test_manifold_mala_route_names_the_route_sample_takes():
+    """ManifoldMALA.route on one hand-built state per route: numpy arrays and ChainArrays over CPU tensors, no engine ("transform"
+    uploads its statistics: tests/test_transform_gpu.py asserts it)."""
+    import torch
+
+    from openmcmc_amd.chains import ChainArray, ragged_from_lists
+    from openmcmc_amd.distribution.location_scale import NullDistribution
+    from openmcmc_amd.parameter import LinearCombinationWithTransform, MixtureParameterMatrix, MixtureParameterVector
+    from openmcmc_amd.sampler.metropolis_hastings import ManifoldMALA
+
+    C, p = 3, 4
+    fixed = ChainArray(torch.zeros(C, p, 1, dtype=torch.float64))
+    ragged = ragged_from_lists([[1.0], [2.0, 3.0], [4.0]], p, 0, "k", torch.device("cpu"))
+    gauss = Model([Normal("beta", mean="m0", precision="P0")])
+    state = {"beta": fixed, "m0": np.zeros((p, 1)), "P0": np.eye(p), "B": np.ones((6, p)), "y": np.ones((6, 1)), "P": sparse.identity(6).tocsc(),
+             "tau": ChainArray(torch.ones(C, 1, 1, dtype=torch.float64)), "k": ChainArray(torch.tensor([1.0, 2.0, 1.0]).reshape(C, 1, 1)),
+             "mu": np.zeros((2, 1)), "lam": np.ones((2, 1)), "alloc": np.zeros((p, 1), dtype=int)}
+    assert ManifoldMALA("beta", gauss).route(state) == "white"
+    assert ManifoldMALA("beta", gauss, whitened=False).route(state) == "products"
+    lik = dict(mean=LinearCombination({"beta": "B"}), precision=ScaledMatrix("P", "tau"))
+    mixture_prior = Normal("beta", mean=MixtureParameterVector("mu", "alloc"), precision=MixtureParameterMatrix("lam", "alloc"))
+    regression = Model([Normal("y", **lik), Normal("beta", mean="m0", precision="P0")])
+    # "diag": a ragged parameter whatever the model; the parameter's own mixture prior under nothing but null distributions
+    assert ManifoldMALA("beta", regression).route({**state, "beta": ragged}) == "diag"
+    assert ManifoldMALA("beta", Model([NullDistribution("y", **lik), mixture_prior])).route(state) == "diag"
+    # ... and not a model with a likelihood that does depend on the parameter, nor a null likelihood under a plain prior
+    assert ManifoldMALA("beta", regression).route(state) == "dense"
+    assert ManifoldMALA("beta", Model([Normal("y", **lik), mixture_prior])).route(state) == "dense"
+    assert ManifoldMALA("beta", Model([NullDistribution("y", **lik), Normal("beta", mean="m0", precision="P0")])).route(state) == "dense"
+    moving = Normal("y", mean=LinearCombinationWithTransform(form={"beta": "B"}, transform={"beta": True}), precision=ScaledMatrix("P", "tau"))
+    assert ManifoldMALA("beta", Model([moving, Normal("beta", mean="m0", precision="P0")]), fused=False).route(state) == "general"
+
+
 @pytest.mark.parametrize("shape", [1e-3, 0.5, 1.0, 2.0, 1e6])
 def test_gamma_log_p_by_observation_at_zero_matches_scipy(shape):
     """The torch branch of Gamma.log_p (per-replicate densities of a per-chain response, run here on CPU tensors): at x = 0

@@ -185,6 +185,7 @@ def test_chain_replays_the_reference(golden, tag, fused):
     smp, state = _mala_setup(G, tag, eng, C, fused)
     took = []
     if fused:
+        assert smp.route(state) == "transform"
         inner = smp._transform_step
         smp._transform_step = lambda *a, **k: (took.append(1), inner(*a, **k))[1]
     else:
