@@ -984,6 +984,50 @@ omc_status omc_store_histogram2d(omc_ctx* ctx, int64_t n_iter, int64_t size_x, c
  * form), byte offsets of the x edges, the y edges, the counters, the occupancy counters and the outside counts, end of the
  * image = bytes launched, the budget the tile was chosen for, threads of a workgroup}.                                  */
 omc_status omc_store_histogram2d_layout(int32_t nx, int32_t ny, int32_t edges_per_pair, int32_t pool_pairs, int32_t* out);
+/* Co-allocation (posterior similarity, co-clustering) matrix of the allocation vectors in the same store -- the labels 0 .. K - 1
+ * that MixtureAllocation draws, stored as fp64: (Z[:, :, None] == Z[:, None, :]).sum(0) of the gathered labels Z [rows][n_idx] of
+ * the reference's host arrays MCMC.store[param] (mcmc.py:105-111).  Invariant to label switching, which the mean or a quantile of
+ * a label is not.  Contract common to omc_store_coalloc and omc_store_partition_score:
+ *   store   [n_iter][C][size] (device), seen as omc_store_cov sees it; idx [n_idx] (device) the elements that take part, in that
+ *           order, repeats allowed; NULL = all of them (n_idx must then equal size).  An index outside [0, size) is
+ *           OMC_INVALID_ARG, found on the device before anything is written (the host reads one word back);
+ *   pooled != 0: one batch of R = n_iter C rows; pooled == 0: C batches, chain c over its own R = n_iter rows;
+ *   1 <= n_labels <= 64: more is OMC_UNSUPPORTED, less OMC_INVALID_ARG;
+ *   the label rule: a draw v carries label k iff v == k for an integer 0 <= k < n_labels; -0.0 is label 0.  NaN is "element
+ *           absent" (the padding of variable-size parameters); any other value (fractional, negative, >= n_labels, +-inf) is "not
+ *           a label".  An absent or non-label draw matches nothing, not even itself -- numpy's NaN == NaN is False, extended to
+ *           the non-labels;
+ *   every output is overwritten; nothing is written on an error status, whose cause omc_last_error names.
+ * omc_store_coalloc:
+ *   per_label == 0: counts_out int64 [batches][n_idx][n_idx], entry (i, j) = the rows in which elements i and j both carry a label
+ *           and the same one; the diagonal = the rows in which the element carries a label at all;
+ *   per_label != 0: counts_out int64 [batches][n_labels][n_idx][n_idx], entry (k, i, j) = the rows with z_i == k and z_j == k:
+ *           (Z[:, :, None] == k) & (Z[:, None, :] == k) summed over the rows -- for spike-and-slab the joint inclusion count of two
+ *           coefficients.  Its diagonal is the marginal label count (omc_store_histogram on the edges 0, 1, .., K), its sum over
+ *           k the plain form;
+ *   flags_out int64 [batches][n_idx][2] = {NaN draws, other non-label draws} of every selected element; may be NULL.
+ *   out == out' bit for bit: one triangle of tiles is computed and mirrored.
+ * One read of the selected columns turns every draw into a byte; the counts are the Gram product of the one-hot int8 indicators
+ * of the labels on the int8 matrix cores, accumulated in int32 over slices of fewer than 2^31 rows and joined in int64.  Every
+ * result is an exact integer: repeated calls are bit-equal.  Runs on the context's stream; workspace from the context (the
+ * label bytes of at most 1 GiB of rows at a time, the slices' partial tiles).                                              */
+omc_status omc_store_coalloc(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
+                             int32_t n_labels, int32_t pooled, int32_t per_label, int64_t* counts_out, int64_t* flags_out);
+/* Least-squares partition (Dahl 2006) of the same selection: the stored state whose co-membership matrix is nearest to the
+ * similarity matrix, which is the stored state of least posterior expected Binder loss.
+ *   counts  int64 [batches][n_idx][n_idx] (device): the per_label == 0 output of omc_store_coalloc for the same arguments;
+ *   score_out int64 [n_iter][C]: for the stored state s of batch b, over positions i < j of the selection,
+ *           score = sum_{i<j} [z_i^s == z_j^s] (R_b - 2 counts[b][i][j])
+ *           = R_b sum_{i<j} (c_ij^s - counts_ij / R_b)^2 minus a term that does not depend on s, an exact integer:
+ *           ((Z[s][:, None] == Z[s][None, :]) * np.triu(R - 2 * counts, 1)).sum();
+ *   best_out int64 [batches][2] = {row of the first minimum of the batch's scores, that score}: np.argmin's first-minimum rule;
+ *           the row is it C + c pooled and it per chain.
+ *   n_idx (n_idx - 1) / 2 x R >= 2^62 is OMC_UNSUPPORTED.
+ * One read of the selected columns (the same bytes); the compares run on the vector ALU against tiles of R - 2 counts in LDS, the
+ * partial scores are added with 64-bit integer atomics: repeated calls are bit-equal.  Runs on the context's stream.      */
+omc_status omc_store_partition_score(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx,
+                                     int64_t n_idx, int32_t n_labels, int32_t pooled, const int64_t* counts, int64_t* score_out,
+                                     int64_t* best_out);
 /* Ranks of the draws of every selected element of the same store; store, idx, n_idx, the NULL convention and the out-of-range rule
  * as omc_store_minmax (an index outside [0, size) is OMC_INVALID_ARG, found on the device before any output is written).
  * With N = n_iter >= 4: M = N / 2, J = 2 C, S = J M; the SPLIT DRAWS of an element are the first M and the last M iterations of

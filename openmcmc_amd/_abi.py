@@ -163,6 +163,8 @@ SIGNATURES = {
     "omc_store_histogram2d": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, c_dp, c_dp, i64, i32, i32, i32, c_dp, i32, c_dp, i32, c_dp,
                                     c_dp, c_dp]),
     "omc_store_histogram2d_layout": (i32, [i32, i32, i32, i32, C.POINTER(i32)]),
+    "omc_store_coalloc": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i32, i32, i32, c_dp, c_dp]),
+    "omc_store_partition_score": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i32, i32, c_dp, c_dp, c_dp]),
     "omc_store_ranks": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i32, c_dp]),
     "omc_store_rank_diagnostics": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, c_dp, c_dp, c_dp]),
     "omc_store_ess_indicator": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, i32,

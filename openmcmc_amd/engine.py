@@ -1434,6 +1434,51 @@ class Engine:
         return (counts, outside, occupied) if occupancy else (counts, outside)
 
     @staticmethod
+    def _n_labels(n_labels):
+        k = int(n_labels)
+        if k != n_labels or k < 1:
+            raise ValueError("n_labels must be an integer >= 1")
+        if k > 64:
+            raise NotImplementedError("at most 64 labels")
+        return k
+
+    def store_coalloc(self, store, n_labels, index=None, pooled=True, per_label=False):
+        """(counts, flags) of the allocation vectors in a device store (n_iter, C, size) of fp64 labels 0 .. n_labels - 1, on the
+        device (omc_store_coalloc).  counts int64 (n, n) pooled over chains and iterations, else (C, n, n): entry (i, j) = the
+        rows in which elements i and j carry the same label -- (Z[:, :, None] == Z[:, None, :]).sum(0) of the gathered labels;
+        with per_label (K, n, n) or (C, K, n, n): entry (k, i, j) = the rows with z_i == k and z_j == k.  flags int64 (.., n, 2) =
+        NaN draws (element absent) and other draws that are no label in [0, n_labels), per element; such a draw matches
+        nothing, not even itself.  Exactly symmetric; every entry an exact integer; at most 64 labels."""
+        torch = _torch()
+        n_iter, size, idx, n = self._selection(store, index)
+        k = self._n_labels(n_labels)
+        lead = () if pooled else (self.n_chains,)
+        counts = self.empty(lead + ((k,) if per_label else ()) + (n, n), dtype=torch.int64)
+        flags = self.empty(lead + (n, 2), dtype=torch.int64)
+        self._check_text(lib.omc_store_coalloc(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, k, int(bool(pooled)),
+                                               int(bool(per_label)), counts.data_ptr(), flags.data_ptr()))
+        return counts, flags
+
+    def store_partition_score(self, store, n_labels, counts, index=None, pooled=True):
+        """(score, best) of the stored states of the same selection against counts, the plain (per_label=False) result of
+        store_coalloc for the same arguments, on the device (omc_store_partition_score).  score int64 (n_iter, C): of the state
+        s of a batch of R rows, sum over i < j of [z_i == z_j] (R - 2 counts_ij) -- R times the squared distance of the
+        state's co-membership matrix from counts / R, up to a constant; best int64 (2,) pooled, else (C, 2) = the row of the
+        first minimum of the batch (it * C + c pooled, it per chain) and its score: Dahl's least-squares partition."""
+        torch = _torch()
+        n_iter, size, idx, n = self._selection(store, index)
+        k = self._n_labels(n_labels)
+        lead = () if pooled else (self.n_chains,)
+        if not isinstance(counts, torch.Tensor) or counts.dtype is not torch.int64 or not counts.is_cuda or tuple(counts.shape) != lead + (n, n):
+            raise TypeError(f"counts must be an int64 ROCm tensor {lead + (n, n)}")
+        counts = counts.contiguous()
+        score = self.empty((n_iter, self.n_chains), dtype=torch.int64)
+        best = self.empty(lead + (2,), dtype=torch.int64)
+        self._check_text(lib.omc_store_partition_score(self._ctx, n_iter, size, self._p(store), _ptr(idx), n, k, int(bool(pooled)),
+                                                       counts.data_ptr(), score.data_ptr(), best.data_ptr()))
+        return score, best
+
+    @staticmethod
     def rank_schedule(n_draws, tile=0):
         """The launches that sort columns of n_draws keys with LDS tiles of `tile` keys (0: the default 8192), as
         omc_store_rank_schedule lists them: [(kind, k, j), ...] (include/omcmc_hip.h; needs no GPU)."""
