@@ -947,6 +947,58 @@ omc_status omc_kde_binned(omc_ctx* ctx, int64_t n_cols, int32_t G, const int64_t
  * workgroup, byte offsets of the counts [G], of A2 [G], of the quarter-wave cosines [G + 1], of the Gaussian table [2 G] and of the
  * block sums [64] (all doubles), end of the image = bytes launched, the budget}.                                          */
 omc_status omc_kde_layout(int32_t G, int32_t* out);
+/* Joint kernel density estimate, kernel covariance, joint mode and highest-density-region levels of n_grids pairs of coordinates
+ * from their 2-D bin counts: what scipy.stats.gaussian_kde on two rows / az.plot_kde(x, y, hdi_probs=...) give for two columns of
+ * MCMC.store[param] on the host (mcmc.py:105-111 of the reference), from counts such as omc_store_histogram2d's over evenly spaced
+ * edges.  Everything is a function of (counts, grid) alone: int64 counts of several ranks over the same edges can be added, and one
+ * call gives the estimate of all ranks' chains, bit-equal to the call on the whole.  All arrays on the device; any output may be NULL.
+ *   counts  int64 [n_grids][nx][ny], the layout of omc_store_histogram2d's counts_out; 8 <= nx, ny <= 256, else OMC_INVALID_ARG.
+ *           A negative count is OMC_INVALID_ARG, found on the device before anything is written (one read-back of two words); the
+ *           outputs are untouched by every OMC_INVALID_ARG.
+ *   lo_x, hi_x, lo_y, hi_y [n_grids]: grid g spans [lo_x, hi_x] x [lo_y, hi_y]; delta_x = (hi_x - lo_x) / nx, bin centres
+ *           X_i = lo_x + (i + 1/2) delta_x, the same for y.  N = sum_ij c_ij (exact below 2^53), p_ij = c_ij / N.
+ *   Binned moments: m_x = sum_i (sum_j p_ij) X_i, s_xx = N / (N - 1) sum_i (sum_j p_ij) (X_i - m_x)^2, likewise m_y, s_yy;
+ *           s_xy = N / (N - 1) sum_ij p_ij (X_i - m_x) (Y_j - m_y).
+ *   rule    0 given: the symmetric kernel covariance H = (h_xx, h_xy, h_yy) = bw_in[g][0..2] (bw_in NULL is OMC_INVALID_ARG);
+ *           1 Scott: H = N^(-1/3) S -- in two dimensions also Silverman's rule, (N (d + 2) / 4)^(-2 / (d + 4)) at d = 2, and what
+ *             scipy.stats.gaussian_kde and ArviZ's 2-D KDE use (factor N^(-1/6) on the sample covariance with ddof 1).
+ *           Every H is multiplied by bw_fct^2 (bw_fct finite and > 0, else OMC_INVALID_ARG).
+ *   density_out [n_grids][nx][ny]: f(X_k, Y_l) = 1 / (N 2 pi sqrt(det H)) sum_i sum_j c_ij exp(-q / 2), q = A u^2 + 2 B u v + C v^2,
+ *           u = (k - i) delta_x, v = (l - j) delta_y, (A, B, C) = (h_yy, -h_xy, h_xx) / det H.  No truncation, and no reflection at
+ *           a bound: reflecting a correlated kernel is not defined here (out of scope).  q is evaluated as the completed square
+ *           A (u + (B / A) v)^2 + v^2 / h_yy, B / A = -h_xy / h_yy: the same number, as two non-negative terms.  Summed term by
+ *           term, the three terms cancel at a high correlation and the tails lose digits (4.8e-12 relative in fp64 at 0.99);
+ *           a restatement that is to agree within 1e-10 takes this form or more precision.
+ *   bw_out [n_grids][3] the H used; mode_out [n_grids][2] = (X_k, Y_l) of the largest density, the lowest flat index k ny + l of
+ *           equals, each centre formed as lo + (k + 1/2) delta with both roundings.
+ *   Regions: probs [n_probs] (device), 0 <= n_probs <= 16, each in (0, 1), else OMC_INVALID_ARG (found on the device with the
+ *           counts); NULL with n_probs 0: no levels.  D_0 >= D_1 >= .. the nx ny densities of a grid in descending order (the
+ *           key-only sort of the store summaries on the bit patterns: non-negative doubles order as unsigned integers),
+ *           S_r = D_0 + .. + D_r, S = S at r = nx ny - 1; level_pos_out int64 [n_grids][n_probs] = the first r with
+ *           S_r >= prob S, level_out [n_grids][n_probs] = D_r: {f >= level} is the highest-density region that holds that share
+ *           of the mass (ArviZ's _find_hdi_contours).  The order of the additions in S_r depends on nx ny alone: with
+ *           len = ceil(nx ny / 256), the running sum of segment t = [t len, (t + 1) len) starts from the sum of the sums of the
+ *           segments before it (each added up from zero in ascending order, the segments in ascending order) and takes its own
+ *           densities in ascending r.
+ *   flag_out int32 [n_grids]: 0 ok; 2 degenerate -- every output of that grid NaN (level_pos -1), other grids unaffected: an end
+ *           not finite or hi <= lo; under rule 1 N < 2 or fewer than two non-empty rows or columns (decided on the integers);
+ *           under rule 0 N == 0; h_xx or h_yy not finite and positive, h_xy not finite; h_xy^2 >= (1 - 2^-20) h_xx h_yy: the
+ *           kernel is singular or nearly so -- far outside rounding's reach, so that exactly collinear cells always flag and
+ *           honest inputs never do.
+ * Work is split over (grid, tile of output cells): omc_kde2d_layout.  Every sum runs in an order that (nx, ny) alone fixes; no
+ * atomics; repeated calls are bit-equal, and a grid alone gives the bits it gives inside a batch.  Empty cells and rows are
+ * skipped: adding +0 to a non-negative finite sum changes no bit.  Runs on the context's stream.                                */
+omc_status omc_kde2d_binned(omc_ctx* ctx, int64_t n_grids, int32_t nx, int32_t ny, const int64_t* counts, const double* lo_x,
+                            const double* hi_x, const double* lo_y, const double* hi_y, int32_t rule, const double* bw_in,
+                            double bw_fct, int32_t n_probs, const double* probs, double* density_out, double* bw_out,
+                            double* mode_out, double* level_out, int64_t* level_pos_out, int32_t* flag_out);
+/* [host, no GPU] The tiling and LDS image of omc_kde2d_binned's convolution at (nx, ny) (each 8..256, else OMC_INVALID_ARG):
+ * out[16] = {TX, TY (rows and columns of an output tile), RY (adjacent columns a lane owns, TY = 64 RY), RB (rows of a count
+ * block), threads of a workgroup, tiles along x, tiles along y, stride of a count row (doubles: ny rounded up to RY), slots of a
+ * plane of weights, byte offsets of the counts [RB + 1][stride], the rows' flags [RB + 1], the rows' masks of non-empty runs
+ * [RB + 1][2] (64-bit) and the weights [4 waves][RY][slots], bytes of a wave's weights, end of the image = bytes launched, the
+ * budget}.                                                                                                                  */
+omc_status omc_kde2d_layout(int32_t nx, int32_t ny, int32_t* out);
 /* Joint histogram of pairs of elements of the same store(s): np.histogram2d(x, y, bins=[edges_x, edges_y]) of two rows of the
  * reference's host arrays MCMC.store[param] (mcmc.py:105-111), for all pairs at once; layout conventions of omc_store_histogram.
  *   store_x [n_iter][C][size_x], store_y [n_iter][C][size_y] (device): the same tensor or two; pair k = (element idx_x[k] of

@@ -160,6 +160,9 @@ SIGNATURES = {
     "omc_store_histogram_layout": (i32, [i32, i32, C.POINTER(i32)]),
     "omc_kde_binned": (i32, [C.c_void_p, i64, i32, c_dp, c_dp, c_dp, i32, c_dp, C.c_double, i32, c_dp, c_dp, c_dp, c_dp]),
     "omc_kde_layout": (i32, [i32, C.POINTER(i32)]),
+    "omc_kde2d_binned": (i32, [C.c_void_p, i64, i32, i32, c_dp, c_dp, c_dp, c_dp, c_dp, i32, c_dp, C.c_double, i32, c_dp, c_dp, c_dp,
+                               c_dp, c_dp, c_dp, c_dp]),
+    "omc_kde2d_layout": (i32, [i32, i32, C.POINTER(i32)]),
     "omc_store_histogram2d": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, c_dp, c_dp, i64, i32, i32, i32, c_dp, i32, c_dp, i32, c_dp,
                                     c_dp, c_dp]),
     "omc_store_histogram2d_layout": (i32, [i32, i32, i32, i32, C.POINTER(i32)]),

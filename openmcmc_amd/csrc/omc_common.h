@@ -61,10 +61,11 @@ struct omc_ctx {
   omc_buf<double> workspace;  // scratch for the serial kernel (l vectors), grown on demand
   // scratch of a store summary that is consumed before the call returns or the next summary starts: the word(s) of the index and
   // edge checks (omc_store_shared.hip, omc_hist.hip), partial column moments (omc_store_shared.hip: omc_store_moments and
-  // omc_store_cov), radix histograms (omc_store.hip), partial minima / maxima (omc_hist.hip), lag sums and Geyer state (omc_diag.hip), the int32 partial tiles of omc_store_coalloc (omc_coalloc.hip)
+  // omc_store_cov), radix histograms (omc_store.hip), partial minima / maxima (omc_hist.hip), lag sums and Geyer state (omc_diag.hip), the int32 partial tiles of omc_store_coalloc (omc_coalloc.hip),
+  // and, for the whole of an omc_kde2d_binned call, its check words, every grid's kernel parameters and flag and a bit per count row (omc_kde2d.hip)
   omc_buf<void> store_ws;
   omc_buf<double> cov_ws;  // omc_cov.hip: means, variances and partial tiles of omc_store_cov
-  omc_buf<void> rank_ws;  // omc_rank.hip, omc_hdi.hip: keys, series and per-element words of a chunk (its own: it calls omc_store_rhat_ess, which uses store_ws); omc_autocorr.hip: partial lag sums and centred draws of a chunk (omc_col_moments uses store_ws); omc_coalloc.hip: the label bytes of a chunk of rows (its partial tiles and index check use store_ws)
+  omc_buf<void> rank_ws;  // omc_rank.hip, omc_hdi.hip: keys, series and per-element words of a chunk (its own: it calls omc_store_rhat_ess, which uses store_ws); omc_autocorr.hip: partial lag sums and centred draws of a chunk (omc_col_moments uses store_ws); omc_coalloc.hip: the label bytes of a chunk of rows (its partial tiles and index check use store_ws); omc_kde2d.hip: the densities of a chunk of grids (unless the caller takes them) and their sort keys (its parameters stay in store_ws; rank_sort uses neither)
   // rocBLAS handle of the context's stream, created on first use (omc_ensure_blas)
   void* blas = nullptr;
   // blocked dense factorisation: second half of the chains on a side stream (forked from / joined into `stream` by events),

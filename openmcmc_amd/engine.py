@@ -1375,6 +1375,69 @@ class Engine:
                                  self._p(density), self._p(bw_out), flag.data_ptr(), self._p(mode)))
         return density, bw_out, mode, flag
 
+    KDE2D_RULES = {"given": 0, "scott": 1, "silverman": 1}
+
+    @staticmethod
+    def kde2d_layout(nx, ny):
+        """The sixteen numbers of omc_kde2d_layout: TX, TY (output tile), RY (columns a lane owns), RB (rows of a count block),
+        threads, tiles along x and y, stride of a count row, slots of a plane of weights, byte offsets of the counts, the rows'
+        flags, the rows' masks and the weights, bytes of a wave's weights, bytes launched, the budget
+        (openmcmc_amd/csrc/omc_kde2d_layout.h; needs no GPU)."""
+        out = (C.c_int32 * 16)()
+        check(lib.omc_kde2d_layout(int(nx), int(ny), out))
+        return list(out)
+
+    def kde2d_binned(self, counts, lo_x, hi_x, lo_y, hi_y, rule="scott", bw=None, bw_fct=1.0, probs=None):
+        """Joint kernel density estimates from 2-D bin counts, on the device (omc_kde2d_binned): counts int64 (.., nx, ny),
+        8 <= nx, ny <= 256, over evenly spaced bins of [lo_x, hi_x] x [lo_y, hi_y] (fp64 of the leading shape) -> (density
+        (.., nx, ny) at the bin centres, bw (.., 3) = the kernel covariance (h_xx, h_xy, h_yy), mode (.., 2), level (.., n_probs),
+        level_pos int64 (.., n_probs), flag int32), device tensors.  rule: "scott" or "silverman" (the same rule in two
+        dimensions, H = N^(-1/3) S: what scipy.stats.gaussian_kde does) or "given" with bw, a tensor (.., 3); every H is
+        multiplied by bw_fct^2.  probs: the shares of mass, each in (0, 1), at most 16, whose highest-density regions are wanted:
+        {density >= level} holds that share; level_pos is the level's position among the densities in descending order.
+        flag: 0 ok, 2 degenerate (NaN outputs, level_pos -1; the other grids are not affected).  The estimate is a function of
+        (counts, grid) alone: under a sharded run all-reduce the counts taken over the same edges and make one call -- that is the
+        KDE of all ranks' chains.  Repeated calls are bit-equal."""
+        torch = _torch()
+        if rule not in self.KDE2D_RULES:
+            raise ValueError(f"rule must be one of {sorted(self.KDE2D_RULES)}")
+        if not isinstance(counts, torch.Tensor) or counts.dtype is not torch.int64 or not counts.is_cuda or counts.dim() < 2:
+            raise TypeError("counts must be an int64 ROCm tensor (.., nx, ny)")
+        counts = counts.contiguous()
+        lead, (nx, ny) = tuple(counts.shape[:-2]), counts.shape[-2:]
+        if not (8 <= nx <= 256 and 8 <= ny <= 256):
+            raise ValueError("between 8 and 256 bins per axis")
+        n_grids = int(np.prod(lead, dtype=np.int64))
+        if n_grids < 1:
+            raise ValueError("no grid")
+
+        def column(v, what, tail=()):
+            v = self.to_device(v)
+            if tuple(v.shape) != lead + tail:
+                raise ValueError(f"{what} must have the leading shape of counts, {lead}" + (f", and {tail}" if tail else ""))
+            return v
+
+        ends = [column(v, what) for v, what in ((lo_x, "lo_x"), (hi_x, "hi_x"), (lo_y, "lo_y"), (hi_y, "hi_y"))]
+        if (rule == "given") != (bw is not None):
+            raise ValueError('bw goes with rule="given"')
+        bw_in = None if bw is None else column(bw, "bw", (3,))
+        p = np.zeros(0) if probs is None else np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if p.ndim != 1 or p.size > 16 or not np.all((p > 0) & (p < 1)):
+            raise ValueError("probs must be at most 16 shares of mass, each in (0, 1)")
+        n_probs = int(p.size)
+        probs_dev = self._f64(p) if n_probs else None
+        density = torch.empty(lead + (nx, ny), dtype=torch.float64, device=self.device)
+        bw_out = torch.empty(lead + (3,), dtype=torch.float64, device=self.device)
+        mode = torch.empty(lead + (2,), dtype=torch.float64, device=self.device)
+        level = torch.empty(lead + (n_probs,), dtype=torch.float64, device=self.device)
+        level_pos = torch.empty(lead + (n_probs,), dtype=torch.int64, device=self.device)
+        flag = self.empty(lead, dtype=torch.int32)
+        check(lib.omc_kde2d_binned(self._ctx, n_grids, nx, ny, counts.data_ptr(), *(self._p(v) for v in ends),
+                                   self.KDE2D_RULES[rule], self._p(bw_in), float(bw_fct), n_probs, self._p(probs_dev),
+                                   self._p(density), self._p(bw_out), self._p(mode), self._p(level) if n_probs else None,
+                                   level_pos.data_ptr() if n_probs else None, flag.data_ptr()))
+        return density, bw_out, mode, level, level_pos, flag
+
     @staticmethod
     def hist2d_tile(nx, ny, per_pair=False, pool_pairs=False):
         """(TE, RB) of omc_store_histogram2d at an nx x ny grid: a workgroup counts a tile of TE consecutive pairs (1 with

@@ -1347,6 +1347,123 @@ class MCMC:
         (_, _, occupied), ex, ey, rows = self._hist2d(key_x, key_y, index_x, index_y, bins, range, pooled, True, True)
         return occupied / rows, ex, ey
 
+    def kde2d(self, key_x, key_y=None, index_x=None, index_y=None, pooled=True, grid_len=128, bw="scott", bw_fct=1.0, extend=0.1,
+              probs=(0.5, 0.9), pool_elements=False):
+        """Joint kernel density estimate of pairs of elements -- the surface, the contour levels and the joint mode of
+        az.plot_pair(kind="kde") / az.plot_kde(x, y, hdi_probs=...) -- from one joint histogram pass over the store and a
+        full-covariance binned Gaussian convolution on the device (no gather): a dict of host arrays "grid_x" (.., nx), "grid_y"
+        (.., ny) (the bin centres), "density" (.., nx, ny), "bw" (.., 3) = the kernel covariance (h_xx, h_xy, h_yy), "mode" (.., 2),
+        "probs", "levels" (.., n_probs), "flag" (int32), "n" (pairs counted) and "outside" (pairs left out: a NaN coordinate).
+        Pairs are selected as in `histogram2d`: pair k is element index_x[k] of store[key_x] against element index_y[k] of
+        store[key_y] in the same state (key_y=None: two elements of store[key_x]); the leading shape is (n_pairs,) pooled over
+        chains and iterations, else (C, n_pairs); with pool_elements=True all pairs go into one density, () or (C,) -- the joint
+        density of a NaN-padded variable-size parameter, locations against coefficients.  grid_len: an int or (nx, ny), each
+        8..256.  The grid of a coordinate spans its minimum and maximum over ALL chains (with pool_elements: over all selected
+        elements), widened by extend (max - min) either way; a coordinate that never moved is widened by 0.5 as in `kde` and
+        leaves its pair with flag 2 under a rule.  The pairs are counted into the cells with the edges np.linspace(a, b, n + 1)
+        (counts equal np.histogram2d); the density is the binned convolution at the bin centres, without reflection at bounds.
+        bw: "scott" or "silverman" (one rule in two dimensions, H = N^(-1/3) S, S the covariance of the binned pairs: what
+        scipy.stats.gaussian_kde and ArviZ use); "marginal", the product kernel H = diag(h_x^2, h_y^2), h the coordinate's own
+        `kde(..., bw="experimental")` bandwidth on the marginal counts times N^(1/30) (the 1-D rate N^(-1/5) moved to the 2-D
+        rate N^(-1/6)) -- the choice for the bimodal joints of mixture-prior and reversible-jump models, which Scott's rule
+        oversmooths; or a symmetric 2 x 2 matrix, or (n_pairs, 2, 2).  Every H is multiplied by bw_fct^2.  "levels": for every
+        prob the density level whose region {density >= level} is the highest-density region holding that share of the mass
+        (ArviZ's _find_hdi_contours); "mode": the grid point of the largest density, the lowest flat index of equal ones.
+        flag: 0 ok; 1 ("marginal") the Sheather-Jones equation of a coordinate had no root and Silverman's bandwidth stands in; 2
+        degenerate (fewer than two pairs, non-empty rows or columns, a singular or nearly singular H; density, bw, mode and levels
+        are NaN).  An infinite draw raises ValueError as in `histogram2d`.  Under a sharded multi-GPU run this covers this rank's
+        chains only; the estimate is a function of the counts and the grid alone, so counts of several ranks over the same edges
+        can be added and handed to `engine.kde2d_binned`, which gives the estimate of all ranks' chains."""
+        self._whole_store_on_device("kde2d")
+        tx = self._store_3d(key_x)
+        ty = tx if key_y is None else self._store_3d(key_y)
+        try:
+            nx, ny = grid_len
+        except TypeError:
+            nx = ny = grid_len
+        if int(nx) != nx or int(ny) != ny or not (8 <= nx <= 256 and 8 <= ny <= 256):
+            raise ValueError("grid_len must be an integer or (nx, ny), each between 8 and 256")
+        nx, ny = int(nx), int(ny)
+        if not (np.ndim(extend) == 0 and extend >= 0 and np.isfinite(extend)):
+            raise ValueError("extend must be a finite non-negative number")
+        # every argument is judged before the store is read
+        if not (np.ndim(bw_fct) == 0 and bw_fct > 0 and np.isfinite(bw_fct)):
+            raise ValueError("bw_fct must be a finite positive number")
+        p = np.zeros(0) if probs is None else np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if p.ndim != 1 or p.size > 16 or not np.all((p > 0) & (p < 1)):
+            raise ValueError("probs must be at most 16 shares of mass, each in (0, 1)")
+        H = None
+        if not isinstance(bw, str):
+            H = np.asarray(bw, dtype=np.float64)
+            n_sel = tx.shape[2] if index_x is None else len(index_x)
+            if H.shape not in ((2, 2), (n_sel, 2, 2)) or (H.ndim == 3 and pool_elements):
+                raise ValueError("bw must be a rule's name, a 2 x 2 matrix or, without pool_elements, an (n_pairs, 2, 2) array")
+            if not np.array_equal(H[..., 0, 1], H[..., 1, 0]):
+                raise ValueError("bw must be symmetric")
+        elif bw not in ("scott", "silverman", "marginal"):
+            raise ValueError('bw must be "scott", "silverman", "marginal" or a symmetric 2 x 2 matrix')
+
+        def axis(t, index, n):  # (a, b, edges) of a coordinate: per pair, or one for all with pool_elements
+            mn, mx, cnt = (v.cpu().numpy() for v in self.engine.store_minmax(t, index=index, pooled=True))
+            lo, hi = np.where(cnt > 0, mn, 0.0), np.where(cnt > 0, mx, 1.0)
+            if pool_elements:
+                have = cnt > 0
+                lo, hi = (np.array([lo[have].min()]), np.array([hi[have].max()])) if have.any() else (np.zeros(1), np.ones(1))
+            if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+                raise ValueError("autodetected range is not finite")
+            same = lo == hi
+            pad = extend * (hi - lo)
+            a, b = np.where(same, lo - 0.5, lo - pad), np.where(same, hi + 0.5, hi + pad)
+            edges = np.stack([np.linspace(p, q, n + 1) for p, q in zip(a, b)])
+            return (a[0], b[0], edges[0]) if pool_elements else (a, b, edges)
+
+        ax, bx, ex = axis(tx, index_x, nx)
+        ay, by, ey = axis(ty, index_y, ny)
+        counts, outside = self.engine.store_histogram2d(tx, ty, ex, ey, index_x=index_x, index_y=index_y, pooled=pooled,
+                                                        pool_pairs=pool_elements)
+        lead = tuple(counts.shape[:-2])
+        # (device tensors of the leading shape, () with pooled elements, which a host array would not keep)
+        ends = [self.engine.to_device(np.array(np.broadcast_to(v, lead))).reshape(lead) for v in (ax, bx, ay, by)]
+        rule, given, flag1 = bw, None, None
+        if isinstance(bw, str) and bw == "marginal":
+            n_pairs = counts.sum(dim=(-2, -1)).double()
+            _, hx, _, fx = self.engine.kde_binned(counts.sum(dim=-1), ends[0], ends[1], rule="experimental")
+            _, hy, _, fy = self.engine.kde_binned(counts.sum(dim=-2), ends[2], ends[3], rule="experimental")
+            up = n_pairs ** (1.0 / 30.0)
+            hx, hy = hx * up, hy * up
+            given = self.engine.full(lead + (3,), 0.0)
+            given[..., 0], given[..., 2] = hx * hx, hy * hy
+            rule, flag1 = "given", ((fx == 1) | (fy == 1)).cpu().numpy()
+        elif H is not None:
+            rule = "given"
+            given = np.array(np.broadcast_to(np.stack([H[..., 0, 0], H[..., 0, 1], H[..., 1, 1]], axis=-1), lead + (3,)))
+        density, h, mode, level, _, flag = self.engine.kde2d_binned(counts, *ends, rule=rule, bw=given, bw_fct=bw_fct, probs=p)
+        flag = flag.cpu().numpy()
+        if flag1 is not None:
+            flag = np.where((flag == 0) & flag1, np.int32(1), flag).astype(np.int32)
+        gx, gy = 0.5 * (ex[..., :-1] + ex[..., 1:]), 0.5 * (ey[..., :-1] + ey[..., 1:])
+        return {"grid_x": np.ascontiguousarray(np.broadcast_to(gx, lead + (nx,))),
+                "grid_y": np.ascontiguousarray(np.broadcast_to(gy, lead + (ny,))), "density": density.cpu().numpy(),
+                "bw": h.cpu().numpy(), "mode": mode.cpu().numpy(),
+                "probs": p,
+                "levels": level.cpu().numpy(), "flag": flag, "n": counts.sum(dim=(-2, -1)).cpu().numpy(),
+                "outside": outside.sum(dim=-1).cpu().numpy()}
+
+    def joint_mode(self, key_x, key_y=None, index_x=None, index_y=None, pooled=True, **kde2d_args):
+        """Joint posterior mode of pairs of elements: the grid point of the largest joint kernel density estimate,
+        kde2d(key_x, key_y, index_x, index_y, pooled, **kde2d_args)["mode"], (.., 2).  The pair of marginal `mode`s is no joint
+        mode: a ridge or a second cluster moves a marginal's peak to where the joint density has none."""
+        return self.kde2d(key_x, key_y, index_x, index_y, pooled, **kde2d_args)["mode"]
+
+    def density_region(self, key_x, key_y=None, index_x=None, index_y=None, prob=0.9, pooled=True, **kde2d_args):
+        """The highest-density region of pairs of elements that holds the share `prob` of the mass: (mask, grid_x, grid_y), mask
+        bool (.., nx, ny) = density >= level of kde2d(..., probs=(prob,)) -- the cells inside az.plot_kde's contour at
+        hdi_probs=[prob]; all False for a degenerate pair (flag 2)."""
+        out = self.kde2d(key_x, key_y, index_x, index_y, pooled, probs=(prob,), **kde2d_args)
+        with np.errstate(invalid="ignore"):
+            mask = out["density"] >= out["levels"][..., 0, None, None]
+        return mask, out["grid_x"], out["grid_y"]
+
     def _thinned(self, every):
         """{key: device tensor (ceil(n_iter / every), C, ...)}: every `every`-th stored iteration, packed on the device"""
         self._whole_store_on_device("a thinned transfer")
