@@ -25,8 +25,9 @@ SCRIPTS = ["store_covariance.py", "store_hdi.py", "store_rank_diagnostics.py", "
 NOT_OURS = re.compile(r"host|numpy|torch|wall|mcmc_|(^|[/_ ])gram|scipy|arviz", re.I)
 
 
-def cases(node, path=""):
-    """{case: ms} of a script's JSON: numbers under keys ending in "ms", rows {"case": .., "ms": ..} under their label"""
+def cases(node, path="", not_ours=NOT_OURS):
+    """{case: ms} of a script's JSON: numbers under keys ending in "ms", rows {"case": .., "ms": ..} under their label; the cases
+    whose name matches `not_ours` are left out"""
     found = {}
     if isinstance(node, dict):
         if "case" in node and isinstance(node.get("ms"), (int, float)):
@@ -35,11 +36,11 @@ def cases(node, path=""):
             if isinstance(v, (int, float)) and not isinstance(v, bool) and k.endswith("ms"):
                 found[f"{path}{k}"] = float(v)
             elif isinstance(v, (dict, list)):
-                found.update(cases(v, f"{path}{k}/"))
+                found.update(cases(v, f"{path}{k}/", not_ours))
     elif isinstance(node, list):
         for i, v in enumerate(node):
-            found.update(cases(v, path if isinstance(v, dict) and "case" in v else f"{path}{i}/"))
-    return {k: v for k, v in found.items() if not NOT_OURS.search(k)}
+            found.update(cases(v, path if isinstance(v, dict) and "case" in v else f"{path}{i}/", not_ours))
+    return {k: v for k, v in found.items() if not not_ours.search(k)}
 
 
 def main():

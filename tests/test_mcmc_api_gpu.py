@@ -599,3 +599,40 @@ def test_run_mcmc_hands_manifold_mala_whole_blocks(ring):
     assert np.array_equal(a0, a1) and np.array_equal(p0, p1) and p0[0] == n_burn + n_iter and 0 < a0.sum() < p0.sum()
     assert np.array_equal(s0["log_post"], s1["log_post"])
     assert relerr(s1["x"], s0["x"]) < 1e-12 and relerr(x_1, x_0) < 1e-12
+
+
+def test_the_four_binned_summaries_agree_on_the_automatic_range():
+    """histogram, histogram2d, kde and kde2d give an element the same axis: a generic column, a constant one, one without a draw,
+    one with a NaN, one of -0.0 and 0.0 only -- and with pool_elements the range of the flattened draws."""
+    from openmcmc_amd.engine import Engine
+    from openmcmc_amd.mcmc import MCMC
+
+    n_iter, C, size = 6, 2, 5
+    x = np.random.default_rng(21).standard_normal((n_iter, C, size))
+    x[:, :, 1] = 3.25
+    x[:, :, 2] = np.nan
+    x[4, 1, 3] = np.nan
+    x[:, :, 4] = np.where(np.arange(n_iter * C).reshape(n_iter, C) % 2 == 0, -0.0, 0.0)
+    M = MCMC.__new__(MCMC)  # the summaries need the engine, the store and the ring fields only
+    M.engine = Engine(C, seed=0)
+    M.store, M._derived, M.store_ring, M._n_dev, M.n_iter = {"x": M.engine.to_device(x)}, set(), 0, n_iter, n_iter
+    M.n_chains, M.model, M.state = C, None, {}
+    idx = list(range(size))
+    edges = M.histogram("x", bins=8)[1]
+    assert edges.shape == (size, 9)
+    assert np.array_equal(edges[1], np.linspace(2.75, 3.75, 9)) and np.array_equal(edges[2], np.linspace(0.0, 1.0, 9))
+    assert np.array_equal(edges[4], np.linspace(-0.5, 0.5, 9))
+    for i in (0, 3):
+        assert np.array_equal(edges[i], np.linspace(np.nanmin(x[:, :, i]), np.nanmax(x[:, :, i]), 9))
+    _, ex, ey = M.histogram2d("x", index_x=idx, index_y=idx, bins=8)
+    assert np.array_equal(ex, edges) and np.array_equal(ey, edges)
+    mid = 0.5 * (edges[:, :-1] + edges[:, 1:])
+    assert np.array_equal(M.kde("x", grid_len=8, extend=0.0)["grid"], mid)
+    joint = M.kde2d("x", index_x=idx, index_y=idx, grid_len=8, extend=0.0)
+    assert np.array_equal(joint["grid_x"], mid) and np.array_equal(joint["grid_y"], mid)
+    flat = np.linspace(np.nanmin(x), np.nanmax(x), 9)
+    _, ex, ey = M.histogram2d("x", index_x=idx, index_y=idx, bins=8, pool_elements=True)
+    assert np.array_equal(ex, flat) and np.array_equal(ey, flat)
+    joint = M.kde2d("x", index_x=idx, index_y=idx, grid_len=8, extend=0.0, pool_elements=True)
+    assert np.array_equal(joint["grid_x"], 0.5 * (flat[:-1] + flat[1:])) and np.array_equal(joint["grid_y"], joint["grid_x"])
+    M.engine.close()
