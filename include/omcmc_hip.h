@@ -1233,6 +1233,52 @@ enum { OMC_REDUCE_SUM = 0, OMC_REDUCE_MIN = 1, OMC_REDUCE_MAX = 2, OMC_REDUCE_AR
        OMC_REDUCE_COUNT_ABOVE = 5, OMC_REDUCE_SUPNORM = 6 };
 omc_status omc_store_reduce(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx, int64_t n_idx,
                             int32_t op, int32_t omit_nan, const double* a, const double* b, double* out, int64_t* count_out);
+/* First failures of the stored states of the same store against per-element sides: the integer counts from which joint excursion
+ * sets, contour-avoiding sets, contour credible regions and the reliability of a contour map are computed (Bolin and Lindgren
+ * 2015, 2017; R's excursions) -- "over which set of elements is the field above u at ALL of them at once with probability 0.95",
+ * which the pointwise P(x_k > u) of a histogram cannot answer.  On host arrays it is a (rows x n_idx) boolean temporary and a
+ * permuted argmax; here it is one read of the store for up to 8 slots.
+ *   store, idx, n_idx and the NULL convention as omc_store_reduce (order kept, repeats allowed, n_idx may exceed size); an index
+ *   outside [0, size) is OMC_INVALID_ARG, found on the device before any output is written.  Selection position k = 0 .. n - 1,
+ *   n = n_idx, is element idx[k] of the row (k itself without an index) with value x.  Rows s = 0 .. R - 1, R = n_iter C, pooled
+ *   over chains.
+ *   One SLOT l = 0 .. n_slots - 1 is a triple of device arrays aligned with the selection (position k), the tables [n_slots][n]:
+ *     lo, hi   fp64 bounds; -inf and +inf mean "no bound on that side"
+ *     pos      int32, a permutation of 0 .. n - 1: the place of element k in the order in which the slot's elements are taken
+ *   Row s AGREES at k iff  x == x && (lo[k] == -inf || x > lo[k]) && (hi[k] == +inf || x < hi[k]):
+ *     a NaN draw is on no side; +-inf draws are ordinary values (a -inf draw agrees with lo = -inf, not with any finite lo);
+ *     bounds are strict (a draw equal to a bound does not agree).
+ *   The FIRST FAILURE of row s is  r_s = min({pos[k] : s does not agree at k} u {n}): an integer minimum, the same however the
+ *   work is cut.
+ *   h_out     [n_slots][n + 1] int64:  h[j] = #{s : r_s == j}.
+ *   rows_out  [n_slots][n_iter][C] int32 (may be NULL): r_s itself.
+ *   From h the caller has J[j] = R - sum_{i <= j} h[i], the rows that agree at all of the first j + 1 elements of the order, and the
+ *   excursion function F_k = J[pos[k]] / R (one IEEE division per element).  Counts taken by several contexts over the same
+ *   tables -- chains sharded over ranks -- add.
+ *   Only the range of pos is checked, on the device before any output is written; a pos that is no permutation gives the h the
+ *   definition above gives.
+ *   algo      0 automatic, 1 the short form, 2 the long form (below): tests and A/B runs reach each form on any shape.  It is an
+ *             argument, not a context option like "reduce_algo": the forms give the same integers, so nothing else depends on it.
+ *   OMC_INVALID_ARG, with a text in omc_last_error and the outputs untouched: ctx, store, lo, hi, pos or h_out NULL, n_iter < 1,
+ *     size < 1, n_idx < 1 (or no index and n_idx != size), n_idx > 2^31 - 2, n_slots outside 1 .. 8, algo outside 0 .. 2, an index
+ *     outside [0, size), a pos entry outside [0, n_idx), more than 2^31 - 1 workgroups.
+ * No floating point reaches a result: r is a minimum of int32, h is added with 64-bit integer atomics.  Repeated calls and both
+ * forms are equal in every bit.
+ * How: one read of the store for all slots.  Long rows: a workgroup owns 32 consecutive rows, a wave eight of them one after the
+ * other; 16-byte loads without an index (a row that starts 8 bytes off a 16-byte boundary gives its first element to lane 0, a
+ * last element without a partner goes to lane 63), a gathered 8-byte load per lane with one.  Short rows (automatic: size <= 128,
+ * omc_store_reduce's crossover) are staged, a tile of consecutive rows at a time, into LDS with 16-byte loads and walked by a
+ * power-of-two group of lanes per row; a row that does not fit 40 KiB of LDS takes the long form whatever algo says.  A lane
+ * keeps n_slots running minima (1, 2, 4 or 8 registers), lanes are joined by a butterfly of integer min.  The slot tables, 20
+ * n_slots bytes per selected element, are read through the caches (a wave needs the tables of the whole row; at n = 10 000 and 8
+ * slots they are 1.6 MB: more than a workgroup's LDS, less than an XCD's L2).  The r of a workgroup's rows meet in LDS, where the
+ * first of equal values within 32 rows adds their number to h with one atomic: to h_out, or in the short form, where
+ * n_slots (n + 1) <= 2048, to counters in LDS, which the workgroup adds to h_out after its last rows (at most eight workgroups per
+ * compute unit walk the rows).  No scratch.  Workspace (store_ws): two words,
+ * which the host reads back (the validation).  Runs on the context's stream.                                                   */
+omc_status omc_store_first_failure(omc_ctx* ctx, int64_t n_iter, int64_t size, const double* store, const int64_t* idx,
+                                   int64_t n_idx, int32_t n_slots, const double* lo, const double* hi, const int32_t* pos,
+                                   int32_t algo, int64_t* h_out, int32_t* rows_out);
 /* Autocovariance, autocorrelation and integrated autocorrelation time of the same store: the plot next to the trace, and the
  * one principled way to choose a thinning.  store, idx, n_idx and the NULL convention as omc_store_reduce (order kept, repeats
  * allowed, n_idx may exceed size); an index outside [0, size) is OMC_INVALID_ARG, found on the device before any output is written.

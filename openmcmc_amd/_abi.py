@@ -176,6 +176,7 @@ SIGNATURES = {
     "omc_store_rank_schedule": (i32, [i64, i32, C.POINTER(i64), i64, C.POINTER(i64)]),
     "omc_store_hdi": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, C.POINTER(C.c_double), i32, i32, i32, c_dp, c_dp]),
     "omc_store_reduce": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i32, i32, c_dp, c_dp, c_dp, c_dp]),
+    "omc_store_first_failure": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i32, c_dp, c_dp, c_dp, i32, c_dp, c_dp]),
     "omc_store_autocorr": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i64, i32, i32, c_dp, c_dp, c_dp, c_dp]),
     "omc_store_project": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, i64, c_dp, i64, c_dp, c_dp, i32, c_dp, i64, c_dp, u64, c_dp]),
     "omc_store_loglik": (i32, [C.c_void_p, i64, i64, c_dp, c_dp, i64, c_dp, c_dp, i64, c_dp, c_dp, c_dp, c_dp]),

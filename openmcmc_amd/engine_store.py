@@ -520,6 +520,41 @@ class StoreOps:
             self._p(out), cnt.data_ptr()))
         return out, cnt
 
+    def store_first_failure(self, store, lo, hi, pos, index=None, want_rows=False, algo=0):
+        """First failures of the stored states of a device store (n_iter, C, size) against per-element sides, on the device
+        (omc_store_first_failure; one read of the store for all slots): (h, r) as device tensors.  lo, hi (fp64) and pos
+        (integers, a permutation of 0 .. n_idx - 1 per slot) are (L, n_idx) tables of 1 <= L <= 8 slots, host arrays or device
+        tensors; (n_idx,) vectors are one slot.  With x the element at selection position k, a row agrees at k iff x is not NaN,
+        (lo[k] == -inf or x > lo[k]) and (hi[k] == +inf or x < hi[k]); its first failure is the smallest pos[k] among the positions
+        it does not agree at, n_idx if it agrees everywhere.  h is int64 (L, n_idx + 1): h[l, j] = the rows, pooled over chains and
+        iterations, whose first failure is j; r is int32 (L, n_iter, C), the first failures themselves, or None without
+        want_rows.  algo: 0 automatic, 1 short rows staged in LDS, 2 a wave per row -- the same integers.  Exact: repeated calls
+        are equal, and the h of several engines over the same tables (chains sharded over ranks) add."""
+        torch = _torch()
+        n_iter, size, idx, n = self._selection(store, index)
+        lo_t, hi_t = self._f64(lo), self._f64(hi)
+        pos_t = self._int64(pos, "pos", empty_ok=False)
+        if lo_t.dim() == 1:
+            lo_t = lo_t.unsqueeze(0)
+        if hi_t.dim() == 1:
+            hi_t = hi_t.unsqueeze(0)
+        if pos_t.dim() == 1:
+            pos_t = pos_t.unsqueeze(0)
+        L = lo_t.shape[0]
+        if lo_t.dim() != 2 or not (tuple(lo_t.shape) == tuple(hi_t.shape) == tuple(pos_t.shape) == (L, n)):
+            raise ValueError(f"lo, hi and pos must be ({n},) or (L, {n}), one value per selected element and slot, all of one shape")
+        if not 1 <= L <= 8:
+            raise ValueError("between 1 and 8 slots")
+        if int(pos_t.min()) < 0 or int(pos_t.max()) >= n:  # (before the cast to int32; the library checks its table again)
+            raise ValueError(f"pos must lie in [0, {n})")
+        pos_t = pos_t.to(torch.int32).contiguous()
+        h = self.empty((L, n + 1), dtype=torch.int64)
+        r = self.empty((L, n_iter, self.n_chains), dtype=torch.int32) if want_rows else None
+        self._check_text(lib.omc_store_first_failure(
+            self._ctx, n_iter, size, self._p(store), _ptr(idx), n, L, self._p(lo_t), self._p(hi_t), pos_t.data_ptr(), int(algo),
+            h.data_ptr(), _ptr(r)))
+        return h, r
+
     def store_autocorr(self, store, max_lag, index=None, pooled=True, normalize=True):
         """Autocorrelation of every selected element of a device store (n_iter, C, size), on the device (omc_store_autocorr):
         (acf, tau, window, mean) as device tensors.  acf is fp64 (n_idx, max_lag + 1) pooled -- the chains' autocovariances
