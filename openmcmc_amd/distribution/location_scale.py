@@ -6,7 +6,7 @@ exposes that view to the samplers; log_p evaluates it with omc_tridiag_quadform 
 omc_scaled_gauss_logpdf.
 """
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Union
 
 import numpy as np
@@ -14,6 +14,7 @@ from scipy import sparse
 
 from openmcmc_amd.chains import is_chain
 from openmcmc_amd.distribution.distribution import Distribution
+from openmcmc_amd.memo import by_identity
 from openmcmc_amd.parameter import (Identity, LinearCombination, LinearCombinationWithTransform, MixtureParameterMatrix, MixtureParameterVector,
                                      ScaledMatrix, _is_identity)
 
@@ -84,12 +85,26 @@ class NormalStructure:
     off: object
     n_pos: int              # #{diag(M) > 0}  (sampler.py:283)
     band: object = None     # (w+1, n) band storage when M is banded but wider than tridiagonal, else None
+    # The structure class, worked out once from the fields above; every caller asks these, none the sentinels:
+    kind: str = field(init=False)            # "identity", "diagonal", "tridiagonal", "band" or "dense" (too wide for band storage)
+    narrow: bool = field(init=False)         # identity, diagonal or tridiagonal: diag / off hold M (the tridiagonal kernels)
+    diagonal_only: bool = field(init=False)  # identity or diagonal: the elements of the residual are uncorrelated
+
+    def __post_init__(self):
+        if self.diag is False:
+            self.kind = "dense" if self.band is None else "band"
+        elif self.off is not None:
+            self.kind = "tridiagonal"
+        else:
+            self.kind = "identity" if self.diag is None else "diagonal"
+        self.narrow = self.kind in ("identity", "diagonal", "tridiagonal")
+        self.diagonal_only = self.kind in ("identity", "diagonal")
 
     def band_rows(self):
         """Band storage of M whatever its structure class (identity -> None = the kernels' identity)."""
-        if self.diag is False:
+        if not self.narrow:
             return self.band
-        if self.diag is None and self.off is None:
+        if self.kind == "identity":
             return None
         diag = np.ones(self.n) if self.diag is None else self.diag
         if self.off is None:
@@ -161,20 +176,19 @@ class Normal(Distribution):
             M, scale_key = state[self.precision.form], None
         if is_chain(M):
             raise NotImplementedError("per-chain precision matrices")
-        memo = self.__dict__.setdefault("_structure_memo", {})
-        hit = memo.get(id(M))
-        if hit is not None and hit.matrix is M and hit.scale_key == scale_key:
-            return hit  # shared matrices are immutable: the band extraction is done once, not every log_p
-        if M.shape[0] != M.shape[1]:
-            raise ValueError("Matrix is not square")
-        n = M.shape[0]
-        bands = tridiagonal_bands(M, n)
-        diag, off = bands if bands is not None else (False, False)  # False = not tridiagonal
-        d = M.diagonal() if sparse.issparse(M) else np.diag(np.asarray(M))
-        st = NormalStructure(n=n, matrix=M, scale_key=scale_key, diag=diag, off=off, n_pos=int(np.sum(d > 0)),
-                             band=band_storage(M, n) if bands is None else None)
-        memo[id(M)] = st
-        return st
+
+        def make():
+            if M.shape[0] != M.shape[1]:
+                raise ValueError("Matrix is not square")
+            n = M.shape[0]
+            bands = tridiagonal_bands(M, n)
+            diag, off = bands if bands is not None else (False, False)  # False = not tridiagonal
+            d = M.diagonal() if sparse.issparse(M) else np.diag(np.asarray(M))
+            return NormalStructure(n=n, matrix=M, scale_key=scale_key, diag=diag, off=off, n_pos=int(np.sum(d > 0)),
+                                   band=band_storage(M, n) if bands is None else None)
+
+        # shared matrices are immutable: the band extraction is done once per (matrix, label of the scalar), not every log_p
+        return by_identity(self.__dict__.setdefault("_structure_memo", {}), make, M, scale_key)
 
     def chain_and_center(self, state):
         """(x, m): the per-chain vector and the shared vector such that the residual of the Gaussian
@@ -211,132 +225,99 @@ class Normal(Distribution):
         hit = engine.quad_cache_get(self, self.residual_inputs(state))
         if hit is not None:  # the draw that produced this state computed it (NormalNormal.sample)
             return hit
-        resp = state[self.response]
-        transformed = isinstance(self.mean, LinearCombinationWithTransform) and self.mean.is_transformed()
-        dense_design = (isinstance(self.mean, LinearCombination) and not is_chain(resp)
-                        and any(is_chain(state[k]) and (transformed or not _is_identity(state[a], state[k].shape[0]))
-                                for k, a in self.mean.form.items()))
-        rep_mult, rep_const = 1.0, 0.0
-        if dense_design and transformed and resp.shape[1] != 1 and replicates:
-            # replicated response under an exp-transformed mean (location_scale.py:236 sums the replicates): the residual form
-            # around ybar times n_rep, plus the spread of the replicates around it (_replicate_split)
-            ybar, rep_const = self._replicate_split(st, np.asarray(resp, dtype=np.float64))
-            memo = self.__dict__.setdefault("_ybar_memo", {})
-            hit = memo.get(id(resp))
-            if hit is None or hit[0] is not resp:
-                hit = memo[id(resp)] = (resp, ybar)
-            rep_mult, resp = float(resp.shape[1]), hit[1]
-        if dense_design and (st.diag is False or st.off is not None):
-            # a correlated response under a design matrix: r_c = y - fitted_c on the device, then r'Wr on W's own route
-            if resp.shape[1] != 1:
-                raise NotImplementedError("replicated responses")
-            frozen = getattr(self.mean, "_frozen", None)
-            fitted = self.mean.predictor_device(state, engine)
-            r = engine.chain_lincomb(-1.0, fitted, 1.0, engine.shared(resp).reshape(-1))
-            if rep_mult != 1.0:
-                if st.diag is False and st.band is None:
-                    return engine.dense_quadform(engine.shared(st.matrix), r) * rep_mult + rep_const
-                raise NotImplementedError("replicated responses under a banded precision and a transformed mean")
-            if st.diag is False and st.band is None:
-                return engine.dense_quadform(engine.shared(st.matrix), r)
-            quad = engine.empty(engine.n_chains)
-            if st.diag is False:
-                engine.band_quadform(st.n, engine.band_cache(self, st, np.zeros((st.n, 1)))["band"], r, quad)
-                return quad
-            cache = engine.model_cache(self, state, st, np.zeros((st.n, 1)))
-            q2 = engine.empty(1, engine.n_chains)
-            engine.tridiag_quadform(st.n, cache["terms_unit"], r, q2)
-            return q2[0]
-        if dense_design:
-            if resp.shape[1] != 1:
-                raise NotImplementedError("replicated responses")
+        of, x, center, mult, const = self._residual_form(state, engine, st, replicates)
+        if of == "regression":
+            # uncorrelated observations under a design matrix: sum_i w_i (y_i - fitted_i)^2 is a kernel of its own, not a
+            # quadratic form of a vector
+            y = engine.shared(x).reshape(-1)
             w = None if st.diag is None else engine.shared(st.diag)
             frozen = getattr(self.mean, "_frozen", None)
+            quad = None
             if not (frozen and "fitted" in frozen):  # (fitted values at hand for this state: the residual is one pass over them)
-                quad = self.mean.resid_sq_device(state, engine, engine.shared(resp).reshape(-1), w)
-                if quad is not None:
-                    return quad
-            fitted = self.mean.predictor_device(state, engine)
-            quad = engine.empty(engine.n_chains)
-            engine.weighted_resid_sq(engine.shared(resp).reshape(-1), fitted, quad, w=w)
-            return quad if rep_mult == 1.0 else quad * rep_mult + rep_const
-        if st.diag is False and st.band is None:
-            # dense shared precision: r'Mr through one GEMM over all chains
-            x, m = self.chain_and_center(state)
-            if x.shape[1] != 1:
-                raise NotImplementedError("replicated per-chain side of a Normal")
-            if is_chain(m):  # both sides sampled: the residual is formed on the device
-                if m.shape[1] != 1:
-                    raise NotImplementedError("replicated per-chain side of a Normal")
-                r = engine.chain_lincomb(1.0, x.vector(), -1.0, m.vector())
-                return engine.dense_quadform(engine.shared(st.matrix), r)
-            n_rep, const = m.shape[1], 0.0
-            if n_rep != 1:
-                if not replicates:
-                    raise NotImplementedError("replicated responses")
-                m, const = self._replicate_split(st, m)
-            memo = self.__dict__.setdefault("_dense_memo", {})
-            key = id(st.matrix)
-            c_host = np.ascontiguousarray(m, dtype=np.float64).reshape(-1)
-            hit = memo.get(key)
-            if hit is None or not np.array_equal(hit[0], c_host):
-                Mm = np.asarray(st.matrix @ c_host).reshape(-1)
-                hit = memo[key] = (c_host, engine.to_device(c_host) if c_host.any() else None,
-                                   engine.to_device(Mm) if c_host.any() else None)
-            quad = engine.dense_quadform(engine.shared(st.matrix), x.vector(), center=hit[1], M_center=hit[2])
-            return quad if n_rep == 1 else quad * float(n_rep) + const
-        if st.diag is False:
-            x, m = self.chain_and_center(state)
-            if x.shape[1] != 1:
-                raise NotImplementedError("replicated per-chain side of a Normal")
-            if is_chain(m):  # both sides sampled
-                if m.shape[1] != 1:
-                    raise NotImplementedError("replicated per-chain side of a Normal")
-                r = engine.chain_lincomb(1.0, x.vector(), -1.0, m.vector())
-                cache = engine.band_cache(self, st, np.zeros((st.n, 1)))
+                quad = self.mean.resid_sq_device(state, engine, y, w)
+            if quad is None:
+                fitted = self.mean.predictor_device(state, engine)
                 quad = engine.empty(engine.n_chains)
-                engine.band_quadform(st.n, cache["band"], r, quad)
-                return quad
-            n_rep, const = m.shape[1], 0.0
-            if n_rep != 1:
-                if not replicates:
-                    raise NotImplementedError("replicated responses")
-                m, const = self._replicate_split(st, m)
-            cache = engine.band_cache(self, st, m)
-            quad = engine.empty(engine.n_chains)
-            engine.band_quadform(st.n, cache["band"], x.vector(), quad, center=cache["center"])
-            return quad if n_rep == 1 else quad * float(n_rep) + const
-        x, m = self.chain_and_center(state)
-        if x.shape[1] != 1:
-            raise NotImplementedError("replicated per-chain side of a Normal")
-        if is_chain(m):
-            # both sides per chain (a sampled mean under a sampled response): r_c = x_c - m_c on the device, then r'Mr
-            if m.shape[1] != 1:
+                engine.weighted_resid_sq(y, fitted, quad, w=w)
+        else:
+            quad = self._form_quad(engine, st, of, x, center)
+        return quad if mult == 1.0 else quad * mult + const
+
+    def _residual_form(self, state, engine, st, replicates):
+        """What the statistic is taken of, (of, x, center, mult, const) with r'Mr = mult * (x - center)'M(x - center) + const
+        and `of` one of
+          "shared"      x (C, n) the per-chain side, center the shared side m as a host vector (mult, const: _replicate_split
+                        of a replicated m);
+          "per_chain"   both sides sampled: x and center (C, n) device tensors, the residual is formed on the device;
+          "residual"    x is the residual already, center None: a correlated response under a design matrix, y - fitted_c
+                        made here;
+          "regression"  uncorrelated observations under a design matrix: x is the shared response y (host) and center None;
+                        the statistic is not a form of a vector (residual_quad's own arm).
+        Nothing here depends on the route M takes but what is refused."""
+        resp = state[self.response]
+        transformed = isinstance(self.mean, LinearCombinationWithTransform) and self.mean.is_transformed()
+        design = (isinstance(self.mean, LinearCombination) and not is_chain(resp)
+                  and any(is_chain(state[k]) and (transformed or not _is_identity(state[a], state[k].shape[0]))
+                          for k, a in self.mean.form.items()))
+        if design:
+            # (an exp-transformed mean sums the replicates, location_scale.py:236; any other design takes one column)
+            m, splits = resp, transformed and replicates
+        else:
+            x, m = self.chain_and_center(state)
+            if x.shape[1] != 1:
                 raise NotImplementedError("replicated per-chain side of a Normal")
-            cache = engine.model_cache(self, state, st, np.zeros((st.n, 1)))
-            quad = engine.empty(1, engine.n_chains)
-            mv = m.vector()
-            if mv.stride(1) == 1:  # one launch: the quadratic form around the chain's own centre
-                engine.set_center_chain(cache["terms_unit"], [mv], st.n)
-                try:
-                    engine.tridiag_quadform(st.n, cache["terms_unit"], x.vector(), quad)
-                finally:
-                    engine.set_center_chain(cache["terms_unit"], [None], st.n)
-            else:
-                r = engine.chain_lincomb(1.0, x.vector(), -1.0, mv)
-                engine.tridiag_quadform(st.n, cache["terms_unit"], r, quad)
-            return quad[0]
-        n_rep = m.shape[1]
-        if n_rep != 1 and not replicates:
-            # NormalGamma's b* = r'Pr is a scalar only for one replicate (the reference's .item() raises, sampler.py:284)
+            if is_chain(m):  # a sampled mean under a sampled response
+                if m.shape[1] != 1:
+                    raise NotImplementedError("replicated per-chain side of a Normal")
+                return "per_chain", x.vector(), m.vector(), 1.0, 0.0
+            if m.shape[1] != 1 and not replicates:
+                # NormalGamma's b* = r'Pr is a scalar only for one replicate (the reference's .item() raises, sampler.py:284)
+                raise NotImplementedError("replicated responses")
+            splits = True
+        mult, const = 1.0, 0.0
+        if m.shape[1] != 1 and splits:
+            mult = float(m.shape[1])
+            ybar, const = self._replicate_split(st, np.asarray(m, dtype=np.float64))
+            # (under a design the device copy of ybar is kept by identity, engine.shared: one object per response)
+            m = by_identity(self.__dict__.setdefault("_ybar_memo", {}), lambda: ybar, m) if design else ybar
+        if not design:
+            return "shared", x.vector(), m, mult, const
+        if m.shape[1] != 1:
             raise NotImplementedError("replicated responses")
-        const = 0.0
-        if n_rep != 1:
-            m, const = self._replicate_split(st, m)
-        cache = engine.model_cache(self, state, st, m)
-        quad = engine.empty(1, engine.n_chains)
-        engine.tridiag_quadform(st.n, cache["terms_unit"], x.vector(), quad)
-        return quad[0] if n_rep == 1 else quad[0] * float(n_rep) + const
+        if st.diagonal_only:
+            return "regression", m, None, mult, const
+        r = engine.chain_lincomb(-1.0, self.mean.predictor_device(state, engine), 1.0, engine.shared(m).reshape(-1))
+        if mult != 1.0 and st.kind != "dense":
+            raise NotImplementedError("replicated responses under a banded precision and a transformed mean")
+        return "residual", r, None, mult, const
+
+    def _form_quad(self, engine, st, of, x, center):
+        """(C,) tensor (x - center)'M(x - center) of a form of _residual_form, on the route of M's structure class.  The shared
+        pieces come from the engine's model cache; a per-chain centre goes into the launch where the route takes one
+        (tridiagonal, unit inner stride) and is subtracted by a launch of its own elsewhere."""
+        per_chain = of == "per_chain"
+        m = center if of == "shared" else np.zeros((st.n, 1))
+        if st.narrow:
+            terms = engine.model_cache(self, st, m, "narrow")["terms_unit"]
+            quad = engine.empty(1, engine.n_chains)
+            if per_chain and center.stride(1) == 1:  # one launch: the quadratic form around the chain's own centre
+                engine.set_center_chain(terms, [center], st.n)
+                try:
+                    engine.tridiag_quadform(st.n, terms, x, quad)
+                finally:
+                    engine.set_center_chain(terms, [None], st.n)
+            else:
+                engine.tridiag_quadform(st.n, terms, engine.chain_lincomb(1.0, x, -1.0, center) if per_chain else x, quad)
+            return quad[0]
+        if per_chain:
+            x = engine.chain_lincomb(1.0, x, -1.0, center)
+        if st.kind == "dense":  # r'Mr through one GEMM over all chains
+            dense = engine.model_cache(self, st, m, "dense")
+            return engine.dense_quadform(dense["mat"], x, center=dense["center"], M_center=dense["M_center"])
+        band = engine.model_cache(self, st, m, "band")
+        quad = engine.empty(engine.n_chains)
+        engine.band_quadform(st.n, band["band"], x, quad, center=band["center"])
+        return quad
 
     # ------------------------------------------------------------------ log density
     def log_p(self, state: dict, by_observation: bool = False, engine=None, out=None, accumulate=False):
@@ -444,15 +425,15 @@ class Normal(Distribution):
         if self.is_mixture:
             raise NotImplementedError("by_observation of a mixture Normal")
         st = self.structure(state)
-        memo = self.__dict__.setdefault("_byobs_memo", {})
-        hit = memo.get(id(st.matrix))
-        if hit is None or hit[0] is not st.matrix:
+
+        def make():
             Md = st.matrix.toarray() if sparse.issparse(st.matrix) else np.array(st.matrix, dtype=np.float64, ndmin=2)
             sign, logdet = np.linalg.slogdet(Md)
             if sign <= 0:
                 raise np.linalg.LinAlgError("Matrix is not positive definite")  # gmrf.py:518 through the Cholesky factor
-            hit = memo[id(st.matrix)] = (st.matrix, engine.to_device(Md), float(logdet))
-        Md, logdetM = hit[1], hit[2]
+            return engine.to_device(Md), float(logdet)
+
+        Md, logdetM = by_identity(self.__dict__.setdefault("_byobs_memo", {}), make, st.matrix)
         resp = state[self.response] if values is None else values
         d = st.n
         X = resp.data if is_chain(resp) else engine.to_device(np.asarray(resp, dtype=np.float64).reshape(d, -1)).unsqueeze(0)
@@ -485,15 +466,14 @@ class Normal(Distribution):
         if is_chain(mean):
             raise NotImplementedError("replicate columns need a shared mean")
         Q = state[self.precision.form]
-        memo = self.__dict__.setdefault("_columns_memo", {})
-        hit = memo.get(id(Q))
-        if hit is None or hit[0] is not Q:
+
+        def make():
             Qd = Q.toarray() if sparse.issparse(Q) else np.array(Q, dtype=np.float64, ndmin=2)
             L = np.linalg.cholesky(Qd)
-            hit = memo[id(Q)] = (Q, engine.to_device(Qd), 2.0 * float(np.sum(np.log(np.diag(L)))),
-                                 engine.to_device(np.linalg.inv(L)))
-        mu = engine.to_device(np.asarray(mean, dtype=np.float64).reshape(-1).copy())
-        return mu, hit[1], hit[2], hit[3]
+            return engine.to_device(Qd), 2.0 * float(np.sum(np.log(np.diag(L)))), engine.to_device(np.linalg.inv(L))
+
+        Qd, logdet, Linv = by_identity(self.__dict__.setdefault("_columns_memo", {}), make, Q)
+        return engine.to_device(np.asarray(mean, dtype=np.float64).reshape(-1).copy()), Qd, logdet, Linv
 
     def _columns_values(self, state, engine):
         """(C, d, kmax) values the Gaussian density is evaluated at, the live-column mask and what is subtracted per live column
@@ -608,12 +588,12 @@ class Normal(Distribution):
             sv = state[st.scale_key]
             scale = sv.scalar() if is_chain(sv) else engine.full((engine.n_chains,), float(np.asarray(sv).item()))
         x = engine.empty(engine.n_chains, st.n)
-        if st.diag is False:  # dense precision: x = Q^-1 (Q mean) + L^-T z
+        if not st.narrow:  # band or dense precision, on the dense route: x = Q^-1 (Q mean) + L^-T z
             M = engine.shared(st.matrix)
             rhs = engine.design_rhs(M, engine.to_device(mean)) if mean.any() else None
             engine.dense_sample_canonical(st.n, [{"mat": M, "rhs": rhs, "scale": scale}], x, z=z, draw_index=draw_index)
         else:
-            cache = engine.model_cache(self, state, st, mean)
+            cache = engine.model_cache(self, st, mean, "narrow")
             engine.tridiag_sample_canonical(st.n, [{"diag": cache["diag"], "off": cache["off"], "rhs": cache["rhs"],
                                                     "scale": scale}], x, z=z, draw_index=draw_index)
         return x
@@ -702,7 +682,7 @@ class Normal(Distribution):
         in_mean = param in self.mean.get_grad_param_list() and param not in self.precision.get_grad_param_list()
         if in_mean and param != self.response and is_chain(x) and not self.is_mixture:
             st = self.structure(state)
-            general_w = st.diag is False or st.off is not None  # a correlated response: W r through (W A)' (location_scale.py:234-242 with any Q)
+            general_w = not st.diagonal_only  # a correlated response: W r through (W A)' (location_scale.py:234-242 with any Q)
             resp = state[self.response]
             if is_chain(resp) or x.shape[1] != 1:
                 raise NotImplementedError("gradient through the mean needs a shared response and a (p, 1) parameter")
@@ -715,30 +695,30 @@ class Normal(Distribution):
             ysum = engine.to_device(np.asarray(resp, dtype=np.float64).sum(axis=1).reshape(1, -1))
             r = (ysum - float(n_rep) * fitted) * engine.to_device(w.reshape(1, -1))   # W sum_rep (y - fitted) (W applied below if general)
             memo = self.__dict__.setdefault("_grad_memo", {})
+
+            def general():  # ((W A)' on the device, H) of this design under this matrix
+                Wh = st.matrix
+                if A is None:
+                    WA = Wh.toarray() if sparse.issparse(Wh) else np.asarray(Wh, dtype=np.float64)  # G = I: g = W r, H = n_rep W
+                    Hh = float(n_rep) * WA
+                else:
+                    Ad = A.toarray() if sparse.issparse(A) else np.asarray(A, dtype=np.float64)
+                    WA = np.asarray(Wh @ Ad, dtype=np.float64)
+                    Hh = float(n_rep) * (Ad.T @ WA)
+                return engine.to_device(np.ascontiguousarray(WA.T)), Hh
+
+            def weighted():  # (A' on the device, H) of this design under the diagonal w
+                Ad = A.toarray() if sparse.issparse(A) else np.asarray(A, dtype=np.float64)
+                return engine.to_device(np.ascontiguousarray(Ad.T)), float(n_rep) * (Ad.T * w) @ Ad
+
             if general_w:
-                key = ("general", id(A), id(st.matrix))
-                hit = memo.get(key)
-                if hit is None or hit[0] is not A:
-                    Wh = st.matrix
-                    if A is None:
-                        WA = Wh.toarray() if sparse.issparse(Wh) else np.asarray(Wh, dtype=np.float64)  # G = I: g = W r, H = n_rep W
-                        Hh = float(n_rep) * WA
-                    else:
-                        Ad = A.toarray() if sparse.issparse(A) else np.asarray(A, dtype=np.float64)
-                        WA = np.asarray(Wh @ Ad, dtype=np.float64)
-                        Hh = float(n_rep) * (Ad.T @ WA)
-                    hit = memo[key] = (A, engine.to_device(np.ascontiguousarray(WA.T)), Hh)
-                g = engine.design_predict(hit[1], r.contiguous())  # (W A)' r_c for every chain: (C, p)
-                H = hit[2]
+                op, H = by_identity(memo, general, A, st.matrix)
+                g = engine.design_predict(op, r.contiguous())  # (W A)' r_c for every chain: (C, p)
             elif A is None:
                 g, H = r, (sparse.diags(w) * float(n_rep)).tocsc()
             else:
-                hit = memo.get(id(A))
-                if hit is None or hit[0] is not A:
-                    Ad = A.toarray() if sparse.issparse(A) else np.asarray(A, dtype=np.float64)
-                    hit = memo[id(A)] = (A, engine.to_device(np.ascontiguousarray(Ad.T)), float(n_rep) * (Ad.T * w) @ Ad)
-                g = engine.design_predict(hit[1], r.contiguous())  # rows of r times A: (C, p)
-                H = hit[2]
+                op, H = by_identity(memo, weighted, A)
+                g = engine.design_predict(op, r.contiguous())  # rows of r times A: (C, p)
             scale = state[st.scale_key].scalar() if st.scale_key is not None else None
             if self._transformed_param(param):
                 # parameter.py:281-297 in location_scale.py:237-241: the rows of the mean's gradient carry s_c = exp(x_c), so
@@ -826,12 +806,12 @@ class LogNormal(Normal):
             lx, sumlog = engine.log_transform(resp.vector())
             logged[self.response] = ChainArray(lx)
         else:
-            memo = self.__dict__.setdefault("_log_memo", {})
-            hit = memo.get(id(resp))
-            if hit is None or hit[0] is not resp:
+
+            def make():
                 arr = np.asarray(resp, dtype=np.float64)
-                hit = memo[id(resp)] = (resp, np.log(arr), float(np.sum(np.log(arr))))
-            logged[self.response], sumlog = hit[1], hit[2]
+                return np.log(arr), float(np.sum(np.log(arr)))
+
+            logged[self.response], sumlog = by_identity(self.__dict__.setdefault("_log_memo", {}), make, resp)
         out = Normal.log_p(self, logged, engine=engine, out=out, accumulate=accumulate)
         out -= sumlog
         return out

@@ -12,6 +12,7 @@ import numpy as np
 from openmcmc_amd import _abi
 from openmcmc_amd._abi import check, lib
 from openmcmc_amd.engine_store import StoreOps, _torch
+from openmcmc_amd.memo import by_identity
 
 _TORCH = None  # torch, from the first Engine on: what _p compares a dtype with, without a call
 
@@ -40,7 +41,7 @@ class Engine(StoreOps):
         self._write_serial = 0
         self._written = {}
         # per-model constants and the quadratic forms a draw left behind, filled on demand
-        self._quad_cache, self._logdet_cache, self._shared_cache, self._band_cache, self._model_cache = {}, {}, {}, {}, {}
+        self._quad_cache, self._logdet_cache, self._shared_cache, self._model_cache = {}, {}, {}, {}
 
     # ------------------------------------------------------------------ memory helpers
     def empty(self, *shape, dtype=None):
@@ -493,67 +494,60 @@ class Engine(StoreOps):
 
     # ------------------------------------------------------------------ per-model constants
     def matrix_logdet(self, st):
-        """Device scalar log det M of a Normal's unscaled precision (tridiagonal bands), cached."""
-        hit = self._logdet_cache.get(id(st.matrix))
-        if hit is not None and hit[0] is st.matrix:
-            return hit[1]
-        if st.diag is False and st.band is None:
-            # dense: one Cholesky of M itself (gmrf.py:339: 2 sum log L_ii)
-            _, sumlog = self.dense_cholesky(self.shared(st.matrix), 1.0)
-            ld = sumlog * 2.0
-        elif st.diag is False:
-            # banded: one factorisation of M itself on the device (every chain computes the same number)
-            x, out = self.empty(self.n_chains, st.n), self.empty(self.n_chains)
-            self.band_sample_canonical(st.n, [{"band": self.to_device(st.band)}], x, logdet_out=out)
-            ld = out[:1].clone()
-        elif st.diag is None and st.off is None:
-            ld = self.zeros(1)
-        else:
+        """Device scalar log det M of a Normal's unscaled precision, on the route of its structure class, cached."""
+        def make():
+            if st.kind == "dense":
+                # one Cholesky of M itself (gmrf.py:339: 2 sum log L_ii)
+                _, sumlog = self.dense_cholesky(self.shared(st.matrix), 1.0)
+                return sumlog * 2.0
+            if st.kind == "band":
+                # one factorisation of M itself on the device (every chain computes the same number)
+                x, out = self.empty(self.n_chains, st.n), self.empty(self.n_chains)
+                self.band_sample_canonical(st.n, [{"band": self.to_device(st.band)}], x, logdet_out=out)
+                return out[:1].clone()
+            if st.kind == "identity":
+                return self.zeros(1)
             diag = self.to_device(st.diag) if st.diag is not None else self.full((st.n,), 1.0)
-            ld = self.tridiag_logdet(st.n, diag, None if st.off is None else self.to_device(st.off))
-        self._logdet_cache[id(st.matrix)] = (st.matrix, ld)
-        return ld
+            return self.tridiag_logdet(st.n, diag, None if st.off is None else self.to_device(st.off))
+
+        return by_identity(self._logdet_cache, make, st.matrix)
 
     def shared(self, array):
         """Device copy of a shared host array (dense or scipy.sparse -> dense), cached by identity."""
-        from scipy import sparse
+        def make():
+            from scipy import sparse
 
-        hit = self._shared_cache.get(id(array))
-        if hit is not None and hit[0] is array:
-            return hit[1]
-        dense = array.toarray() if sparse.issparse(array) else np.asarray(array, dtype=np.float64)
-        t = self.to_device(np.ascontiguousarray(dense, dtype=np.float64))
-        self._shared_cache[id(array)] = (array, t)
-        return t
+            dense = array.toarray() if sparse.issparse(array) else np.asarray(array, dtype=np.float64)
+            return self.to_device(np.ascontiguousarray(dense, dtype=np.float64))
 
-    def band_cache(self, dist, st, center):
-        """Device copies of a banded Normal's shared pieces: band rows of M, the vector m its residual is taken around
-        and M m (host product, once per model)."""
+        return by_identity(self._shared_cache, make, array)
+
+    def model_cache(self, dist, st, center, part):
+        """Device copies of one Normal's shared pieces (M of structure `st`, the vector m its residual is taken around, M m):
+        one entry per (distribution, matrix), reused every sweep.  The entry has a part per route, each a dict made the first
+        time it is asked for, so that its set-up launches come where its first user stands, and made again only when it is
+        asked for around another vector (the other parts stay):
+          "narrow"  diag, off (None, None: the identity), center, rhs = M m by a launch, logdet, and terms_unit, the one
+                    unscaled term omc_tridiag_quadform takes -- of a narrow structure;
+          "band"    band (the rows of st.band_rows(); None: the identity), center, rhs = M m (host product);
+          "dense"   mat = M on the device, center, M_center = M m (host product)."""
         key = (id(dist), id(st.matrix))
-        c_host = np.ascontiguousarray(center, dtype=np.float64).reshape(-1)
-        hit = self._band_cache.get(key)
-        if hit is not None and np.array_equal(hit["center_host"], c_host):
-            return hit
-        rows = st.band_rows()
-        entry = {"band": None if rows is None else self.to_device(rows), "center_host": c_host,
-                 "center": self.to_device(c_host) if c_host.any() else None,
-                 "rhs": self.to_device(np.asarray(st.matrix @ c_host).reshape(-1)) if c_host.any() else None}
-        self._band_cache[key] = entry
-        return entry
-
-    def model_cache(self, dist, state, st, center):
-        """Device copies of one Normal's shared pieces (bands of M, the vector m its residual is taken
-        around, M m, log det M), built once per (distribution, matrix, vector) and reused every sweep."""
-        key = (id(dist), id(st.matrix))
-        hit = self._model_cache.get(key)
+        entry = self._model_cache.get(key)
         c_host = np.ascontiguousarray(center, dtype=np.float64).reshape(-1)
         # ids can be recycled after garbage collection: the entry keeps the objects and is checked by identity
-        if hit is not None and hit["dist"] is dist and hit["matrix"] is st.matrix and np.array_equal(hit["center_host"], c_host):
-            return hit
+        if entry is None or entry["dist"] is not dist or entry["matrix"] is not st.matrix:
+            entry = self._model_cache[key] = {"dist": dist, "matrix": st.matrix}
+        hit = entry.get(part)
+        if hit is None or not np.array_equal(hit[0], c_host):
+            cvec = self.to_device(c_host) if c_host.any() else None
+            build = {"narrow": self._narrow_pieces, "band": self._band_pieces, "dense": self._dense_pieces}[part]
+            hit = entry[part] = (c_host, build(st, c_host, cvec))
+        return hit[1]
+
+    def _narrow_pieces(self, st, c_host, cvec):
         n = st.n
         diag = None if st.diag is None else self.to_device(st.diag)
         off = None if st.off is None else self.to_device(st.off)
-        cvec = self.to_device(c_host) if c_host.any() else None
         if cvec is None:
             rhs = None
         elif diag is None and off is None:
@@ -561,11 +555,17 @@ class Engine(StoreOps):
         else:
             rhs = self.tridiag_matvec(n, diag, off, cvec)
         logdet = self.zeros(1) if (diag is None and off is None) else self.tridiag_logdet(n, diag, off)
-        entry = {"dist": dist, "matrix": st.matrix, "diag": diag, "off": off, "center": cvec, "rhs": rhs, "logdet": logdet,
-                 "center_host": c_host,
-                 "terms_unit": self.tridiag_terms([{"diag": diag, "off": off, "center": cvec}], n)}
-        self._model_cache[key] = entry
-        return entry
+        return {"diag": diag, "off": off, "center": cvec, "rhs": rhs, "logdet": logdet,
+                "terms_unit": self.tridiag_terms([{"diag": diag, "off": off, "center": cvec}], n)}
+
+    def _band_pieces(self, st, c_host, cvec):
+        rows = st.band_rows()
+        return {"band": None if rows is None else self.to_device(rows), "center": cvec,
+                "rhs": None if cvec is None else self.to_device(np.asarray(st.matrix @ c_host).reshape(-1))}
+
+    def _dense_pieces(self, st, c_host, cvec):
+        return {"mat": self.shared(st.matrix), "center": cvec,
+                "M_center": None if cvec is None else self.to_device(np.asarray(st.matrix @ c_host).reshape(-1))}
 
     # ------------------------------------------------------------------ scalars
     def normal_gamma_update(self, a0, b0, n_pos, quad, out, g=None, draw_index=0):

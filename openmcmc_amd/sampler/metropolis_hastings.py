@@ -442,7 +442,7 @@ class RandomWalkLoop(RandomWalk):
         if coef is None:
             return None
         st = lik.structure(state)
-        if st.diag is False or st.off is not None or (st.scale_key is not None and not is_chain(state[st.scale_key])):
+        if not st.diagonal_only or (st.scale_key is not None and not is_chain(state[st.scale_key])):
             return None
         eng = self._need_engine()
         return {"basis": basis, "x": x, "B": Bm, "coef": coef, "offset": offset, "lower": lower, "upper": upper,

@@ -16,6 +16,7 @@ import numpy as np
 
 from openmcmc_amd.chains import ChainArray, is_chain
 from openmcmc_amd.distribution.location_scale import Normal
+from openmcmc_amd.memo import by_identity
 from openmcmc_amd.model import Model
 from openmcmc_amd.parameter import (Identity, LinearCombination, MixtureParameterMatrix, MixtureParameterVector,
                                      ScaledMatrix, _is_identity)
@@ -39,7 +40,7 @@ class MCMCSampler(ABC):
         self._plan = None
         self.inject = None  # test hook: callable(sampler, sweep) -> injected draws (device tensor)
         self._later_params = frozenset()  # the parameters the rest of the sweep samples after this block (MCMC sets it)
-        self._rep_structs = {}  # NormalNormal: the structures of replicated responses, by key
+        self._rep_structs = {}  # NormalNormal: the structures of replicated responses, by the structure they replicate
 
     def bind(self, engine, position=0, n_samplers=1):
         self.engine, self._position, self._n_samplers = engine, position, n_samplers
@@ -250,11 +251,11 @@ class NormalNormal(MCMCSampler):
                         # (the reference fails here too: b (p, 1) += A'W(y - d) of shape (p, n_rep), sampler.py:192)
                         raise NotImplementedError("replicated response under a LinearCombination mean")
                     y = y.mean(axis=1, keepdims=True)
-                    piece.st, piece.replicated = self._replicated_structure(key, st, n_rep), True
+                    piece.st, piece.replicated = self._replicated_structure(st, n_rep), True
                 piece.center = y - rest
             pieces.append(piece)
-        tridiagonal = all(pc.design is None and pc.st.diag is not False and pc.st.n == n for pc in pieces)
-        banded = all(pc.design is None and pc.st.n == n and (pc.st.diag is not False or pc.st.band is not None) for pc in pieces)
+        tridiagonal = all(pc.design is None and pc.st.narrow and pc.st.n == n for pc in pieces)
+        banded = all(pc.design is None and pc.st.n == n and pc.st.kind != "dense" for pc in pieces)
         if mixture_prior:
             plan = self._dense_plan(state, n, pieces, mixture_prior=prior)
         elif tridiagonal and n <= self.TRIDIAG_WG_MAX:
@@ -298,28 +299,31 @@ class NormalNormal(MCMCSampler):
             return None
         return lo, hi
 
-    def _replicated_structure(self, key, st, n_rep):
-        """The structure of n_rep * M (kept on the sampler so the device cache sees one stable matrix object)."""
+    def _replicated_structure(self, st, n_rep):
+        """The structure of n_rep * M (kept on the sampler so the device cache sees one stable matrix object): of M's own
+        kind, but that n_rep times the identity is a constant diagonal."""
         from openmcmc_amd.distribution.location_scale import NormalStructure
 
-        hit = self._rep_structs.get(key)
-        if hit is None or hit[0] is not st.matrix or hit[1].n_pos != st.n_pos:
-            r, wide = float(n_rep), st.diag is False  # wide: dense, or banded with its band rows (no tridiagonal bands)
-            diag = False if wide else (np.full(st.n, r) if st.diag is None else st.diag * r)
-            off = None if wide or st.off is None else st.off * r
-            rep = NormalStructure(n=st.n, matrix=st.matrix * r, scale_key=st.scale_key, diag=diag, off=off, n_pos=st.n_pos,
-                                  band=None if st.band is None else st.band * r)
-            hit = self._rep_structs[key] = (st.matrix, rep)
-        return hit[1]
+        def make():
+            r = float(n_rep)
+            diag = False  # band and dense: no tridiagonal bands
+            if st.narrow:
+                diag = np.full(st.n, r) if st.kind == "identity" else st.diag * r
+            return NormalStructure(n=st.n, matrix=st.matrix * r, scale_key=st.scale_key, diag=diag,
+                                   off=st.off * r if st.kind == "tridiagonal" else None, n_pos=st.n_pos,
+                                   band=st.band * r if st.kind == "band" else None)
+
+        # (keyed on the structure alone: n_pos is a property of its matrix, and n_rep is fixed with the response it belongs to)
+        return by_identity(self._rep_structs, make, st)
 
     def _tridiag_plan(self, state, n, pieces):
         eng = self.engine
         terms, caches = [], []
         for pc in pieces:
             st = pc.st
-            if pc.offset and (st.diag is not None or st.off is not None):
+            if pc.offset and st.kind != "identity":
                 raise NotImplementedError("per-chain offset under a non-identity response precision")
-            cache = eng.model_cache(pc.dist, state, st, pc.center)
+            cache = eng.model_cache(pc.dist, st, pc.center, "narrow")
             scale = _as_chain_scalar(eng, state, st.scale_key) if st.scale_key is not None else None
             terms.append({"diag": cache["diag"], "off": cache["off"], "rhs": cache["rhs"], "center": cache["center"],
                           "scale": None if scale is None else scale.scalar()})
@@ -348,7 +352,7 @@ class NormalNormal(MCMCSampler):
         if in_launch and not offsets:
             for k, pc in enumerate(pieces):
                 st = pc.st
-                if st.scale_key is None and st.off is None and st.diag is not None and pc.chain_vec is None \
+                if st.scale_key is None and st.kind == "diagonal" and pc.chain_vec is None \
                         and np.ptp(st.diag) == 0.0 and st.diag[0] > 0.0:
                     d0, cvec = float(st.diag[0]), caches[k]["center"]
                     terms[k] = {"diag": None, "off": None, "rhs": cvec, "center": cvec, "scale": eng.full((eng.n_chains,), d0)}
@@ -369,7 +373,7 @@ class NormalNormal(MCMCSampler):
             if not isinstance(dist, Normal) or not isinstance(dist.mean, LinearCombination):
                 raise NotImplementedError("ragged NormalNormal needs LinearCombination likelihood means")
             st = dist.structure(state)
-            if st.diag is False or st.off is not None:
+            if not st.diagonal_only:
                 raise NotImplementedError("regression likelihood needs a diagonal response precision")
             if not is_chain(state[dist.mean.form[self.param]]):
                 raise NotImplementedError("ragged parameter with a shared design matrix")
@@ -387,7 +391,7 @@ class NormalNormal(MCMCSampler):
         terms, chain_terms = [], []
         for pc in pieces:
             st = pc.st
-            cache = eng.band_cache(pc.dist, st, pc.center)
+            cache = eng.model_cache(pc.dist, st, pc.center, "band")
             scale = _as_chain_scalar(eng, state, st.scale_key) if st.scale_key is not None else None
             rhs = cache["rhs"] if cache["rhs"] is not None else cache["center"]  # (identity matrix: M m = m)
             terms.append({"band": cache["band"], "rhs": rhs, "scale": None if scale is None else scale.scalar()})
@@ -398,8 +402,8 @@ class NormalNormal(MCMCSampler):
         # quadratic forms (x - m_k)' M_k (x - m_k) are the residual statistics NormalGamma and log_p ask for right after the
         # draw: ONE launch over x for all terms (omc_tridiag_quadform) behind the draw, cached like the fused forms of the
         # workgroup-per-chain kernel -- instead of one pass per distribution and caller (3.3 per sweep at n = 20 000).
-        if all(pc.st.diag is not False and not pc.offset and pc.chain_vec is None and not pc.replicated for pc in pieces):
-            caches = [eng.model_cache(pc.dist, state, pc.st, pc.center) for pc in pieces]
+        if all(pc.st.narrow and not pc.offset and pc.chain_vec is None and not pc.replicated for pc in pieces):
+            caches = [eng.model_cache(pc.dist, pc.st, pc.center, "narrow") for pc in pieces]
             plan.quad_terms = eng.tridiag_terms([{"diag": c["diag"], "off": c["off"], "center": c["center"]} for c in caches], n)
             plan.quad_ok, plan.quad_factor = [True] * len(pieces), [1.0] * len(pieces)
         return plan
@@ -416,10 +420,10 @@ class NormalNormal(MCMCSampler):
             if A is None:
                 if st.n != n:
                     raise ValueError("precision / parameter size mismatch")
-                mat = None if (st.diag is None and st.off is None) else eng.shared(st.matrix)
+                mat = None if st.kind == "identity" else eng.shared(st.matrix)
                 rhs = center if mat is None else eng.design_rhs(mat, center)  # M' m = M m, once per model
                 op = mat
-            elif st.diag is False or st.off is not None:
+            elif not st.diagonal_only:
                 # a correlated response (tridiagonal, banded or dense W, any symmetric matrix the reference accepts:
                 # sampler.py:185-192 forms A'QA and A'Q(y - d) with whatever Q is): W A once per model on the host (a band or
                 # sparse product), then the same contraction as the diagonal case, A'(W A), on the device

@@ -252,6 +252,81 @@ def test_null_distribution_and_band_recognition():
         band_storage(sparse.csc_matrix(np.triu(np.ones((8, 8)), 0) * (np.abs(np.subtract.outer(np.arange(8), np.arange(8))) <= 2)), 8)
 
 
+def _structure_matrices():
+    """(name, matrix as an ndarray, the kind it has): one matrix per structure class, and a band too wide to pay"""
+    def rw(n, order):
+        D = np.diff(np.eye(n), order, axis=0)
+        return D.T @ D + 1e-2 * np.eye(n)
+
+    A = np.random.default_rng(7).standard_normal((9, 5))
+    return [("identity", np.eye(5), "identity"), ("diagonal", np.diag([1.0, 2.0, 0.5, 1.0, 3.0]), "diagonal"),
+            ("rw1", rw(5, 1), "tridiagonal"), ("rw2_n12", rw(12, 2), "band"),  # (w + 1) * 2 = 6 <= 12: band_storage gives rows
+            ("full_spd", A.T @ A / 5 + 0.5 * np.eye(5), "dense"),
+            ("rw2_n5", rw(5, 2), "dense")]                                     # (w + 1) * 2 = 6 > 5: the band would not pay
+
+
+@pytest.mark.parametrize("as_sparse", [False, True])
+@pytest.mark.parametrize("name,M,kind", _structure_matrices())
+def test_normal_structure_kind(name, M, kind, as_sparse):
+    """NormalStructure.kind for every structure class, from a dense array and from a scipy.sparse matrix, and the booleans the
+    callers ask next to the sentinel expressions they replace; NormalNormal's structure of a replicated response keeps the kind
+    (n_rep times the identity is a constant diagonal)."""
+    from openmcmc_amd.sampler.sampler import NormalNormal
+
+    dist = Normal("b", mean="mu", precision=ScaledMatrix("P", "lam"))
+    st = dist.structure({"P": sparse.csc_matrix(M) if as_sparse else M, "lam": 1.0})
+    assert st.kind == kind
+    assert st.narrow == (st.diag is not False)
+    assert st.diagonal_only == (not (st.diag is False or st.off is not None))
+    assert (st.kind == "dense") == (st.diag is False and st.band is None)
+    assert (st.kind == "identity") == (st.diag is None and st.off is None)
+    assert (st.kind == "band") == (st.band is not None) == (st.diag is False and st.band_rows() is not None)
+    rep = NormalNormal("b", Model([dist]))._replicated_structure(st, 3)
+    assert rep.kind == ("diagonal" if kind == "identity" else kind)
+    assert rep.narrow == (rep.diag is not False) and rep.diagonal_only == (not (rep.diag is False or rep.off is not None))
+    assert (rep.kind == "dense") == (rep.diag is False and rep.band is None)
+    dense = np.asarray(rep.matrix.toarray() if as_sparse else rep.matrix)
+    assert np.array_equal(dense, 3.0 * M)
+    if rep.narrow:
+        assert np.array_equal(rep.diag, np.diag(3.0 * M)) and (rep.off is None or np.array_equal(rep.off, np.diag(3.0 * M, 1)))
+    elif rep.kind == "band":
+        assert np.array_equal(rep.band, 3.0 * st.band)
+
+
+def test_identity_memo():
+    """by_identity: a hit only for the very objects the entry was made from -- not for an equal object, not for an entry that
+    sits under another object's key (an id handed out again after a collection), not when the second of two objects differs."""
+    from openmcmc_amd.memo import by_identity
+
+    made = []
+
+    def make():
+        made.append(len(made))
+        return made[-1]
+
+    memo, A, B = {}, np.arange(3.0), np.arange(3.0)
+    assert by_identity(memo, make, A) == 0 and by_identity(memo, make, A) == 0 and made == [0]    # the same object: one call
+    assert by_identity(memo, make, B) == 1 and by_identity(memo, make, A) == 0 and made == [0, 1]  # equal, another object
+    # the entry made from A under the key of B: what a recycled id looks like
+    only_b = {}
+    by_identity(only_b, lambda: None, B)
+    (key_b,) = only_b
+    planted = {}
+    by_identity(planted, lambda: "from A", A)
+    (key_a,) = planted
+    planted[key_b] = planted.pop(key_a)
+    assert by_identity(planted, lambda: "from B", B) == "from B" and by_identity(planted, lambda: "again", B) == "from B"
+    # two key objects: both must be the same
+    two, A2, B2 = {}, np.arange(3.0), np.arange(3.0)
+    assert by_identity(two, lambda: "A, B", A, B) == "A, B" and by_identity(two, lambda: "new", A, B) == "A, B"
+    assert by_identity(two, lambda: "A, B2", A, B2) == "A, B2" and by_identity(two, lambda: "A2, B", A2, B) == "A2, B"
+    (key_ab,) = [k for k, (objs, v) in two.items() if v == "A, B"]
+    (key_ab2,) = [k for k, (objs, v) in two.items() if v == "A, B2"]
+    two[key_ab2] = two[key_ab]  # first object right, second object another
+    assert by_identity(two, lambda: "made again", A, B2) == "made again"
+    assert by_identity(two, lambda: "none", A, None) == "none" and by_identity(two, lambda: "x", A, None) == "none"  # None is a key object too
+
+
 def test_manifold_mala_route_names_the_route_sample_takes():
     """ManifoldMALA.route on one hand-built state per route: numpy arrays and ChainArrays over CPU tensors, no engine ("transform"
     uploads its statistics: tests/test_transform_gpu.py asserts it)."""

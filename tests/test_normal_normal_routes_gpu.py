@@ -109,6 +109,36 @@ def check_quadratic_forms(smp, state, eng, C, tol):
             assert abs(got[c] - (r.T @ M @ r).item()) < tol * max(1.0, abs(got[c])), (key, c)
 
 
+COLD = [(P, v) for P in ("rw1", "rw2", "full_spd") for v in ("plain", "mean", "replicated+const")] + [("regression", "diag"),
+                                                                                                      ("regression", "corr")]
+
+
+@pytest.mark.parametrize("C", [3, 65])
+@pytest.mark.parametrize("matrix,variant", COLD)
+def test_residual_quad_on_a_state_no_draw_has_touched(matrix, variant, C):
+    """The checks above run after a draw and mostly read the engine's cache.  Here nothing has been drawn: residual_quad of every
+    Normal of the model takes its own path -- a shared centre, both sides sampled and three replicates of the response on the
+    tridiagonal, the band and the dense route; the weighted residual kernel and the residual formed on the device under a design
+    matrix -- against sum over the columns of r'Mr on the host.  Bar: check_quadratic_forms' 1e-10."""
+    import normal_normal_models as models
+
+    if matrix == "regression":
+        M, smp, _ = prepare(models.regression, (variant, N), C, "beta")
+    else:
+        M, smp, _ = prepare(models.smoother, (getattr(models, matrix)(N), variant, N), C, "b")
+    eng, state = M.engine, M.state
+    for key, dist in smp.model.items():
+        if not hasattr(dist, "residual_quad"):
+            continue  # (the Gamma priors of the scalars)
+        got = dist.residual_quad(state, eng, replicates=True).cpu().numpy()
+        eng.check_status()
+        for c in chains_checked(C):
+            P, _ = unscaled(dist, state, c)
+            r = host(state, key, c) - mean_of(dist, state, c)  # (n, n_rep): the mean is one column
+            assert abs(got[c] - np.sum(r * (P @ r))) < 1e-10 * max(1.0, abs(got[c])), (key, c)
+    eng.close()
+
+
 TRIDIAGONAL = ["mean_lincomb", "mean+const", "mean_lincomb+const", "two_vectors", "offset+mean", "offset+two_vectors", "replicated+const"]
 # (at n = 700 a workgroup serves a chain, the form of the kernel that takes the per-chain centre inside the launch)
 TRIDIAGONAL = [(v, N) for v in TRIDIAGONAL] + [(v, 700) for v in TRIDIAGONAL[:3]]
